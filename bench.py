@@ -14,7 +14,15 @@ matvec; steps are chained (v <- A v) with every vector resident in HBM, in tree
 order (a fixed relabelling of the unknowns: no permutation gathers on the data
 path).  fp64 throughout.  --workload mode0 instead times main.cpp's matvec
 u - K_0(sigma_s .* u) (main.cpp:125-136) with main.cpp's coefficients; the block
-run also reports that number as `mode0_matvec_per_s`.
+run also reports that number as `mode0_matvec_per_s` under --full.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the result line: the headline rate, `ms_per_step`, the setup times and
+the roofline of the two spans its timed region records.  --dump-outputs DIR then also
+writes the last timed step's output, the (blocks, N) fp64 iterate in tree order (N > 1:
+the rank's owned slice), as DIR/matvec_out.npy; the inputs are fixed, so two builds run
+with the same arguments can be compared entry for entry.  Every other leg below runs
+only with --full.
 
 N GPUs (one process per GPU, RCCL over xGMI; `bench.py --gpus N` run bare starts its
 N ranks itself under torch.distributed.run, and under a launcher WORLD_SIZE must equal
@@ -27,7 +35,7 @@ it then computes its targets into its slice of the next iterate.  Config 4 (one
 right-hand side) keeps the two-collective form: a halo all-to-all and the tier-0
 root all-gather.
 
-Also reported on the same JSON line:
+Reported on the same JSON line (all but the roofline only with --full):
   roofline      HBM roofline of the dominant kernel (the clustered M2L with the upper up
                 tiers, k_top_m2l_hc, one launch per matvec) and of the near-field sweep,
                 timed with HIP events
@@ -43,7 +51,9 @@ Also reported on the same JSON line:
                 129,600 points at d = 3 (matvec/s, roofline, rel_err vs the oracle),
                 4M points sharded over the run's GPUs (matvec/s, per-rank roofline), the
                 16-RHS fp32 mixed-precision solve (seconds, iterations, rel_err vs fp64
-                GMRES); config2 and config5 on one GPU only.
+                GMRES); config2 and config5 on one GPU only;
+  stage_ms      the M2L and near-field spans of the timed region; with --full every
+                stage, from 5 more steps after it (stage_pass).
 """
 import argparse
 import json
@@ -470,6 +480,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)  # 50 x 1.2 ms: the steady state, seconds of run time
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg: the mode-0 and deterministic matvecs, the per-stage "
+                         "timing pass, GMRES, the block solve, configs 2, 4 and 5, --verify and the CPU baseline "
+                         "(their own switches below choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (fp64, tree order) to DIR/matvec_out.npy")
     ap.add_argument("--workload", default="block", choices=["block", "mode0"])
     ap.add_argument("--sz", type=int, default=1024)
     ap.add_argument("--d", type=int, default=1)
@@ -499,6 +515,8 @@ def main():
     ap.add_argument("--config5", type=int, default=1,
                     help="secondary leg (one GPU): BASELINE configs[4], 16-RHS fp32 mixed-precision solve; 0 skips")
     args = ap.parse_args()
+    if args.verify and not args.full:
+        ap.error("--verify is a secondary leg: run it with --full")
 
     # --gpus N > 1 without a launcher: start N ranks under torch.distributed.run as a
     # child process and exit with its code (before torch or HIP is touched here, so
@@ -625,7 +643,11 @@ def main():
             dist.barrier()
         el = time.perf_counter() - t0
         roof = op.stage_times()  # per-apply averages over the timed region (HIP events)
-        times = merge_stage_times(roof, stage_pass(op, lambda: fn(v, w)))
+        if args.full:
+            times = merge_stage_times(roof, stage_pass(op, lambda: fn(v, w)))
+        else:
+            op.set_timing(0)
+            times = {"m2l": roof["m2l"], "near": roof["near"]}
         if world > 1:
             t = torch.tensor([el], device="cuda", dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -636,7 +658,7 @@ def main():
     # matvec) run first, so the headline leg below measures the GPU in the steady
     # state a long GMRES solve runs in
     sec = {}
-    if block:
+    if block and args.full:
         def mode0(x, y):
             if world == 1:
                 op.forward_tree_dev(x[0], y[0])
@@ -655,6 +677,12 @@ def main():
         sec["deterministic_matvec_per_s"] = round(args.steps / eld, 3)
         sec["deterministic_stage_ms"] = {k: round(v_, 5) for k, v_ in tds.items()}
     elapsed, times = timed(matvec, args.steps, args.warmup)
+    if args.dump_outputs:
+        # v is the last timed step's output (stage_pass wrote w only)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = v if world == 1 else v[:, ob:oe]
+        name = "matvec_out.npy" if world == 1 else f"matvec_out_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), last.cpu().numpy())
     my_stats = op.stats()
     ms = 1e3 * elapsed / args.steps
     value = args.steps / elapsed
@@ -790,7 +818,7 @@ def main():
                 "halo_bytes_received": 8 * nb * o1["halo_points"] + 8 * xchg.R * o1["need_nodes"],
                 "multipoles_received": o1["need_nodes"], "input_points_received": o1["halo_points"]})
     line.update(sec)  # mode-0 operator and deterministic block matvec (measured before the headline leg)
-    if args.gmres > 0 and block:
+    if args.full and args.gmres > 0 and block:
         # GMRES over this run's (possibly sharded) block matvec: aniso_amd.solve.gmres_dist
         # on the library's DCGS2 Arnoldi (two all-reduces of its inner products per step on
         # N > 1), one cycle of exactly --gmres steps (tol 0) from x0 = 0 (no matvec for its
@@ -834,7 +862,7 @@ def main():
                                    "rotations and residual estimate on the device; 2 all-reduces per step on N > 1), "
                                    "the next matvec enqueued before the host reads the step's estimate; tol 0 so "
                                    "exactly `steps` Arnoldi steps are timed"}
-    if args.config4_sz > 0 and block:
+    if args.full and args.config4_sz > 0 and block:
         # BASELINE configs[3]: sz = 2048 (4,194,304 points), d = 1, mode 0 -- main.cpp's GMRES
         # matvec u - K_0(sigma_s .* u), the configuration BASELINE names for 8 GPUs --
         # sharded over this run's ranks like the headline (the library's one-call exchange at
@@ -947,7 +975,7 @@ def main():
             dist.all_reduce(sq)
         line["verify_rel_err_vs_unsharded"] = float((sq[0] / sq[1]) ** 0.5)
         del ref_op
-    if world == 1 and block and not args.no_solve:
+    if args.full and world == 1 and block and not args.no_solve:
         # aniso.m:159-173 as the MATLAB caller runs it: rhs = forward(charge), u = gmres(A,
         # rhs, 400, 1e-11, 400), A(u) = u - mforward(u), through aniso_block_solve_dev
         # (Krylov basis of 401 x 5 x N doubles in HBM; wall time incl. its allocation)
@@ -965,11 +993,11 @@ def main():
                                "ms_per_iteration": round(1e3 * sel / max(abs(its), 1), 4)}
     # BASELINE's one-GPU configs[1] and configs[4] (after the block solve: their handles'
     # allocations would otherwise be recycled into the solve's 16.8 GB Krylov basis)
-    if world == 1 and block and args.config2:
+    if args.full and world == 1 and block and args.config2:
         line["config2"] = config2_leg(args, with_cpu=not args.no_cpu)
-    if world == 1 and block and args.config5:
+    if args.full and world == 1 and block and args.config5:
         line["config5"] = config5_leg(args)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         def block_check(sz):
             """x - mforward(x) (aniso.m:155) at sz: HIP harmonic block apply vs the
             oracle's per-mode composition (45 mapping calls in the reference)."""

@@ -272,7 +272,7 @@ def test_bench_sharded_path_rehearsal_two_ranks(comm, port):
         f"--master-port={port}"]
     cmd = [sys.executable] + launcher + [
         os.path.join(ROOT, "bench.py"),
-        "--gpus", "2", "--steps", "2", "--warmup", "1", "--sz", "128", "--backend", "gloo",
+        "--gpus", "2", "--steps", "2", "--warmup", "1", "--sz", "128", "--backend", "gloo", "--full",
         "--same-device", "--verify", "--no-cpu", "--comm", comm, "--gmres", "6", "--config4-sz", "256"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
@@ -284,6 +284,52 @@ def test_bench_sharded_path_rehearsal_two_ranks(comm, port):
     assert res["verify_halo_rel_err"] <= 1e-15
     assert res["gmres"]["steps"] == 6 and res["gmres"]["relres_after"] < 1.0
     assert res["config4"]["N"] == 256 * 256 and res["config4"]["matvec_per_s"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_output(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the headline leg only (no
+    secondary leg's key on its line; they need --full), K sets the timed steps, and
+    --dump-outputs writes the last timed step's output: the (blocks, N) fp64 iterate in
+    tree order, here against the same W + K chained block matvecs run in this process
+    (1e-12: fp64 sums of ~1e3 terms in an order that varies, through 4 contractions)."""
+    import subprocess
+    import sys
+
+    import aniso_amd
+
+    torch = _torch()
+    sz, ks, steps, warmup = 48, 5, 3, 1
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+           "--warmup", str(warmup), "--sz", str(sz), "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert res["steps"] == steps and res["warmup"] == warmup and res["n_gpus"] == 1
+    assert res["unit"] == "matvec/s" and res["higher_is_better"] is True and res["dtype"] == "f64"
+    assert res["ms_per_step"] > 0 and abs(res["value"] * res["ms_per_step"] / 1e3 - 1) <= 1e-3
+    for key in ("mode0_matvec_per_s", "deterministic_matvec_per_s", "gmres", "config2", "config4", "config5",
+                "block_solve", "rel_err_vs_cpu"):
+        assert key not in res, key
+    assert res["cpu_baseline"] is None and sorted(res["stage_ms"]) == ["m2l", "near"]
+    assert os.listdir(tmp_path) == ["matvec_out.npy"]
+    got = np.load(tmp_path / "matvec_out.npy")
+    a = aniso_amd.Aniso(sz, 1, ks, 0.8, 10, 4, 20)
+    xy = a.getNodes()
+    ss = np.full(a.N, 20.0)  # demo.m:15-16, the bench's coefficients
+    a.setCoeff(ss, ss + 0.2)
+    for m in range(2 * ks - 1):
+        a.cache(m)
+    perm = torch.tensor(a.tree_perm(), device="cuda", dtype=torch.int64)
+    v = torch.zeros(ks, a.N, dtype=torch.float64, device="cuda")
+    v[0] = torch.tensor(gaussian_charge(xy), device="cuda")[perm]
+    w = torch.zeros_like(v)
+    for _ in range(warmup + steps):
+        a.block_op_dev(2, v, w, tree=True)
+        v, w = w, v
+    ref = v.cpu().numpy()
+    assert got.dtype == np.float64 and got.shape == ref.shape
+    assert np.isfinite(got).all() and _rel(got, ref) <= 1e-12, _rel(got, ref)
 
 
 def test_rccl_shard_exchange_collectives_one_rank():

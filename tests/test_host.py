@@ -254,6 +254,19 @@ def test_bench_gpus_must_match_launcher_world_size():
     assert "WORLD_SIZE=1" in out.stderr
 
 
+def test_bench_verify_needs_full():
+    """--verify is one of the legs behind --full: asked for alone it is an argument error
+    (before torch or the GPU is touched), not a silently skipped check."""
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--verify"],
+                         capture_output=True, text=True, timeout=120, env=env)
+    assert out.returncode == 2
+    assert "--full" in out.stderr
+
+
 def test_fixed_size_stats_writes_its_26_entries():
     """aniso_stats keeps the contract aniso_mi355x_dev.h gives it (26 entries, the same
     values aniso_stats_n reports first) and writes nothing past them."""

@@ -1,6 +1,8 @@
 # the round-end checks on one box: the GPU suite, smoke(), one bench run
 set -o pipefail
 T=${1:-r05}
-timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > gpurun_out/${T}_gpu_tests.log 2>&1 || exit $?
-timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${T}_smoke.log 2>&1 || exit $?
-timeout -k 10 400 python -u bench.py --no-cpu > gpurun_out/${T}_bench.log 2>&1
+LOGS=${LOGS:-bench_logs}
+mkdir -p $LOGS
+timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $LOGS/${T}_gpu_tests.log 2>&1 || exit $?
+timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > $LOGS/${T}_smoke.log 2>&1 || exit $?
+timeout -k 10 400 python -u bench.py --full --no-cpu > $LOGS/${T}_bench.log 2>&1
