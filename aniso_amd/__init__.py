@@ -97,6 +97,8 @@ def lib():
             "aniso_apply_block_dev": [P, I, P, I64, I, I, ip, dp, P, I64, I, P],
             "aniso_block_op_dev": [P, I, P, I64, P, I64, I, P],
             "aniso_block_mixes": [I, D, I, dp],
+            "aniso_block_pass_plan": [I, ip, ip],
+            "aniso_block_pass_dev": [P, I, I, I, P, I64, P, I64, P],
             "aniso_block_op": [P, I, dp, dp],
             "aniso_apply_block": [P, dp, dp, D, dp],
             "aniso_shard_cuts": [P, I, lp],
@@ -420,6 +422,23 @@ class Aniso:
         _check(lib().aniso_block_op_dev(self.address, int(which), ctypes.c_void_p(x.data_ptr()), int(x.stride(0)),
                                         ctypes.c_void_p(out.data_ptr()), int(out.stride(0)), int(bool(tree)),
                                         ctypes.c_void_p(s)))
+        return out
+
+    def block_pass_dev(self, which, I, J, x, out, stream=None):
+        """One pass of the block operator beyond 8 blocks: the
+        contribution of input chunk J of x to output chunk I; which = 0 forward, 1 mforward.
+
+        x: the full (ks, N) device tensor, original order; out: (chunk, N) with chunk
+        from block_pass_plan(ks).  Unsharded handles only."""
+        import torch
+
+        chunk, _ = block_pass_plan(self.ks)
+        _dev_rows(x, self.ks, self.N, "x")
+        _dev_rows(out, chunk, self.N, "out")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _check(lib().aniso_block_pass_dev(self.address, int(which), int(I), int(J), ctypes.c_void_p(x.data_ptr()),
+                                          int(x.stride(0)), ctypes.c_void_p(out.data_ptr()), int(out.stride(0)),
+                                          ctypes.c_void_p(s)))
         return out
 
     # ---- sharded applies in two phases around the caller's root all-gather
@@ -854,6 +873,14 @@ def block_mixes(nb, g, chi=True):
     m = np.zeros((2 * nb - 1) * nb * nb)
     _check(lib().aniso_block_mixes(int(nb), float(g), int(bool(chi)), _dp(m)))
     return m.reshape(2 * nb - 1, nb, nb)
+
+
+def block_pass_plan(ks):
+    """(chunk, nchunks): the block operator of ks blocks runs as nchunks x nchunks passes
+    over chunks of `chunk` blocks (ks <= 8: (ks, 1); else (8, ceil(ks / 8)))."""
+    chunk, n = ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib().aniso_block_pass_plan(int(ks), ctypes.byref(chunk), ctypes.byref(n)))
+    return chunk.value, n.value
 
 
 def version():

@@ -843,11 +843,16 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     const int64_t obase = treeOut ? plan.ownBegin : 0;
     const double scale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
     HarmWeights hw;
-    const bool harmonic = harmonicWeights(K, nterm, ids, mixes, hw);
+    // one pass of a block operator of more than kMaxRhs blocks (blockPass): its weights
+    // come with it, and it runs the plain harmonic launches in their offset form; without
+    // the mode-shared caches the pass's sub-mixes take the per-mode stream like any mix
+    const HarmWindow* const win = passWin && useAtt && attReady && plan.nearPartTotal == 0 ? passWin : nullptr;
+    if (win) hw = passHw;
+    const bool harmonic = win ? true : harmonicWeights(K, nterm, ids, mixes, hw);
     // the harmonic block apply runs its near field + corrections (they write `out`)
     // on a side stream beside the M2L (it writes the locals), forked as soon as the
     // weighted charges are complete: after the last up tier with a P2M leaf
-    const ModeArgs* tab = modeTable(K, nterm, ids, mixes);
+    const ModeArgs* tab = win ? nullptr : modeTable(K, nterm, ids, mixes);  // (the harmonic launches read no mode table)
     const CorrFold& cf = corrTable(K, nterm, ids, mixes);
     const NearCorr nc{dNearCorrRow.as<uint16_t>(), dPerm.as<int>(), dIperm.as<int>(), dCT.as<double>(),
                       cf.Wc.as<double>(), cf.Wm.as<double>(), P};
@@ -858,7 +863,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     const bool upPartial = oneXActive && upActive && phase != 0;
     // the upper tiers ride in the M2L launch (k_top_m2l_hc) when every leaf is in the
     // bottom tier: the near field then forks after it
-    const bool topFused = harmonic && (mask & kStageFar) && topFusedOn() && !upPartial;
+    const bool topFused = harmonic && (mask & kStageFar) && topFusedOn() && !upPartial && !win;
     // ANISO_NEAR_IN_TOP: the near field (+ corrections) as the last blocks of that
     // launch (the one-block M2L form; a shard's phase 1 then leaves it to phase 2)
     const bool ringOn = hmRing > 0 && hm_ring_xl(K, plan.hmMaxLds, hmRing) >= 0;
@@ -964,7 +969,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
                            dNearPts.as<int>(), hmKOff, dAttNear.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
                            dSigDiag.as<double>(), hw, dFT.as<double>(), operm, obase, ldo, mask, scale, out, hmLoc,
                            dNsPtr.as<int64_t>(), dNsPts.as<int>(), plan.nsMax, plan.nearCorrOk ? &nc : nullptr,
-                           nearWpe, sn, &nin);
+                           nearWpe, sn, &nin, win);
         } else if (plan.nearPartTotal > 0) {
             // symmetric U storage (K = 1 handles): one launch per term; the transposed
             // products go to partials summed over the terms
@@ -991,7 +996,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         span(6, e1, e2);
         if (fork) HIP_CHECK(hipEventRecord(evJoin, side));
     };
-    const bool clustered = harmonic && useClusters;
+    const bool clustered = harmonic && useClusters && !win;  // a pass: the per-target launch (its offset form)
     const int ncl = (int)plan.hmClPtr.size() - 1;
     HcArgs hca{dHmClPtr.as<int>(), dHmTgt.as<int>(), dHmPtr.as<int64_t>(), dHmNDir.as<int>(), dHmSrc.as<int>(),
                      dHmBlk.as<int>(), dHmSlot.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(),
@@ -1172,7 +1177,8 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         } else if (harmonic) {
             launch_m2l_hm(K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
                           dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(),
-                          dNrx.as<double>(), dNry.as<double>(), P, hw, dMult.as<double>(), dLocal.as<double>(), s);
+                          dNrx.as<double>(), dNry.as<double>(), P, hw, dMult.as<double>(), dLocal.as<double>(), s,
+                          win);
         } else {
             launch_m2l(K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dM2LPtr.as<int64_t>(), dM2LNDir.as<int>(),
                        dM2LCanonBase.as<int>(), dM2LOutSlot.as<int>(), dM2LSrc.as<int>(), tab, nterm,
@@ -1233,8 +1239,14 @@ void Operator::blockOpDev(int which, const double* x, int64_t ldx, double* out, 
                           hipStream_t s, double gval, const double* sigT, int phase, double* rootsSend,
                           const double* rootsRecv) {
     if (which < 0 || which > 2) throw std::invalid_argument("block operator: which must be 0, 1 or 2");
+    checkBlockLimit(phase != 0);
     if (!coeffSet) throw std::runtime_error("block operator before setCoeff");
     ensureDevice();
+    if (ks > kMaxRhs) {  // more blocks than one harmonic launch holds: P x P passes of 8
+        blockOpPasses(which, x, ldx, out, ldo, treeIo, s, std::isnan(gval) ? g : gval,
+                      sigT ? sigT : dSigmaT.as<double>());
+        return;
+    }
     const int nb = ks, nm = 2 * ks - 1;
     const auto mix = blockMixes(nb, std::isnan(gval) ? g : gval, which != 0);
     const double* sig = sigT ? sigT : dSigmaT.as<double>();
@@ -1270,7 +1282,121 @@ void Operator::blockOpDev(int which, const double* x, int64_t ldx, double* out, 
     if (phase != 1) launch_sub_slice(nOut, nb, xo, ldx, dBlk.as<double>(), nOut, out, ldo, s);
 }
 
+// ---- more than kMaxRhs blocks ----
+//
+// aniso.m loops over any number of blocks (aniso.m:139-157); the harmonic kernels hold
+// kMaxRhs.  The identity of harmonic.hip does not depend on the block count, so the
+// blocks are cut into P = ceil(ks / 8) chunks of 8 (the last zero-padded) and the
+// operator into P x P passes: pass (I, J) adds to output rows 8 I .. 8 I + 7
+//     (E / r) T_{8I+i}(c) sum_{b < 8} hw_{8J+b} T_{8J+b}(c) x_{8J+b},
+// over the M2L and the near field, with the correction stencils folded from the
+// (2 ks - 1) x 8 x 8 sub-block of the mixes and the r = 0 diagonal term only at I == J.
+// Every pass reads the mode-shared E caches once (P^2 reads per block apply) and no
+// per-mode operator cache.
+
+void Operator::blockPassPlan(int ks, int* chunk, int* nchunks) {
+    if (ks < 1) throw std::invalid_argument("block count must be >= 1");
+    *chunk = ks <= kMaxRhs ? ks : kMaxRhs;
+    *nchunks = ks <= kMaxRhs ? 1 : (ks + kMaxRhs - 1) / kMaxRhs;
+}
+
+// ks > kMaxRhs runs on one unsharded handle only; raised before anything is launched
+// or any pending-call state is set
+void Operator::checkBlockLimit(bool shardedCall) const {
+    if (ks > kMaxRhs && (plan.nranks > 1 || shardedCall))
+        throw std::invalid_argument("block operator: ks = " + std::to_string(ks) + " blocks on a sharded handle (more than " +
+                                    std::to_string(kMaxRhs) + " blocks run on unsharded handles only)");
+}
+
+// One pass: input chunk J of x (ks rows) to the 8 rows out8 of output chunk I.  sig:
+// sigma_s in tree order, or nullptr (forward).  mix: blockMixes(ks, g, chi).
+void Operator::blockPass(int I, int J, const std::vector<double>& mix, const double* x, int64_t ldx, bool tree,
+                         const double* sig, double* out8, int64_t ldo, hipStream_t s) {
+    constexpr int K = kMaxRhs;
+    const int nm = 2 * ks - 1, i0 = I * K, b0 = J * K;
+    const int64_t N = geo.N;
+    if (ldx < N || ldo < N) throw std::invalid_argument("block apply: leading dimension too small");
+    auto mx = [&](int m, int i, int b) { return i < ks && b < ks ? mix[((size_t)m * ks + i) * ks + b] : 0.0; };
+    std::vector<double> sub((size_t)nm * K * K);
+    for (int m = 0; m < nm; ++m)
+        for (int i = 0; i < K; ++i)
+            for (int b = 0; b < K; ++b) sub[((size_t)m * K + i) * K + b] = mx(m, i0 + i, b0 + b);
+    std::vector<int> ids(nm);
+    for (int m = 0; m < nm; ++m) ids[m] = m;
+    // the pass's harmonic weights straight from the block weights: output row 0 holds
+    // hw_B at mode B (w_0, or 2 w_B: j = B and j = -B), the mode-0 weight of row i is w_i
+    HarmWeights hw;
+    std::memset(&hw, 0, sizeof(hw));
+    for (int b = 0; b < K; ++b) hw.hw[b] = b0 + b < ks ? mx(b0 + b, 0, b0 + b) : 0.0;
+    for (int i = 0; i < K; ++i) {
+        hw.om[i] = i0 + i < ks ? 1.0 : 0.0;
+        hw.dw[i] = I == J ? mx(0, i0 + i, i0 + i) : 0.0;
+    }
+    // the chunk's rows of x; the last chunk zero-padded to 8
+    const int nin = std::min(K, ks - b0);
+    const double* xin = x + (size_t)b0 * ldx;
+    int64_t ldin = ldx;
+    if (nin < K) {
+        dPassIn.alloc((size_t)K * N * sizeof(double));
+        HIP_CHECK(hipMemsetAsync(dPassIn.p, 0, dPassIn.bytes, s));
+        HIP_CHECK(hipMemcpy2DAsync(dPassIn.p, N * sizeof(double), xin, ldx * sizeof(double), N * sizeof(double), nin,
+                                   hipMemcpyDeviceToDevice, s));
+        xin = dPassIn.as<double>();
+        ldin = N;
+    }
+    const HarmWindow win{i0, b0};
+    struct Restore {
+        const HarmWindow*& w;
+        ~Restore() { w = nullptr; }
+    } restore{passWin};
+    passWin = &win;
+    passHw = hw;
+    applyBlock(K, xin, ldin, tree, sig, nm, ids.data(), sub.data(), out8, ldo, tree, s, kStageAll);
+}
+
+void Operator::blockOpPasses(int which, const double* x, int64_t ldx, double* out, int64_t ldo, bool treeIo,
+                             hipStream_t s, double gval, const double* sig) {
+    constexpr int K = kMaxRhs;
+    const int P = (ks + K - 1) / K;
+    const int64_t N = geo.N;
+    if (ldx < N || ldo < N) throw std::invalid_argument("block apply: leading dimension too small");
+    const auto mix = blockMixes(ks, gval, which != 0);
+    dPassOut.alloc((size_t)K * N * sizeof(double));
+    double* acc = out;
+    int64_t lda = ldo;
+    if (which == 2) {  // x - mforward(x): the passes sum into dBlk
+        dBlk.alloc((size_t)ks * N * sizeof(double));
+        acc = dBlk.as<double>();
+        lda = N;
+    }
+    for (int I = 0; I < P; ++I)
+        for (int J = 0; J < P; ++J) {
+            blockPass(I, J, mix, x, ldx, treeIo, which != 0 ? sig : nullptr, dPassOut.as<double>(), N, s);
+            launch_add_rows(N, std::min(K, ks - I * K), dPassOut.as<double>(), N, acc + (size_t)I * K * lda, lda,
+                            J > 0 ? 1 : 0, s);
+        }
+    if (which == 2) launch_sub_slice(N, ks, x, ldx, dBlk.as<double>(), N, out, ldo, s);
+}
+
+void Operator::blockPassDev(int which, int I, int J, const double* x, int64_t ldx, double* out, int64_t ldo,
+                            hipStream_t s) {
+    if (which < 0 || which > 1) throw std::invalid_argument("block pass: which must be 0 or 1");
+    if (plan.nranks > 1) throw std::invalid_argument("block pass: unsharded handles only");
+    int chunk = 0, P = 0;
+    blockPassPlan(ks, &chunk, &P);
+    if (I < 0 || I >= P || J < 0 || J >= P) throw std::invalid_argument("block pass: chunk index out of range");
+    if (!coeffSet) throw std::runtime_error("block operator before setCoeff");
+    ensureDevice();
+    if (P == 1) {  // one pass is the operator itself
+        blockOpDev(which, x, ldx, out, ldo, false, s);
+        return;
+    }
+    const auto mix = blockMixes(ks, g, which != 0);
+    blockPass(I, J, mix, x, ldx, false, which != 0 ? dSigmaT.as<double>() : nullptr, out, ldo, s);
+}
+
 void Operator::blockOpHost(int which, const double* u, const double* sigmaS, double gval, double* out) {
+    checkBlockLimit(false);
     if (plan.nranks != 1) throw std::logic_error("host block operator on a sharded handle");
     if (!coeffSet) throw std::runtime_error("block operator before setCoeff");
     ensureDevice();
@@ -1989,6 +2115,7 @@ bool Operator::oneExchangeUsable(int which) {
 }
 
 void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s) {
+    checkBlockLimit(true);
     if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
     if (ldx < geo.N || ldy < geo.N) throw std::invalid_argument("sharded block operator: leading dimension below N");
     ensureDevice();

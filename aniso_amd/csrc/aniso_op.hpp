@@ -102,6 +102,12 @@ public:
     void blockOpHost(int which, const double* u, const double* sigmaS, double gval, double* out);
     // the (2 nb - 1) mode mixes of forward (chi = false) or mforward (chi = true)
     static std::vector<double> blockMixes(int nb, double g, bool chi);
+    // More than kMaxRhs blocks: the block operator runs as
+    // nchunks x nchunks passes over chunks of `chunk` blocks (ks <= 8: one pass of ks).
+    static void blockPassPlan(int ks, int* chunk, int* nchunks);
+    // one pass (development interface): the contribution of input chunk J of x (ks x N,
+    // original order) to output chunk I, out (chunk x N); which = 0 forward, 1 mforward
+    void blockPassDev(int which, int I, int J, const double* x, int64_t ldx, double* out, int64_t ldo, hipStream_t s);
 
     // --- extensions
     void setShard(int rank, int nranks);
@@ -202,6 +208,9 @@ public:
     // launches of their own; ANISO_DET_PER_TARGET=1 keeps the round-2 form instead (one
     // wave per target, every sum in a fixed order, every block read from both ends)
     void setDeterministic(bool on) {
+        if (on && ks > kMaxRhs)
+            throw std::invalid_argument("deterministic applies: not with more than " + std::to_string(kMaxRhs) +
+                                        " blocks (ks = " + std::to_string(ks) + ")");
         detSums = on && !detPerTarget;
         useClusters = !(on && detPerTarget);
     }
@@ -254,6 +263,15 @@ private:
         }
     } pendCall;
     void pendingCall(int phase, const PendingCall& c);
+    // ks > kMaxRhs: the passes of the block operator (blockOpDev), one pass, the limit
+    void blockOpPasses(int which, const double* x, int64_t ldx, double* out, int64_t ldo, bool treeIo, hipStream_t s,
+                       double gval, const double* sig);
+    void blockPass(int I, int J, const std::vector<double>& mix, const double* x, int64_t ldx, bool tree,
+                   const double* sig, double* out8, int64_t ldo, hipStream_t s);
+    void checkBlockLimit(bool shardedCall) const;
+    const HarmWindow* passWin = nullptr;  // set by blockPass for its applyBlock
+    HarmWeights passHw{};
+    DevBuf dPassIn, dPassOut;  // a pass's zero-padded input chunk, its 8 output rows
     void ensureWork(int K);  // work arrays for K right-hand sides
     const ModeArgs* modeTable(int K, int nterm, const int* ids, const double* mixes);
     // harmonic (mode-shared) block apply, DESIGN.md §3.9: the E caches of every

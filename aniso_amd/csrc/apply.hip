@@ -89,6 +89,17 @@ __global__ void k_sub_slice(int64_t n, int nrhs, const double* __restrict__ x, i
     y[r * ldy + j] = x[r * ldx + j] - a[r * lda + j];
 }
 
+// out[i] = a[i] (add == 0) or out[i] += a[i] for each right-hand side: the sum over the
+// passes of a block operator of more than kMaxRhs blocks (Operator::blockOpPasses)
+__global__ void k_add_rows(int64_t n, int nrhs, const double* __restrict__ a, int64_t lda, double* __restrict__ out,
+                           int64_t ldo, int add) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * nrhs) return;
+    const int64_t r = i / n, j = i - r * n;
+    const double v = a[r * lda + j];
+    out[r * ldo + j] = add ? out[r * ldo + j] + v : v;
+}
+
 // ----------------------------------------------------------------- up pass
 
 // One partial task of the upper multipoles (Plan::xUpTask): this rank's
@@ -1123,6 +1134,13 @@ void launch_sub_slice(int64_t n, int nrhs, const double* x, int64_t ldx, const d
                       int64_t ldy, hipStream_t s) {
     if (n <= 0 || nrhs <= 0) return;
     k_sub_slice<<<blocks_for(n * nrhs, 256), 256, 0, s>>>(n, nrhs, x, ldx, a, lda, y, ldy);
+    HIP_LAUNCH_CHECK();
+}
+
+void launch_add_rows(int64_t n, int nrhs, const double* a, int64_t lda, double* out, int64_t ldo, int add,
+                     hipStream_t s) {
+    if (n <= 0 || nrhs <= 0) return;
+    k_add_rows<<<blocks_for(n * nrhs, 256), 256, 0, s>>>(n, nrhs, a, lda, out, ldo, add);
     HIP_LAUNCH_CHECK();
 }
 

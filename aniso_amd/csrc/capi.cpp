@@ -333,6 +333,24 @@ int aniso_block_op_end_dev(aniso_handle h, int which, const double* x, int64_t l
     });
 }
 
+int aniso_block_pass_plan(int ks, int* chunk, int* nchunks) {
+    return guarded([&] {
+        CHECK_PTR(chunk);
+        CHECK_PTR(nchunks);
+        aniso::Operator::blockPassPlan(ks, chunk, nchunks);
+    });
+}
+
+int aniso_block_pass_dev(aniso_handle h, int which, int I, int J, const double* x, int64_t ldx, double* out,
+                         int64_t ldo, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(x);
+        CHECK_PTR(out);
+        get(h).blockPassDev(which, I, J, x, ldx, out, ldo, (hipStream_t)stream);
+    });
+}
+
 int aniso_block_op(aniso_handle h, int which, const double* u, double* out) {
     ENTER(h);
     return guarded([&] {

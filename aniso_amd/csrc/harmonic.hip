@@ -114,6 +114,87 @@ __device__ __forceinline__ void hm_entry(double e, double dx, double dy2, const 
     for (int i = 0; i < K; ++i) o[i] = __builtin_fma(T[i], av, o[i]);
 }
 
+// The offset form of hm_entry (more than kMaxRhs blocks): one pass
+// of the block operator takes K input blocks b0 .. b0 + K - 1 to K output blocks
+// i0 .. i0 + K - 1,
+//     o[i] += T_{i0+i}(c) (E / r) V,   V = sum_b T_{b0+b}(c) xw[b]   (xw[b] = hw_{b0+b} x_{b0+b}).
+// i0 and b0 are wave-uniform run-time values: for each window the three-term recurrence
+// runs from (T_0, T_1) to the window's start in a uniform loop and the window is then
+// unrolled from its two seeds.  The input window is consumed into V before the output
+// window is formed, so two values of T per row are live at a time.
+template <bool OFF>
+struct HarmArg : HarmWeights {};
+template <>
+struct HarmArg<true> : HarmWeights {
+    int i0, b0;  // first output / input block of the pass
+};
+static_assert(sizeof(HarmArg<false>) == sizeof(HarmWeights), "the flag-off kernels take HarmWeights as it is");
+
+template <bool OFF>
+static HarmArg<OFF> harm_arg(const HarmWeights& hw, const HarmWindow* win) {
+    HarmArg<OFF> a;
+    static_cast<HarmWeights&>(a) = hw;
+    if constexpr (OFF) {
+        a.i0 = win->i0;
+        a.b0 = win->b0;
+    }
+    return a;
+}
+
+// A lane's four rows share the uniform loops: four independent chains.
+template <int K, bool guard0, int NR = 2>
+__device__ __forceinline__ void hm_rows_win(const double (&e)[4], const double (&dx)[4], const double (&dy2)[4], int i0,
+                                            int b0, const double (&xw)[K], double (&o)[4][K]) {
+    static_assert(K >= 2, "a window holds at least T_n and T_{n+1}");
+    double c2[4], er[4], t0[4], t1[4], v[4];
+    auto step = [&](int j) {  // (T_n, T_{n+1}) -> (T_{n+1}, T_{n+2}); returns T_{n+2}
+        const double t = __builtin_fma(c2[j], t1[j], -t0[j]);
+        t0[j] = t1[j];
+        t1[j] = t;
+        return t;
+    };
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double r2 = __builtin_fma(dx[j], dx[j], dy2[j]);
+        if constexpr (guard0) r2 = __builtin_fmax(r2, 1e-300);
+        const double ri = rsqrt_nr<NR>(r2);
+        const double c = dx[j] * ri;
+        c2[j] = c + c;
+        er[j] = e[j] * ri;
+        t0[j] = 1.0;
+        t1[j] = c;
+    }
+#pragma nounroll
+    for (int n = 0; n < b0; ++n)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) (void)step(j);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = __builtin_fma(t1[j], xw[1], t0[j] * xw[0]);
+#pragma unroll
+    for (int b = 2; b < K; ++b)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = __builtin_fma(step(j), xw[b], v[j]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        v[j] *= er[j];  // (E / r) V
+        t0[j] = 1.0;
+        t1[j] = 0.5 * c2[j];
+    }
+#pragma nounroll
+    for (int n = 0; n < i0; ++n)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) (void)step(j);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        o[j][0] = __builtin_fma(t0[j], v[j], o[j][0]);
+        o[j][1] = __builtin_fma(t1[j], v[j], o[j][1]);
+    }
+#pragma unroll
+    for (int i = 2; i < K; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j][i] = __builtin_fma(step(j), v[j], o[j][i]);
+}
+
 // ----------------------------------------------------------------- M2L
 
 // M2L over V then X (bbfmm.h:1051-1065) for every mode of the block matvec: one
@@ -129,15 +210,21 @@ __device__ __forceinline__ void hm_entry(double e, double dx, double dy2, const 
 // then loading rows 4q..4q+3 of its column with stride 16 (each of the 4 loads
 // covers four 128-B lines across the wave).  Plain loads: the partner's read of a
 // shared block should find it in the Infinity Cache.
-template <int K, int PG, int NR, int WPE>
+// OFF: the offset form (hm_rows_win; one pass of a block operator of more than kMaxRhs blocks)
+template <int K, int PG, int NR, int WPE, bool OFF = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) k_m2l_hm(int ntgt, int xcd, const int* __restrict__ tgt,
                                                 const int64_t* __restrict__ ptr, const int* __restrict__ src,
                                                 const int* __restrict__ blk,
                                                 const double* __restrict__ E, const double* __restrict__ ncx,
                                                 const double* __restrict__ ncy, const double* __restrict__ nrx,
                                                 const double* __restrict__ nry, const Params* __restrict__ P,
-                                                HarmWeights hw, const double* __restrict__ mult,
+                                                HarmArg<OFF> hw, const double* __restrict__ mult,
                                                 double* __restrict__ local) {
+    int i0 = 0, b0 = 0;
+    if constexpr (OFF) {
+        i0 = hw.i0;
+        b0 = hw.b0;
+    }
     const int bid = xcd ? xcd_tile((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(bid * (int)(blockDim.x / kWave) + (int)(threadIdx.x / kWave));
     const int lane = threadIdx.x & (kWave - 1);
@@ -188,7 +275,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 #pragma unroll
                 for (int b = 0; b < K; ++b) xw[b] = hw.hw[b] * xm[g][b];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) hm_entry<K, false, NR>(e4[g][j], ax - bx[j], dy2, xw, c[j]);
+                for (int j = 0; j < 4; ++j) {
+                    if constexpr (!OFF) hm_entry<K, false, NR>(e4[g][j], ax - bx[j], dy2, xw, c[j]);
+                }
+                if constexpr (OFF) {
+                    const double dxs[4] = {ax - bx[0], ax - bx[1], ax - bx[2], ax - bx[3]};
+                    const double dys[4] = {dy2, dy2, dy2, dy2};
+                    hm_rows_win<K, false, NR>(e4[g], dxs, dys, i0, b0, xw, c);
+                }
             }
         }
     }
@@ -976,8 +1070,8 @@ __device__ __forceinline__ void m2l_cluster_form(int cid, const HcArgs& a, doubl
     else m2l_hcr_cluster<K, NR, D, XL>(cid, a, sm);
 }
 
-template <int K, int U, int NR, bool FUSE, bool SYM = false, bool UP = false>
-__device__ __forceinline__ void near_hs_group(int g, const NearHsArgs& n, double* tab);
+template <int K, int U, int NR, bool FUSE, bool SYM = false, bool UP = false, bool OFF = false>
+__device__ __forceinline__ void near_hs_group(int g, const NearHsArgs& n, double* tab, int i0 = 0, int b0 = 0);
 
 // NEAR: the staged near field's groups (k_near_hs with fused corrections) are the last
 // blocks (ANISO_NEAR_IN_TOP).  The dispatcher hands out blocks in
@@ -1033,16 +1127,22 @@ k_top_m2l_hc(UpArgs u, TopArgs t, HcArgs a, NearHsArgs n) {
 // 4rq..4rq+3 for its columns, U columns in flight; the sources' points and charges
 // are read straight from pxT / pyT / fT (the lanes of a column share the lines).
 // out (stored, not added) = scale * (sum over sources + the mode-0 diagonal).
-template <int K, int G, int U, int NR, bool XCD = false>
+// OFF: the offset form (hm_rows_win).
+template <int K, int G, int U, int NR, bool XCD = false, bool OFF = false>
 __global__ void __launch_bounds__(256) k_near_hm(int nl, const int4* __restrict__ leafInfo,
                                                  const int64_t* __restrict__ nearPtsPtr,
                                                  const int* __restrict__ nearPts, const int64_t* __restrict__ nearKOff,
                                                  const double* __restrict__ E, const double* __restrict__ pxT,
                                                  const double* __restrict__ pyT, const double* __restrict__ sigDiag,
-                                                 HarmWeights hw, const double* __restrict__ fT,
+                                                 HarmArg<OFF> hw, const double* __restrict__ fT,
                                                  const int* __restrict__ operm, int64_t obase, int64_t ldo,
                                                  int flags, double scale, double* __restrict__ out) {
     static_assert(G == 16 || G == 64, "leaf group of 16 or 64 lanes");
+    int i0 = 0, b0 = 0;
+    if constexpr (OFF) {
+        i0 = hw.i0;
+        b0 = hw.b0;
+    }
     constexpr int KS = kStride<K>;
     const int gl = threadIdx.x & (G - 1);
     const int bid = XCD ? xcd_tile((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;  // XCD: contiguous leaves per L2
@@ -1112,7 +1212,16 @@ __global__ void __launch_bounds__(256) k_near_hm(int nl, const int4* __restrict_
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const double dy = sy[u] - ty[j];
-                        hm_entry<K, true, NR>(e4[j], sx[u] - tx[j], dy * dy, xw, a[j]);
+                        if constexpr (!OFF) hm_entry<K, true, NR>(e4[j], sx[u] - tx[j], dy * dy, xw, a[j]);
+                    }
+                    if constexpr (OFF) {
+                        double dxs[4], dys[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            dxs[j] = sx[u] - tx[j];
+                            dys[j] = (sy[u] - ty[j]) * (sy[u] - ty[j]);
+                        }
+                        hm_rows_win<K, true, NR>(e4, dxs, dys, i0, b0, xw, a);
                     }
                 }
             }
@@ -1292,8 +1401,10 @@ __device__ __forceinline__ void near_up_tail(int g, bool active, int nT, int64_t
     }
 }
 
-template <int K, int U, int NR, bool FUSE, bool SYM, bool UP>
-__device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, double* tab) {
+// OFF: the offset form (hm_rows_win with the pass's windows i0, b0; directed storage only)
+template <int K, int U, int NR, bool FUSE, bool SYM, bool UP, bool OFF>
+__device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, double* tab, int i0, int b0) {
+    static_assert(!(OFF && (SYM || UP)), "the offset form: the plain staged near field");
     constexpr int KS = kStride<K>;
     constexpr int RW = kTabRow<K>;  // table row: x, y, the charges (padded)
     const int nl = n.nl;
@@ -1407,7 +1518,16 @@ __device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, 
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const double dy = sy - ty[j];
-                    hm_entry<K, true, NR>(e4[j], sx - tx[j], dy * dy, xw, a[j]);
+                    if constexpr (!OFF) hm_entry<K, true, NR>(e4[j], sx - tx[j], dy * dy, xw, a[j]);
+                }
+                if constexpr (OFF) {
+                    double dxs[4], dys[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        dxs[j] = sx - tx[j];
+                        dys[j] = (sy - ty[j]) * (sy - ty[j]);
+                    }
+                    hm_rows_win<K, true, NR>(e4, dxs, dys, i0, b0, xw, a);
                 }
             }
         };
@@ -1568,12 +1688,23 @@ static size_t near_hs_lds(const NearHsArgs& n) {
 #ifndef ANISO_NEAR_SYM_WPE
 #define ANISO_NEAR_SYM_WPE 1
 #endif
-template <int K, int U, int NR, bool FUSE, bool W4 = false, bool SYM = false, bool UP = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W4 ? 4 : SYM ? ANISO_NEAR_SYM_WPE : 1))) k_near_hs(NearHsArgs n) {
+template <bool OFF>
+struct NearHsArg : NearHsArgs {};
+template <>
+struct NearHsArg<true> : NearHsArgs {
+    int i0, b0;  // the offset form's windows (HarmArg)
+};
+static_assert(sizeof(NearHsArg<false>) == sizeof(NearHsArgs), "the flag-off kernels take NearHsArgs as it is");
+
+template <int K, int U, int NR, bool FUSE, bool W4 = false, bool SYM = false, bool UP = false, bool OFF = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W4 ? 4 : SYM ? ANISO_NEAR_SYM_WPE : 1))) k_near_hs(NearHsArg<OFF> n) {
     extern __shared__ double tab[];
     // the fused top-of-tree launch's counters (the bottom tier launch that zeroes them is skipped)
     if (n.zeroCnt && blockIdx.x == 0 && threadIdx.x <= kMaxTopTiers) n.zeroCnt[threadIdx.x] = 0u;
-    near_hs_group<K, U, NR, FUSE, SYM, UP>(n.grpList ? n.grpList[blockIdx.x] : (int)blockIdx.x, n, tab);
+    if constexpr (OFF)
+        near_hs_group<K, U, NR, FUSE, SYM, UP, true>(n.grpList ? n.grpList[blockIdx.x] : (int)blockIdx.x, n, tab, n.i0,
+                                                     n.b0);
+    else near_hs_group<K, U, NR, FUSE, SYM, UP>(n.grpList ? n.grpList[blockIdx.x] : (int)blockIdx.x, n, tab);
 }
 
 
@@ -1592,11 +1723,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W4 ? 4
 // per SIMD (measured best, r01e)
 void launch_m2l_hm(int K, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk, const double* E,
                    const double* ncx, const double* ncy, const double* nrx, const double* nry, const Params* P,
-                   const HarmWeights& hw, const double* mult, double* local, hipStream_t s) {
+                   const HarmWeights& hw, const double* mult, double* local, hipStream_t s, const HarmWindow* win) {
     if (ntgt <= 0) return;
     const unsigned nb = blocks_for((int64_t)ntgt * kWave, 256);
+    if (win) {  // one pass of a block operator of more than kMaxRhs blocks: the offset form, K = kMaxRhs only
+        if (K != kMaxRhs) throw std::invalid_argument("harmonic M2L: the offset form takes 8 blocks per pass");
+        // 2 waves per SIMD: the window form needs ~250 VGPRs with two blocks in flight (it
+        // spills at 3 and 4 waves; one block in flight needs 175, still over 3 waves' 168)
+        k_m2l_hm<kMaxRhs, 2, 2, 2, true><<<nb, 256, 0, s>>>(ntgt, 0, tgt, ptr, src, blk, E, ncx, ncy, nrx, nry, P,
+                                                            harm_arg<true>(hw, win), mult, local);
+        HIP_LAUNCH_CHECK();
+        return;
+    }
     ANISO_HM_DISPATCH_K(K, (k_m2l_hm<KK, 2, 2, 4><<<nb, 256, 0, s>>>(ntgt, 0, tgt, ptr, src, blk, E, ncx, ncy, nrx, nry,
-                                                                      P, hw, mult, local)));
+                                                                      P, harm_arg<false>(hw, nullptr), mult, local)));
     HIP_LAUNCH_CHECK();
 }
 
@@ -1829,8 +1969,13 @@ bool launch_near_hm(int K, int nl, int maxLeaf, const int4* leafInfo, const int6
                     const int64_t* nearKOff, const double* E, const double* pxT, const double* pyT,
                     const double* sigDiag, const HarmWeights& hw, const double* fT, const int* operm, int64_t obase,
                     int64_t ldo, int flags, double scale, double* out, const uint16_t* nearLoc, const int64_t* nsPtr,
-                    const int* nsPts, int nsMax, const NearCorr* corr, int wpe, hipStream_t s, const NearHsArgs* in) {
+                    const int* nsPts, int nsMax, const NearCorr* corr, int wpe, hipStream_t s, const NearHsArgs* in,
+                    const HarmWindow* win) {
     if (nl <= 0) return false;
+    // one pass of a block operator of more than kMaxRhs blocks: the offset form, K = kMaxRhs,
+    // the plain directed kernels only
+    if (win && (K != kMaxRhs || (in && (in->upMult || in->colDst))))
+        throw std::invalid_argument("harmonic near field: the offset form takes 8 blocks per pass, directed storage");
     if (near_hs_staged(nl, maxLeaf, nsMax, nearLoc)) {  // sources staged in LDS (k_near_hs)
         unsigned ng = (unsigned)((nl + 15) / 16);
         // the corrections ride along when the table is loaded (near field on)
@@ -1875,6 +2020,20 @@ bool launch_near_hm(int K, int nl, int maxLeaf, const int4* leafInfo, const int6
             n.grpIn = in->grpIn;
             n.grpSlots = in->grpSlots;
         }
+        if (win) {
+            NearHsArg<true> na;
+            static_cast<NearHsArgs&>(na) = n;
+            na.i0 = win->i0;
+            na.b0 = win->b0;
+            const size_t shm = near_hs_lds<kMaxRhs>(n);
+            auto f = fuse ? k_near_hs<kMaxRhs, 2, 2, true, false, false, false, true>
+                          : k_near_hs<kMaxRhs, 2, 2, false, false, false, false, true>;
+            f<<<ng, 256, shm, s>>>(na);
+            HIP_LAUNCH_CHECK();
+            return fuse;
+        }
+        NearHsArg<false> na;
+        static_cast<NearHsArgs&>(na) = n;
         ANISO_HM_DISPATCH_K(K, ({
             const size_t shm = near_hs_lds<KK>(n);
             auto f = n.colDst ? (fuse ? k_near_hs<KK, 4, 2, true, false, true> : k_near_hs<KK, 4, 2, false, false, true>)
@@ -1882,15 +2041,22 @@ bool launch_near_hm(int K, int nl, int maxLeaf, const int4* leafInfo, const int6
                      : fuse ? (n.upMult ? k_near_hs<KK, 2, 2, true, true, false, true>
                                : wpe == 4 ? k_near_hs<KK, 2, 2, true, true> : k_near_hs<KK, 2, 2, true>)
                             : (wpe == 4 ? k_near_hs<KK, 2, 2, false, true> : k_near_hs<KK, 2, 2, false>);
-            f<<<ng, 256, shm, s>>>(n);
+            f<<<ng, 256, shm, s>>>(na);
         }));
         HIP_LAUNCH_CHECK();
         return fuse;
     }
-#define ANISO_NEAR_HM(G)                                                                                      \
-    ANISO_HM_DISPATCH_K(K, (k_near_hm<KK, G, 4, 2><<<blocks_for((int64_t)nl * G, 256), 256, 0, s>>>(           \
-                               nl, leafInfo, nearPtsPtr, nearPts, nearKOff, E, pxT, pyT, sigDiag, hw, fT, operm, \
-                               obase, ldo, flags, scale, out)))
+// (the offset form takes 2 columns per step: with 4 its windows push it past 256 VGPRs
+// into the AGPRs, one wave per SIMD)
+#define ANISO_NEAR_HM(G)                                                                                          \
+    if (win)                                                                                                      \
+        k_near_hm<kMaxRhs, G, 2, 2, false, true><<<blocks_for((int64_t)nl * G, 256), 256, 0, s>>>(                \
+            nl, leafInfo, nearPtsPtr, nearPts, nearKOff, E, pxT, pyT, sigDiag, harm_arg<true>(hw, win), fT, operm, \
+            obase, ldo, flags, scale, out);                                                                       \
+    else                                                                                                          \
+        ANISO_HM_DISPATCH_K(K, (k_near_hm<KK, G, 4, 2><<<blocks_for((int64_t)nl * G, 256), 256, 0, s>>>(           \
+                                   nl, leafInfo, nearPtsPtr, nearPts, nearKOff, E, pxT, pyT, sigDiag,              \
+                                   harm_arg<false>(hw, nullptr), fT, operm, obase, ldo, flags, scale, out)))
     if (in && in->colDst) throw std::invalid_argument("symmetric near storage needs the staged near field");
     if (in && in->grpList) throw std::invalid_argument("a near-field group subset needs the staged near field");
     if (maxLeaf <= 16) {

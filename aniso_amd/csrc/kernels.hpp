@@ -50,6 +50,13 @@ struct HarmWeights {
     double om[kMaxRhs];
 };
 
+// One pass of a block operator of more than kMaxRhs blocks: the
+// harmonic kernels' offset form takes input blocks b0 .. b0 + 7 to output blocks
+// i0 .. i0 + 7 (hw / dw / om hold the pass's 8 weights); multiples of kMaxRhs.
+struct HarmWindow {
+    int i0, b0;
+};
+
 enum StageMask : int {
     kStageFar = 1,      // M2L + L2L + L2P (both kernels)
     kStageNear = 2,     // U/W near field (both kernels)
@@ -190,7 +197,8 @@ void launch_corr(int K, int d, int64_t b, int64_t e, const int* perm, const int*
 // harmonic block apply (harmonic.hip): all modes from the mode-shared E caches
 void launch_m2l_hm(int K, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk, const double* E,
                    const double* ncx, const double* ncy, const double* nrx, const double* nry, const Params* P,
-                   const HarmWeights& hw, const double* mult, double* local, hipStream_t s);
+                   const HarmWeights& hw, const double* mult, double* local, hipStream_t s,
+                   const HarmWindow* win = nullptr);  // win: the offset form (K = 8)
 // the clustered M2L's arguments (harmonic.hip k_m2l_hc, k_top_m2l_hc)
 struct HcArgs {
     const int* clPtr;
@@ -370,7 +378,11 @@ bool launch_near_hm(int K, int nl, int maxLeaf, const int4* leafInfo, const int6
                     const double* sigDiag, const HarmWeights& hw, const double* fT, const int* operm, int64_t obase,
                     int64_t ldo, int flags, double scale, double* out, const uint16_t* nearLoc, const int64_t* nsPtr,
                     const int* nsPts, int nsMax, const NearCorr* corr, int wpe, hipStream_t s,
-                    const NearHsArgs* in = nullptr);  // in->xin: the staged kernel's charges from the input
+                    const NearHsArgs* in = nullptr,  // in->xin: the staged kernel's charges from the input
+                    const HarmWindow* win = nullptr);  // win: the offset form (K = 8, directed storage)
+// out[i] = a[i] (add == 0) or out[i] += a[i], rows i < nrhs of n entries: the sum over a block operator's passes
+void launch_add_rows(int64_t n, int nrhs, const double* a, int64_t lda, double* out, int64_t ldo, int add,
+                     hipStream_t s);
 void launch_sub_slice(int64_t n, int nrhs, const double* x, int64_t ldx, const double* a, int64_t lda, double* y,
                       int64_t ldy, hipStream_t s);
 

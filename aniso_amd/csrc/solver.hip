@@ -598,6 +598,7 @@ void Operator::arnoldiSolution(int64_t n, int m, int used, const double* V, int6
 // hist gets the relative residual estimate after every step.
 int Operator::blockSolveDev(const double* rhs, double* x, int restart, double tol, int maxit, double* hist,
                             int maxhist, double* relresOut, hipStream_t s) {
+    checkBlockLimit(false);
     if (plan.nranks != 1) throw std::logic_error("block solve on a sharded handle");
     if (!coeffSet) throw std::runtime_error("block solve before setCoeff");
     for (int m = 0; m < kernelSize; ++m)
@@ -908,6 +909,7 @@ int Operator::solve16Mixed(const double* B, int64_t ldb, double* X, int64_t ldx,
 // the same on host pointers (the MEX shim's 'solve' op): one staging copy each way
 int Operator::blockSolveHost(const double* rhs, double* x, int restart, double tol, int maxit, double* hist,
                              int maxhist, double* relres) {
+    checkBlockLimit(false);
     ensureDevice();
     const size_t bytes = (size_t)ks * geo.N * sizeof(double);
     DevBuf db, dx;

@@ -102,6 +102,18 @@ int aniso_top_trace(aniso_handle h, int64_t *rec, int64_t cap, int64_t *n);
 /* device line integrals tau(a,b) of the current sigma_t for n segments
  * seg[4i..4i+3] = (x0, y0, x1, y1) (KernelFactory.cpp:67-166); host pointers */
 int aniso_line_integrals(aniso_handle h, const double *seg, int n, double *out);
+/* ---- the block operator beyond 8 blocks ---- */
+/* the pass decomposition of a block operator of ks blocks: nchunks x nchunks passes
+ * over chunks of `chunk` blocks (ks <= 8: chunk = ks, nchunks = 1; else chunk = 8,
+ * nchunks = ceil(ks / 8), the last chunk zero-padded).  Host only, no device. */
+int aniso_block_pass_plan(int ks, int *chunk, int *nchunks);
+/* one pass: the contribution of input chunk J of x to output chunk I, which = 0
+ * (forward) or 1 (mforward).  x: the full ks x N input (row stride ldx), out: chunk x N
+ * (row stride ldo), both in original order, device pointers.  The sum over J of the
+ * passes (I, J) is rows chunk I .. of aniso_block_op_dev.  Unsharded handles only
+ * (ANISO_ERR_INVALID otherwise). */
+int aniso_block_pass_dev(aniso_handle h, int which, int I, int J, const double *x, int64_t ldx, double *out,
+                         int64_t ldo, void *stream);
 
 #ifdef __cplusplus
 }
