@@ -70,6 +70,8 @@ def lib():
             "aniso_get_weights": [P, dp],
             "aniso_set_coeff": [P, dp, dp],
             "aniso_cache": [P, I],
+            "aniso_cache_block": [P],
+            "aniso_cache_bytes": [P, lp],
             "aniso_mapping": [P, dp, I, dp],
             "aniso_mapping_dev": [P, P, I, P, P],
             "aniso_mapping_batched": [P, dp, I, I, dp],
@@ -283,6 +285,21 @@ class Aniso:
     def cache(self, id_):
         """Aniso.m:26-28."""
         _check(lib().aniso_cache(self.address, int(id_)))
+
+    def cache_block(self):
+        """Every mode 0 .. 2ks-2 made ready for the block operator (block_op*, apply_block,
+        block_solve*) on the mode-shared caches, without per-mode operator caches: a lean
+        handle.  aniso.m's `for i = 0:(2N-2) cache(i)` in one call.  mapping / mapping_dev
+        still work for every mode; what streams a mode's own operators raises code 3
+        until cache(id) builds them."""
+        _check(lib().aniso_cache_block(self.address))
+
+    def cache_bytes(self):
+        """(per_mode, shared): device bytes of the per-mode Km2l + Knear operator caches
+        over all modes, and of the mode-shared caches."""
+        b = (ctypes.c_int64 * 2)()
+        _check(lib().aniso_cache_bytes(self.address, b))
+        return int(b[0]), int(b[1])
 
     def mapping(self, charge, id_):
         """Aniso.m:30-32: returns K_id * charge (N,)."""

@@ -149,7 +149,7 @@ void Operator::setShard(int rank, int nranks) {
     for (auto& m : modes) {
         m.Knear.alloc(0);
         m.Km2l.alloc(0);
-        m.ready = false;
+        m.tables = m.resident = false;
     }
     f32Ready = false;
     mrhsPlanReady = false;
@@ -442,7 +442,7 @@ void Operator::setCoeff(const double* ss, const double* st) {
     std::vector<double> sT(geo.N);
     for (int64_t k = 0; k < geo.N; ++k) sT[k] = sigma_s[tree.perm[k]];
     up(dSigmaT, sT);
-    for (auto& m : modes) m.ready = false;
+    for (auto& m : modes) m.tables = m.resident = false;
     attReady = false;
     f32Ready = false;  // config 5's fp32 caches are rounded from the mode-0 operators of sigma_t
     m64.clear();       // ... and the fp64 16-RHS caches are the modes' operators
@@ -481,7 +481,55 @@ void Operator::cache(int id) {
     HIP_CHECK(hipStreamSynchronize(own));  // folded tables may still be read by queued work
     corrTabs.clear();
     HIP_CHECK(hipStreamSynchronize(own));
-    mc.ready = true;
+    mc.tables = mc.resident = true;
+}
+
+// cacheBlock: every mode made usable by the block operator on the mode-shared caches
+// (DESIGN.md §3.9.2): those caches once, and per mode the host-built correction tables
+// only -- no Km2l / Knear.  The operator buffers of modes that are not resident (left
+// by an earlier setCoeff) are freed, so afterwards a mode holds operators only if
+// cache(id) built them since the last setCoeff.
+void Operator::cacheBlock() {
+    if (ks < 2) throw std::invalid_argument("aniso_cache_block: a handle of one block (ks = 1) has no block operator on the mode-shared caches; use aniso_cache(id)");
+    if (plan.nearSymmetric)
+        throw std::invalid_argument("aniso_cache_block: symmetric near storage (ANISO_NEAR_SYMMETRIC=1) runs the block operator on the per-mode operators; use aniso_cache(id)");
+    if (!useAtt)
+        throw std::invalid_argument("aniso_cache_block: the mode-shared caches are off (ANISO_HARMONIC=0), the block operator streams the per-mode operators; use aniso_cache(id)");
+    if (!coeffSet) throw std::runtime_error("aniso_cache_block called before setCoeff");
+    ensureDevice();
+    if (!attReady) buildAttCache();
+    // queued work (on the caller's streams too) may still read the stale operators or
+    // the folded tables
+    HIP_CHECK(hipDeviceSynchronize());
+    for (int id = 0; id < kernelSize; ++id) {
+        ModeCache& mc = modes[id];
+        if (!mc.resident) {
+            mc.Knear.alloc(0);
+            mc.Km2l.alloc(0);
+        }
+        if (mc.tables) continue;
+        CorrTables ct;
+        ct.build(geo, id);
+        up(mc.C, ct.C);
+        up(mc.mu, ct.mu);
+        mc.hostC = ct.C;
+        mc.hostMu = ct.mu;
+    }
+    corrTabs.clear();
+    for (auto& mc : modes) mc.tables = true;
+}
+
+void Operator::cacheBytes(int64_t bytes[2]) const {
+    bytes[0] = 0;
+    for (const auto& mc : modes) bytes[0] += (int64_t)(mc.Km2l.bytes + mc.Knear.bytes);
+    bytes[1] = (int64_t)(dAttM2L.bytes + dAttNear.bytes + dSigDiag.bytes);
+}
+
+void Operator::needResident(int id, const char* what) const {
+    if (id < 0 || id >= kernelSize || !modes[id].tables || modes[id].resident) return;
+    throw std::logic_error(std::string(what) + " needs the operators of kernel id " + std::to_string(id) +
+                           " resident: aniso_cache_block builds none, call aniso_cache(" + std::to_string(id) +
+                           ") before it");
 }
 
 // The mode-shared caches: E = e^-tau for every directed M2L pair
@@ -586,7 +634,7 @@ bool Operator::harmonicWeights(int K, int nterm, const int* ids, const double* m
 
 void Operator::mappingHost(const double* charge, int id, double* out) {
     if (id < 0 || id >= kernelSize) throw std::out_of_range("kernel id out of range");
-    if (!modes[id].ready) throw std::runtime_error("mapping on kernel id " + std::to_string(id) + " before cache(" + std::to_string(id) + ")");
+    if (!modes[id].tables) throw std::runtime_error("mapping on kernel id " + std::to_string(id) + " before cache(" + std::to_string(id) + ")");
     ensureDevice();
     HIP_CHECK(hipMemcpyAsync(dCharge.p, charge, geo.N * sizeof(double), hipMemcpyHostToDevice, own));
     if (plan.nranks > 1) HIP_CHECK(hipMemsetAsync(dOut.p, 0, dOut.bytes, own));
@@ -604,10 +652,11 @@ void Operator::mappingHost(const double* charge, int id, double* out) {
 // when that copy fits in the free HBM, else the 8-column batches run.
 void Operator::mappingBatchedHost(const double* Q, int k, int id, double* Out) {
     if (k == 0) return;
+    needResident(id, "aniso_mapping_batched");
     ensureDevice();
     const int64_t N = geo.N;
     bool mfma = k > 8 && plan.nranks == 1;
-    if (mfma && !m64.count(id) && id >= 0 && id < kernelSize && modes[id].ready) {
+    if (mfma && !m64.count(id) && id >= 0 && id < kernelSize && modes[id].resident) {
         // the plan first (mrhs64Bytes builds and uploads it), then the free HBM it leaves
         const size_t need = mrhs64Bytes() + (size_t)64 * N * sizeof(double);  // + the four 16-column staging buffers
         size_t freeB = 0, totalB = 0;
@@ -616,7 +665,7 @@ void Operator::mappingBatchedHost(const double* Q, int k, int id, double* Out) {
     }
     if (mfma) {
         if (id < 0 || id >= kernelSize) throw std::out_of_range("kernel id out of range");
-        if (!modes[id].ready)
+        if (!modes[id].resident)
             throw std::runtime_error("mapping on kernel id " + std::to_string(id) + " before cache(" + std::to_string(id) + ")");
         DevBuf dq, dout, x16, y16;
         dq.alloc((size_t)16 * N * sizeof(double));
@@ -659,13 +708,62 @@ void Operator::mappingBatchedHost(const double* Q, int k, int id, double* Out) {
 // mapping (AnisoWrapper.cpp:92-136) on device pointers, enqueued on stream s.
 // Only owned targets of `out` are written when the operator is sharded.
 void Operator::mappingDev(const double* charge, int id, double* out, hipStream_t s, int mask) {
+    if (id >= 0 && id < kernelSize && modes[id].tables && !modes[id].resident) {
+        leanMapping(charge, id, out, s, mask);
+        return;
+    }
     apply(charge, false, nullptr, id, out, false, s, mask);
+}
+
+// mapping(id) of a mode made ready by cacheBlock only: served from
+// the mode-shared caches as one pass of the offset form (§3.9.1).  The charge is row 0
+// of a zero-padded 8-row input with the harmonic weights hw = [1, 0, ..., 0], the
+// window is i0 = 8 (id / 8), b0 = 0, and om masks every output row but id - i0:
+//     out = (E / r) T_id(c) charge
+// over the M2L and the near field, with mode id's correction stencils and, for id = 0,
+// the sigma_t diagonal (dw).  The launches are the pass's; the stage mask is not
+// supported on this route.
+void Operator::leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask) {
+    constexpr int K = kMaxRhs;
+    if (mask != kStageAll)
+        throw std::logic_error("mapping stages on kernel id " + std::to_string(id) +
+                               ": its operators are not resident (aniso_cache_block builds none); call aniso_cache(" +
+                               std::to_string(id) + ") before a per-stage apply");
+    if (!(useAtt && attReady && plan.nearPartTotal == 0)) needResident(id, "aniso_mapping");
+    ensureDevice();
+    const int64_t N = geo.N;
+    const int i0 = K * (id / K), row = id - i0;
+    dPassIn.alloc((size_t)K * N * sizeof(double));
+    dPassOut.alloc((size_t)K * N * sizeof(double));
+    HIP_CHECK(hipMemsetAsync(dPassIn.p, 0, dPassIn.bytes, s));
+    HIP_CHECK(hipMemcpyAsync(dPassIn.p, charge, N * sizeof(double), hipMemcpyDeviceToDevice, s));
+    double* const orow = dPassOut.as<double>() + (size_t)row * N;
+    // a shard writes its owned targets only: the others keep the caller's values
+    if (plan.nranks > 1) HIP_CHECK(hipMemcpyAsync(orow, out, N * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HarmWeights hw;
+    std::memset(&hw, 0, sizeof(hw));
+    hw.hw[0] = 1.0;
+    hw.om[row] = 1.0;
+    hw.dw[row] = id == 0 ? 1.0 : 0.0;
+    std::vector<double> sub((size_t)K * K, 0.0);  // the correction fold: mode id, input row 0 to output row `row`
+    sub[(size_t)row * K] = 1.0;
+    const HarmWindow win{i0, 0};
+    struct Restore {
+        const HarmWindow*& w;
+        ~Restore() { w = nullptr; }
+    } restore{passWin};
+    passWin = &win;
+    passHw = hw;
+    applyBlock(K, dPassIn.as<double>(), N, false, nullptr, 1, &id, sub.data(), dPassOut.as<double>(), N, false, s,
+               kStageAll);
+    HIP_CHECK(hipMemcpyAsync(out, orow, N * sizeof(double), hipMemcpyDeviceToDevice, s));
 }
 
 // mapping on a tree-order input (all N) into the owned tree-order slice
 // out[k - ownBegin], k in [ownBegin, ownEnd): no permutation gathers, and the
 // slices of the shards concatenate to the tree-order output.
 void Operator::mappingTreeDev(const double* qTree, int id, double* outSlice, hipStream_t s) {
+    needResident(id, "aniso_mapping_tree_dev");
     apply(qTree, true, nullptr, id, outSlice, true, s, kStageAll);
 }
 
@@ -677,6 +775,7 @@ void Operator::forwardTreeDev(const double* xTree, double* ySlice, hipStream_t s
 
 void Operator::forwardTreePhase(int phase, const double* xTree, double* ySlice, double* rootsSend,
                                 const double* rootsRecv, hipStream_t s) {
+    needResident(0, "the forward operator");
     if (!modeCached(0)) throw std::runtime_error("forward operator before cache(0)");
     ensureDevice();
     pendingCall(phase, PendingCall{0, 0, xTree, ySlice, dSigmaT.p, geo.N, 0, 0.0});
@@ -796,11 +895,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     if (K < 1 || K > 8) throw std::invalid_argument("block apply supports 1..8 right-hand sides, got " + std::to_string(K));
     checkDeviceErrors();
     if (nterm < 1) throw std::invalid_argument("block apply needs at least one mode term");
-    for (int t = 0; t < nterm; ++t) {
-        if (ids[t] < 0 || ids[t] >= kernelSize) throw std::out_of_range("kernel id out of range");
-        if (!modes[ids[t]].ready)
-            throw std::runtime_error("mapping on kernel id " + std::to_string(ids[t]) + " before cache(" + std::to_string(ids[t]) + ")");
-    }
+    checkModes(K, nterm, ids, mixes);
     if (phase != 0 && !treeIn) throw std::invalid_argument("a sharded (two-phase) apply takes tree-order input");
     if (phase == 1 && plan.xRootChunk > 0 && !rootsSend) throw std::invalid_argument("sharded apply: null roots_send");
     if (phase == 2 && plan.xRootChunk > 0 && !rootsRecv) throw std::invalid_argument("sharded apply: null roots_recv");
@@ -1215,6 +1310,35 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     }
 }
 
+// The modes of a batched apply: every one needs its correction tables; the per-mode
+// stream (any apply that is not the harmonic one or a pass) needs their operators too.
+// Raised before anything is staged or launched.
+void Operator::checkModes(int K, int nterm, const int* ids, const double* mixes) const {
+    bool lean = false;
+    for (int t = 0; t < nterm; ++t) {
+        if (ids[t] < 0 || ids[t] >= kernelSize) throw std::out_of_range("kernel id out of range");
+        if (!modes[ids[t]].tables)
+            throw std::runtime_error("mapping on kernel id " + std::to_string(ids[t]) + " before cache(" + std::to_string(ids[t]) + ")");
+        lean = lean || !modes[ids[t]].resident;
+    }
+    if (!lean) return;
+    if (passWin && useAtt && attReady && plan.nearPartTotal == 0) return;  // a pass: the mode-shared caches
+    HarmWeights hw;
+    bool harmonic = false;
+    if (rhs_supported(K)) {
+        harmonic = harmonicWeights(K, nterm, ids, mixes, hw);
+    } else if (K >= 1 && K <= kMaxRhs) {  // as applyBlock pads it
+        const int Kp = rhs_padded(K);
+        std::vector<double> mp((size_t)nterm * Kp * Kp, 0.0);
+        for (int t = 0; t < nterm; ++t)
+            for (int i = 0; i < K; ++i)
+                for (int b = 0; b < K; ++b) mp[((size_t)t * Kp + i) * Kp + b] = mixes[((size_t)t * K + i) * K + b];
+        harmonic = harmonicWeights(Kp, nterm, ids, mp.data(), hw);
+    }
+    if (harmonic) return;
+    for (int t = 0; t < nterm; ++t) needResident(ids[t], "a block apply down the per-mode operator stream");
+}
+
 int Operator::rootRhs(int nrhs) { return rhs_supported(nrhs) ? nrhs : rhs_padded(nrhs); }
 
 // aniso.m forward / mforward mixes (aniso.m:121-157).  Output block iid takes,
@@ -1612,6 +1736,7 @@ void Operator::buildMrhsPlan() {
 
 // config 5's fp32 caches: the fp64 mode-0 blocks on the directed lists, rounded
 void Operator::buildF32() {
+    needResident(0, "the fp32 operator");
     if (!modeCached(0)) throw std::runtime_error("fp32 operator before cache(0)");
     buildMrhsPlan();
     const F32Plan& f = f32;
@@ -1695,7 +1820,8 @@ void Operator::mrhs64Dev(int id, bool forward, const double* X, double* Y, hipSt
     if (plan.nranks != 1) throw std::logic_error("16-right-hand-side operator on a sharded handle");
     if (id < 0 || id >= kernelSize) throw std::out_of_range("kernel id out of range");
     if (forward && id != 0) throw std::invalid_argument("the forward operator is mode 0's (main.cpp:125-136)");
-    if (!modes[id].ready)
+    needResident(id, "the 16-RHS fp64 operator");
+    if (!modes[id].resident)
         throw std::runtime_error("16-RHS fp64 operator on kernel id " + std::to_string(id) + " before cache(" +
                                  std::to_string(id) + ")");
     ensureDevice();
@@ -2097,8 +2223,9 @@ bool Operator::oneExchangeLocal() const {
 // every mode cached (and the mode-shared caches built, where the handle uses them):
 // what a sharded block matvec needs on every rank
 bool Operator::cachesReady() const {
+    const bool shared = useAtt && attReady;  // a lean handle (cacheBlock) is ready: the block operator reads these
     for (int m = 0; m < kernelSize; ++m)
-        if (!modes[m].ready) return false;
+        if (!modes[m].tables || !(shared || modes[m].resident)) return false;
     return !useAtt || attReady;
 }
 

@@ -40,7 +40,11 @@ struct DevBuf {
 struct ModeCache {
     DevBuf Knear, Km2l, C, mu;
     std::vector<double> hostC, hostMu;  // the correction tables (folded per batched apply)
-    bool ready = false;
+    // two readiness notions: the correction tables C / mu are built
+    // (enough for the harmonic block apply and its passes, which read the mode-shared
+    // caches), and the mode's own operators Km2l / Knear are built (everything that
+    // streams them).  resident implies tables; setCoeff clears both.
+    bool tables = false, resident = false;
 };
 
 // Correction tables of one batched apply: every term's stencil / singular table
@@ -63,6 +67,12 @@ public:
     void getNodes(double* xy) const;
     void setCoeff(const double* sigma_s, const double* sigma_t);
     void cache(int id);
+    // every mode made ready for the block operator on the mode-shared caches, without
+    // per-mode operators (a lean handle)
+    void cacheBlock();
+    // device bytes of the operator caches: per-mode Km2l + Knear over all modes, the
+    // mode-shared caches
+    void cacheBytes(int64_t bytes[2]) const;
     void mappingHost(const double* charge, int id, double* out);
     void mappingBatchedHost(const double* Q, int k, int id, double* Out);  // N x k column-major
     void mappingDev(const double* charge, int id, double* out, hipStream_t s, int stageMask = 0x3f);
@@ -215,7 +225,11 @@ public:
         useClusters = !(on && detPerTarget);
     }
     bool deterministicOn() const { return detSums || !useClusters; }
-    bool modeCached(int id) const { return id >= 0 && id < kernelSize && modes[id].ready; }
+    // the mode's own operators are resident (cache(id) since the last setCoeff)
+    bool modeCached(int id) const { return id >= 0 && id < kernelSize && modes[id].resident; }
+    // raise (ANISO_ERR_STATE) if the mode was made ready by cacheBlock only: `what`
+    // streams its operators.  A mode with no tables either is left to the caller's check.
+    void needResident(int id, const char* what) const;
     int kernelSize = 0;
     // stage timing with HIP events recorded in-stream (no host sync per apply);
     // stageTimes() averages every apply recorded since setTiming(level > 0).
@@ -269,6 +283,11 @@ private:
     void blockPass(int I, int J, const std::vector<double>& mix, const double* x, int64_t ldx, bool tree,
                    const double* sig, double* out8, int64_t ldo, hipStream_t s);
     void checkBlockLimit(bool shardedCall) const;
+    // mapping of a mode whose operators are not resident: one pass of the offset form
+    void leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask);
+    // the modes of a batched apply are usable by it: tables for the harmonic launches,
+    // resident operators for the per-mode stream (checked before anything is launched)
+    void checkModes(int K, int nterm, const int* ids, const double* mixes) const;
     const HarmWindow* passWin = nullptr;  // set by blockPass for its applyBlock
     HarmWeights passHw{};
     DevBuf dPassIn, dPassOut;  // a pass's zero-padded input chunk, its 8 output rows

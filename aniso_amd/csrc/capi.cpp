@@ -162,6 +162,19 @@ int aniso_cache(aniso_handle h, int id) {
     return guarded([&] { get(h).cache(id); });
 }
 
+int aniso_cache_block(aniso_handle h) {
+    ENTER(h);
+    return guarded([&] { get(h).cacheBlock(); });
+}
+
+int aniso_cache_bytes(aniso_handle h, int64_t bytes[2]) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(bytes);
+        get(h).cacheBytes(bytes);
+    });
+}
+
 int aniso_mapping(aniso_handle h, const double* charge, int id, double* out) {
     ENTER(h);
     return guarded([&] {
@@ -207,6 +220,7 @@ int aniso_forward_dev(aniso_handle h, const double* u, double* out, void* stream
         CHECK_PTR(u);
         CHECK_PTR(out);
         auto& op = get(h);
+        op.needResident(0, "aniso_forward_dev");
         if (!op.modeCached(0)) throw std::runtime_error("forward operator before cache(0)");
         op.forwardDev(u, out, (hipStream_t)stream);
     });
@@ -227,6 +241,7 @@ int aniso_forward_tree_dev(aniso_handle h, const double* x_tree, double* y_slice
         CHECK_PTR(x_tree);
         CHECK_PTR(y_slice);
         auto& op = get(h);
+        op.needResident(0, "aniso_forward_tree_dev");
         if (!op.modeCached(0)) throw std::runtime_error("forward operator before cache(0)");
         op.forwardTreeDev(x_tree, y_slice, (hipStream_t)stream);
     });

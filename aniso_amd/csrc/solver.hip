@@ -339,6 +339,7 @@ void Operator::forwardDev(const double* u, double* out, hipStream_t s) {
 int Operator::gmresHost(const double* q, double* xh, int m, int maxit, double tol, double* hist, int maxhist,
                         double* finalResid) {
     if (m < 1 || maxit < 0) throw std::invalid_argument("GMRES needs m >= 1 and maxit >= 0");
+    needResident(0, "aniso_gmres");
     if (!modeCached(0)) throw std::runtime_error("GMRES before cache(0)");
     ensureDevice();
     const int64_t N = geo.N;
@@ -602,7 +603,9 @@ int Operator::blockSolveDev(const double* rhs, double* x, int restart, double to
     if (plan.nranks != 1) throw std::logic_error("block solve on a sharded handle");
     if (!coeffSet) throw std::runtime_error("block solve before setCoeff");
     for (int m = 0; m < kernelSize; ++m)
-        if (!modes[m].ready) throw std::runtime_error("block solve before cache(" + std::to_string(m) + ")");
+        if (!modes[m].tables) throw std::runtime_error("block solve before cache(" + std::to_string(m) + ")");
+    if (!harmonicReady())  // the matvec streams the per-mode operators
+        for (int m = 0; m < kernelSize; ++m) needResident(m, "the block solve without the mode-shared caches");
     if (restart < 1 || maxit < 1 || !(tol > 0.0)) throw std::invalid_argument("block solve needs restart >= 1, maxit >= 1, tol > 0");
     ensureDevice();
     checkDeviceErrors();
@@ -754,7 +757,8 @@ int Operator::solve16Mixed(const double* B, int64_t ldb, double* X, int64_t ldx,
     using namespace arn16;
     if (plan.nranks != 1) throw std::logic_error("16-RHS solve on a sharded handle");
     if (!coeffSet) throw std::runtime_error("16-RHS solve before setCoeff");
-    if (!modes[0].ready) throw std::runtime_error("16-RHS solve before cache(0)");
+    needResident(0, "aniso_solve16_mixed_dev");
+    if (!modes[0].resident) throw std::runtime_error("16-RHS solve before cache(0)");
     if (m < 1 || m >= kMaxRows) throw std::invalid_argument("16-RHS solve: restart must be in [1, 47]");
     if (!(tol > 0.0) || !(innerTol > 0.0) || maxOuter < 0 || maxCycles < 1)
         throw std::invalid_argument("16-RHS solve needs tol, inner_tol > 0, max_outer >= 0, max_cycles >= 1");

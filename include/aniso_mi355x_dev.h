@@ -17,7 +17,9 @@ extern "C" {
 #endif
 
 /* apply restricted to the stages in `mask` (ANISO_STAGE_*), unscaled stages are
- * still multiplied by 1/(2 pi) like the full output; device pointers */
+ * still multiplied by 1/(2 pi) like the full output; device pointers.  The stages are
+ * those of the mode's own operators: on a lean mode (aniso_cache_block without
+ * aniso_cache(h, id)) any mask but ANISO_STAGE_ALL is ANISO_ERR_STATE */
 int aniso_mapping_stages_dev(aniso_handle h, const double *charge, int id, int mask, double *out, void *stream);
 /* introspection of the exchange plan (each pointer may be NULL): the roots this rank
  * sends (info[6] node ids, send order), the all-gather slot -> node map (info[8] x

@@ -11,6 +11,9 @@
  *   h = AnisoWrapperMI355X('new', sz, d, ks, g, ns, np, maxLevel);
  *   AnisoWrapperMI355X('setCoeff', h, sigma_s, sigma_t);  AnisoWrapperMI355X('cache', h, id);
  *   theta = AnisoWrapperMI355X('mapping', h, charge, id);
+ * aniso.m's cache loop over every mode (for i = 0:(2N-2) cache(i)) becomes one call that
+ * builds no per-mode operator cache:
+ *   AnisoWrapperMI355X('cacheBlock', h);
  * and aniso.m's GMRES operator (aniso.m:155) becomes one call per matvec:
  *   A = @(x) AnisoWrapperMI355X('blockMatvec', h, x);   % x - mforward(x), x = [u_0; ...; u_{ks-1}]
  * and aniso.m:159-173's solve, gmres(A, rhs, 400, 1e-11, 400), as one call with the
@@ -104,6 +107,12 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(op, "cache")) { /* :72-90 */
         need(nrhs, 3, op);
         CALL(aniso_cache(handle_of(prhs[1]), (int)mxGetScalar(prhs[2])));
+    } else if (!strcmp(op, "cacheBlock")) {
+        /* aniso.m's setCoeff loop `for i = 0:(2N-2) cache(i)` in one call: every mode
+         * ready for forward / mforward / blockMatvec / solve on the mode-shared caches,
+         * no per-mode operator cache built (aniso_cache_block) */
+        need(nrhs, 2, op);
+        CALL(aniso_cache_block(handle_of(prhs[1])));
     } else if (!strcmp(op, "mapping")) { /* :92-136 */
         aniso_handle h;
         int64_t n;
