@@ -467,10 +467,11 @@ class Aniso:
 
     def block_op_begin_dev(self, which, x, out, roots_send, stream=None):
         """Phase 1 of the sharded x - mforward(x) etc.: x (ks, N) tree order, valid at
-        the own range and the halo; out (ks, >= n_owned); roots_send >= C x R doubles."""
+        the own range and the halo; out (ks, >= n_owned); roots_send >= C x R doubles.
+        Up to 8 blocks: more raise code 1 from the library (block_op_sharded_dev runs them)."""
         import torch
 
-        ex = self.shard_exchange(self.ks)
+        ex = self.shard_exchange(min(self.ks, 8))
         _dev_rows(x, self.ks, self.N, "x")
         _dev_rows(out, self.ks, self.n_owned(), "out")
         rs = self._roots_buf(roots_send, ex["root_chunk"] * ex["root_record"], "roots_send")
@@ -483,7 +484,7 @@ class Aniso:
         """Phase 2: roots_recv = the all-gather of every rank's roots_send (nranks x C x R)."""
         import torch
 
-        ex = self.shard_exchange(self.ks)
+        ex = self.shard_exchange(min(self.ks, 8))  # (more than 8 blocks: the library raises code 1)
         _dev_rows(x, self.ks, self.N, "x")
         _dev_rows(out, self.ks, self.n_owned(), "out")
         rr = self._roots_buf(roots_recv, nranks * ex["root_chunk"] * ex["root_record"], "roots_recv")
@@ -709,7 +710,8 @@ class Aniso:
 
     def block_op_sharded_dev(self, which, x, y, stream=None):
         """One call of the sharded aniso.m operator: x (ks, N) tree order holds this
-        rank's own range (its halo is filled here), y's owned slice receives the result."""
+        rank's own range (its halo is filled here), y's owned slice receives the result.
+        Any ks: more than 8 blocks run as passes with ceil(ks / 8) exchanges per call."""
         import torch
 
         _dev_rows(x, self.ks, self.N, "x")

@@ -899,8 +899,9 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     if (phase != 0 && !treeIn) throw std::invalid_argument("a sharded (two-phase) apply takes tree-order input");
     if (phase == 1 && plan.xRootChunk > 0 && !rootsSend) throw std::invalid_argument("sharded apply: null roots_send");
     if (phase == 2 && plan.xRootChunk > 0 && !rootsRecv) throw std::invalid_argument("sharded apply: null roots_recv");
-    if (phase == 2 && !(pend.active && pend.K == rootRhs(K)))
+    if (phase >= 2 && !(pend.active && pend.K == rootRhs(K)))
         throw std::logic_error("sharded apply: end without a matching begin");
+    if (phase == 3 && !(shardPass && passWin)) throw std::logic_error("sharded apply: a repeated phase 2 outside a pass");
     ensureDevice();
     const int64_t nOut = treeOut ? plan.ownEnd - plan.ownBegin : geo.N;
     if (ldx < geo.N || ldo < nOut) throw std::invalid_argument("block apply: leading dimension too small");
@@ -943,6 +944,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     // the mode-shared caches the pass's sub-mixes take the per-mode stream like any mix
     const HarmWindow* const win = passWin && useAtt && attReady && plan.nearPartTotal == 0 ? passWin : nullptr;
     if (win) hw = passHw;
+    if (shardPass && !(win && phase != 0)) throw std::logic_error("sharded pass: not the offset harmonic form");
     const bool harmonic = win ? true : harmonicWeights(K, nterm, ids, mixes, hw);
     // the harmonic block apply runs its near field + corrections (they write `out`)
     // on a side stream beside the M2L (it writes the locals), forked as soon as the
@@ -1129,12 +1131,16 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     int e0 = -1;
     int eStart = -1;  // the apply's first event: the total span covers every stage
     bool nearDone = false;
-    if (phase != 2) {
+    // a sharded pass (blockOpShardedPasses): its phase 1 serves every output window of the
+    // input chunk, so nothing that depends on the window -- the near field and the
+    // corrections write `out` -- is issued there; every near group runs in phase 2
+    const bool passShard = win && phase != 0;
+    if (phase < 2) {
         // up pass: tiers bottom-up; its P2M also forms the weighted charges fT (tree
         // order) the near field and the corrections read
         e0 = tm ? mark(s) : -1;
         eStart = e0;
-        const bool nearEarlyGroups = nearIn && oneX && !plan.nearGrpEarly.empty() && shardNearEarly;
+        const bool nearEarlyGroups = nearIn && oneX && !plan.nearGrpEarly.empty() && shardNearEarly && !passShard;
         const bool earlyAfterPack = nearEarlyGroups && phase == 1 && ntier >= 1 && packHook;
         auto nearEarlyStage = [&] {
             // one-collective form: the groups that read only the own range start now,
@@ -1152,7 +1158,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         // workgroup slots first (0.6-1.2 % per block matvec on one GPU, 1.6 % on a rank
         // of 8, r04z; ANISO_NEAR_ORDER=first issues it first)
         const bool nearAfterUp = nearIn && !oneX && fork && nearOrderUp && phase == 0 && ntier >= 1;
-        if (nearIn && !oneX) {  // the near field first: beside the up pass (fork) or before it (serial)
+        if (nearIn && !oneX && !passShard) {  // the near field first: beside the up pass (fork) or before it (serial)
             if (fork) HIP_CHECK(hipEventRecord(evFork, s));
             if (!nearAfterUp) {
                 nearStage();
@@ -1186,7 +1192,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         if (phase == 1) {
             const int ep = tm ? mark(s) : -1;
             span(1, e0, ep);
-            if ((ntier < 1 || forkTier == 0) && !nearFused && !nearDone && !oneX) {
+            if ((ntier < 1 || forkTier == 0) && !nearFused && !nearDone && !oneX && !passShard) {
                 nearStage();
                 nearDone = true;
             }
@@ -1202,20 +1208,23 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         e0 = pend.e0;
         eStart = pend.eStart;
         nearDone = pend.nearDone;
-        pend.active = false;
+        pend.active = shardPass;  // a sharded pass repeats its phase 2 per output window (phase 3)
         const int ex = tm ? mark(s) : -1;
-        span(0, pend.ePack, ex);  // the caller's root exchange
+        if (phase == 2) span(0, pend.ePack, ex);  // the caller's root exchange
+        else eStart = ex;                         // a repeat's total span is its own
         if (oneX && !nearDone) {  // the rest of the near field after the one exchange (it filled the input's halo)
-            // (ANISO_SHARD_NEAR_EARLY=0: every group here, in one launch)
-            nin.grpList = shardNearEarly ? dNearGrpLate.as<int>() : nullptr;
-            nin.ngrp = shardNearEarly ? (int)plan.nearGrpLate.size() : 0;
+            // (ANISO_SHARD_NEAR_EARLY=0, and every pass: every group here, in one launch)
+            const bool late = shardNearEarly && !passShard;
+            nin.grpList = late ? dNearGrpLate.as<int>() : nullptr;
+            nin.ngrp = late ? (int)plan.nearGrpLate.size() : 0;
             if (fork) HIP_CHECK(hipEventRecord(evFork, s));
             nearStage();
             nin.grpList = nullptr;
             nin.ngrp = 0;
             nearDone = true;
         }
-        if (upPartial) {  // the exchange's unpack summed the upper multipoles
+        if (phase == 3) {  // the chunk's multipoles are in dMult since its phase 2
+        } else if (upPartial) {  // the exchange's unpack summed the upper multipoles
         } else if (topFused) {  // the upper tiers run inside the M2L launch below
         } else if (ntier >= 2) {  // the first upper tier reads the gathered roots (and stores them for the M2L)
             upTier(1, nullptr, tierTasks(1), rootsRecv, nullptr);
@@ -1228,8 +1237,11 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     }
     int ep = tr ? mark(s) : -1;
     span(1, e0, ep);
-    if (phase == 2) e0 = pend.e0;
+    if (phase >= 2) e0 = pend.e0;
     if (!nearDone && !nearFused) {
+        // a sharded pass in the two-collective form: the side stream waits here, behind the
+        // previous window's k_add_rows, which reads the rows this near field writes
+        if (passShard && fork) HIP_CHECK(hipEventRecord(evFork, s));
         nearStage();
         if (tr && sn == s) ep = mark(s);  // serial (ANISO_OVERLAP=0): the M2L span starts after the near field
     }
@@ -1424,12 +1436,33 @@ void Operator::blockPassPlan(int ks, int* chunk, int* nchunks) {
     *nchunks = ks <= kMaxRhs ? 1 : (ks + kMaxRhs - 1) / kMaxRhs;
 }
 
-// ks > kMaxRhs runs on one unsharded handle only; raised before anything is launched
-// or any pending-call state is set
+// ks > kMaxRhs runs on an unsharded handle, or on a shard through the library's own
+// exchange (blockOpShardedDev, which does not come here); the phase-0 entry points of
+// a sharded handle and the caller-driven two-phase forms are refused, before anything
+// is launched or any pending-call state is set
 void Operator::checkBlockLimit(bool shardedCall) const {
     if (ks > kMaxRhs && (plan.nranks > 1 || shardedCall))
         throw std::invalid_argument("block operator: ks = " + std::to_string(ks) + " blocks on a sharded handle (more than " +
-                                    std::to_string(kMaxRhs) + " blocks run on unsharded handles only)");
+                                    std::to_string(kMaxRhs) + " blocks run on unsharded handles, and on shards through "
+                                    "aniso_block_op_sharded_dev only)");
+}
+
+void Operator::passMix(int I, int J, const std::vector<double>& mix, std::vector<double>& sub, HarmWeights& hw) const {
+    constexpr int K = kMaxRhs;
+    const int nm = 2 * ks - 1, i0 = I * K, b0 = J * K;
+    auto mx = [&](int m, int i, int b) { return i < ks && b < ks ? mix[((size_t)m * ks + i) * ks + b] : 0.0; };
+    sub.assign((size_t)nm * K * K, 0.0);
+    for (int m = 0; m < nm; ++m)
+        for (int i = 0; i < K; ++i)
+            for (int b = 0; b < K; ++b) sub[((size_t)m * K + i) * K + b] = mx(m, i0 + i, b0 + b);
+    // the pass's harmonic weights straight from the block weights: output row 0 holds
+    // hw_B at mode B (w_0, or 2 w_B: j = B and j = -B), the mode-0 weight of row i is w_i
+    std::memset(&hw, 0, sizeof(hw));
+    for (int b = 0; b < K; ++b) hw.hw[b] = b0 + b < ks ? mx(b0 + b, 0, b0 + b) : 0.0;
+    for (int i = 0; i < K; ++i) {
+        hw.om[i] = i0 + i < ks ? 1.0 : 0.0;
+        hw.dw[i] = I == J ? mx(0, i0 + i, i0 + i) : 0.0;
+    }
 }
 
 // One pass: input chunk J of x (ks rows) to the 8 rows out8 of output chunk I.  sig:
@@ -1440,22 +1473,11 @@ void Operator::blockPass(int I, int J, const std::vector<double>& mix, const dou
     const int nm = 2 * ks - 1, i0 = I * K, b0 = J * K;
     const int64_t N = geo.N;
     if (ldx < N || ldo < N) throw std::invalid_argument("block apply: leading dimension too small");
-    auto mx = [&](int m, int i, int b) { return i < ks && b < ks ? mix[((size_t)m * ks + i) * ks + b] : 0.0; };
-    std::vector<double> sub((size_t)nm * K * K);
-    for (int m = 0; m < nm; ++m)
-        for (int i = 0; i < K; ++i)
-            for (int b = 0; b < K; ++b) sub[((size_t)m * K + i) * K + b] = mx(m, i0 + i, b0 + b);
+    std::vector<double> sub;
+    HarmWeights hw;
+    passMix(I, J, mix, sub, hw);
     std::vector<int> ids(nm);
     for (int m = 0; m < nm; ++m) ids[m] = m;
-    // the pass's harmonic weights straight from the block weights: output row 0 holds
-    // hw_B at mode B (w_0, or 2 w_B: j = B and j = -B), the mode-0 weight of row i is w_i
-    HarmWeights hw;
-    std::memset(&hw, 0, sizeof(hw));
-    for (int b = 0; b < K; ++b) hw.hw[b] = b0 + b < ks ? mx(b0 + b, 0, b0 + b) : 0.0;
-    for (int i = 0; i < K; ++i) {
-        hw.om[i] = i0 + i < ks ? 1.0 : 0.0;
-        hw.dw[i] = I == J ? mx(0, i0 + i, i0 + i) : 0.0;
-    }
     // the chunk's rows of x; the last chunk zero-padded to 8
     const int nin = std::min(K, ks - b0);
     const double* xin = x + (size_t)b0 * ldx;
@@ -1989,7 +2011,9 @@ void Operator::commInit(std::unique_ptr<Collectives> c) {
     gatherList(&PeerLists::halo, std::vector<double>(plan.xHalo.begin(), plan.xHalo.end()), haloAll);
     const auto cuts = shard_cuts(tree, P);
     if (cuts[me] != plan.ownBegin || cuts[me + 1] != plan.ownEnd) throw std::logic_error("shard cuts disagree with the plan");
-    const int nb = ks;
+    // the rows of one exchange: the blocks, or one chunk of a block operator of more than
+    // kMaxRhs blocks (blockOpShardedPasses: every input chunk reuses this layout)
+    const int nb = std::min(ks, kMaxRhs);
     auto ranges = [&](int r) {  // rank r's halo ranges
         std::vector<std::pair<int64_t, int64_t>> v;
         for (size_t i = 0; i + 1 < haloAll[r].size(); i += 2) v.push_back({(int64_t)haloAll[r][i], (int64_t)haloAll[r][i + 1]});
@@ -2212,7 +2236,9 @@ void Operator::commInit(std::unique_ptr<Collectives> c) {
 // into oxReady; what is left here depends only on the problem (ks, g, which) and on
 // the mode caches, which every rank builds alike before a block matvec.
 bool Operator::oneExchangeLocal() const {
-    if (!plan.xOneOk || !oneXOn || !useAtt || !rhs_supported(ks) || !nearEarly || nearInTop || !plan.nearCorrOk ||
+    // (more than kMaxRhs blocks: the exchange carries one chunk of kMaxRhs rows)
+    if (!plan.xOneOk || !oneXOn || !useAtt || !rhs_supported(std::min(ks, kMaxRhs)) || !nearEarly || nearInTop ||
+        !plan.nearCorrOk ||
         plan.nearPartTotal > 0)
         return false;
     const NearCorr probe{dNearCorrRow.as<uint16_t>(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -2242,14 +2268,124 @@ bool Operator::oneExchangeUsable(int which) {
 }
 
 void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s) {
-    checkBlockLimit(true);
     if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
     if (ldx < geo.N || ldy < geo.N) throw std::invalid_argument("sharded block operator: leading dimension below N");
     ensureDevice();
-    const int nb = ks;
+    if (ks > kMaxRhs) {  // P input chunks, each with one exchange and P output windows
+        blockOpShardedPasses(which, x, ldx, y, ldy, s);
+        return;
+    }
     double* yo = y + plan.ownBegin;
+    const bool one = oneExchangeUsable(which);
+    shardedExchange(
+        ks, x, ldx, one, s,
+        [&] { blockOpDev(which, x, ldx, yo, ldy, true, s, NAN, nullptr, 1, dXRootsSend.as<double>(), nullptr); },
+        [&] { blockOpDev(which, x, ldx, yo, ldy, true, s, NAN, nullptr, 2, nullptr, dXRootsRecv.as<double>()); });
+    if (one) {
+        ++oneXApplies;
+        if (oxUp) ++upPartialApplies;
+    }
+}
+
+// More than kMaxRhs blocks on a shard.  The input chunk J is the
+// outer loop: its 8 rows of x (the last chunk zero-padded) take one exchange and one
+// up pass, exactly the sharded apply at K = 8 -- the chunk's multipoles then stand in
+// dMult and its halo in the input.  Under it every output chunk I runs only what
+// depends on the window {8 I, 8 J}: near field + corrections, the per-target M2L and
+// the down pass (phase 2 for I = 0, its repeat -- phase 3 -- after it), into the
+// (8, owned) scratch that k_add_rows sums into the owned slice of rows 8 I ...  A
+// matvec so issues P exchanges, not P^2.  Every rank takes the same route: the form
+// is commInit's all-gathered decision (oxReady), and everything that can fail on one
+// rank alone is checked, and every work buffer sized, before the first collective.
+void Operator::blockOpShardedPasses(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s) {
+    constexpr int K = kMaxRhs;
+    const int P = (ks + K - 1) / K, nm = 2 * ks - 1;
+    const int64_t N = geo.N, own = plan.ownEnd - plan.ownBegin;
+    if (which < 0 || which > 2) throw std::invalid_argument("block operator: which must be 0, 1 or 2");
+    if (!coeffSet) throw std::runtime_error("block operator before setCoeff");
+    if (useAtt && !attReady)
+        throw std::logic_error("sharded block operator before cache(): every rank caches its modes first");
+    if (!useAtt || plan.nearPartTotal != 0)
+        throw std::invalid_argument("sharded block operator: ks = " + std::to_string(ks) + " blocks (more than " +
+                                    std::to_string(kMaxRhs) + ") run as passes over the mode-shared caches with directed "
+                                    "near storage; this handle has " +
+                                    (!useAtt ? "no mode-shared caches (ANISO_HARMONIC=0)" : "symmetric near storage"));
+    if (!cachesReady())  // (a set_coeff since comm_init: the passes would fail in checkModes, between two collectives)
+        throw std::logic_error("sharded block operator before cache(): every rank caches its modes first");
+    if (up_tier_lds(plan.upMaxTask, K) > 160 * 1024 ||
+        down_tier_lds(plan.dnMaxTask, plan.dnMaxLeaves, plan.dnMaxNear, plan.dnMaxChain, K) > 160 * 1024)
+        throw std::logic_error("up/down pass task exceeds one workgroup's LDS at " + std::to_string(K) + " right-hand sides");
+    checkDeviceErrors();
+    const bool one = oxReady;
+    const auto mix = blockMixes(ks, g, which != 0);
+    const double* sig = which != 0 ? dSigmaT.as<double>() : nullptr;
+    std::vector<int> ids(nm);
+    for (int m = 0; m < nm; ++m) ids[m] = m;
+    dPassOut.alloc((size_t)K * N * sizeof(double));
+    if (ks % K) dPassIn.alloc((size_t)K * N * sizeof(double));
+    double* acc = y + plan.ownBegin;
+    int64_t lda = ldy;
+    if (which == 2) {  // x - mforward(x): the passes sum into dBlk
+        dBlk.alloc((size_t)ks * own * sizeof(double));
+        acc = dBlk.as<double>();
+        lda = own;
+    }
+    ensureWork(K);
+    struct Restore {
+        Operator& o;
+        ~Restore() {
+            o.passWin = nullptr;
+            o.shardPass = false;
+            o.pend.active = false;
+        }
+    } restore{*this};
+    shardPass = true;
+    HarmWindow win{0, 0};
+    std::vector<double> sub;
+    for (int J = 0; J < P; ++J) {
+        const int b0 = J * K, nin = std::min(K, ks - b0);
+        double* xin = x + (size_t)b0 * ldx;
+        int64_t ldin = ldx;
+        if (nin < K) {  // the last chunk zero-padded; the exchange fills the copy's halo
+            HIP_CHECK(hipMemsetAsync(dPassIn.p, 0, dPassIn.bytes, s));
+            HIP_CHECK(hipMemcpy2DAsync(dPassIn.p, N * sizeof(double), xin, ldx * sizeof(double), N * sizeof(double), nin,
+                                       hipMemcpyDeviceToDevice, s));
+            xin = dPassIn.as<double>();
+            ldin = N;
+        }
+        auto pass = [&](int I, int phase) {
+            passMix(I, J, mix, sub, passHw);
+            win = HarmWindow{I * K, b0};
+            passWin = &win;
+            applyBlock(K, xin, ldin, true, sig, nm, ids.data(), sub.data(), dPassOut.as<double>(), own, true, s,
+                       kStageAll, phase, phase == 1 ? dXRootsSend.as<double>() : nullptr,
+                       phase == 2 ? dXRootsRecv.as<double>() : nullptr);
+        };
+        shardedExchange(
+            K, xin, ldin, one, s, [&] { pass(0, 1); },
+            [&] {
+                if (nin < K)  // the caller's x has its halo filled for every row
+                    HIP_CHECK(hipMemcpy2DAsync(x + (size_t)b0 * ldx, ldx * sizeof(double), xin, N * sizeof(double),
+                                               N * sizeof(double), nin, hipMemcpyDeviceToDevice, s));
+                for (int I = 0; I < P; ++I) {
+                    pass(I, I == 0 ? 2 : 3);
+                    launch_add_rows(own, std::min(K, ks - I * K), dPassOut.as<double>(), own, acc + (size_t)I * K * lda,
+                                    lda, J > 0 ? 1 : 0, s);
+                }
+            });
+        pend.active = false;
+    }
+    if (which == 2) launch_sub_slice(own, ks, x + plan.ownBegin, ldx, dBlk.as<double>(), own, y + plan.ownBegin, ldy, s);
+    if (one) {
+        ++oneXApplies;
+        if (oxUp) ++upPartialApplies;
+    }
+}
+
+void Operator::shardedExchange(int nb, double* x, int64_t ldx, bool one, hipStream_t s,
+                               const std::function<void()>& phase1, const std::function<void()>& phase2) {
     const int64_t rec = (int64_t)plan.xRootChunk * kRank * rootRhs(nb);
-    if (oneExchangeUsable(which)) {
+    if (one) {
         // phase 1 (own tier-0 subtrees), then ONE grouped exchange: the roots to every
         // rank, and from each owner the input positions and multipoles this rank reads;
         // then phase 2 (near field, upper tiers + M2L, down pass)
@@ -2300,7 +2436,7 @@ void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, i
                 }
             };
             if (nearAfterPack) packHook = pack;
-            blockOpDev(which, x, ldx, yo, ldy, true, s, NAN, nullptr, 1, dXRootsSend.as<double>(), nullptr);
+            phase1();
             packHook = nullptr;
             if (!packIssued) pack(s);
             comm->alltoallv(dOxSendBuf.as<double>(), oxScount.data(), oxSoff.data(), dOxRecvBuf.as<double>(),
@@ -2329,7 +2465,7 @@ void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, i
                 uk.ownRec = dXUpRec.as<double>();
             }
             launch_ox(uk, false, s);
-            blockOpDev(which, x, ldx, yo, ldy, true, s, NAN, nullptr, 2, nullptr, dXRootsRecv.as<double>());
+            phase2();
         } catch (...) {
             oneXActive = false;
             upActive = false;
@@ -2340,8 +2476,6 @@ void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, i
         oneXActive = false;
         upActive = false;
         upTailActive = false;
-        ++oneXApplies;
-        if (oxUp) ++upPartialApplies;
         return;
     }
     // the input's halo from its owners
@@ -2352,9 +2486,9 @@ void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, i
     launch_halo_unpack(hxNrecv, nb, dHxRecvPos.as<int64_t>(), dHxRecvBase.as<int64_t>(), dHxRecvStride.as<int64_t>(),
                        dHxRecvBuf.as<double>(), x, ldx, s);
     // phase 1, the tier-0 root all-gather, phase 2 (the owned slice of y)
-    blockOpDev(which, x, ldx, yo, ldy, true, s, NAN, nullptr, 1, dXRootsSend.as<double>(), nullptr);
+    phase1();
     if (rec > 0) comm->allgather(dXRootsSend.as<double>(), dXRootsRecv.as<double>(), (size_t)rec, s);
-    blockOpDev(which, x, ldx, yo, ldy, true, s, NAN, nullptr, 2, nullptr, dXRootsRecv.as<double>());
+    phase2();
 }
 
 void Operator::checkDeviceErrors() {

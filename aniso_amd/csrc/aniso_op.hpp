@@ -124,6 +124,7 @@ public:
     // the library's own multi-GPU exchange (comm.hpp): attach a
     // communicator of this shard's rank / nranks, then blockOpShardedDev runs the
     // input's halo all-to-all, phase 1, the root all-gather and phase 2 in one call
+    // (any ks: more than kMaxRhs blocks as passes, one exchange per input chunk)
     void commInit(std::unique_ptr<Collectives> c);
     void blockOpShardedDev(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s);
     bool commReady() const { return comm != nullptr; }
@@ -256,7 +257,9 @@ private:
     void apply(const double* charge, bool treeIn, const double* sigT, int id, double* out, bool treeOut, hipStream_t s,
                int mask);
     // phase 0: the whole apply (input valid everywhere, every up task); 1 / 2: the
-    // two halves of a sharded apply (forwardTreeBegin / End)
+    // two halves of a sharded apply (forwardTreeBegin / End); 3: phase 2 again for
+    // another output window of a sharded pass (blockOpShardedPasses), on the
+    // multipoles already in dMult: no unpack, no upper tier
     void applyBlock(int K, const double* x, int64_t ldx, bool treeIn, const double* sigT, int nterm, const int* ids,
                     const double* mixes, double* out, int64_t ldo, bool treeOut, hipStream_t s, int mask,
                     int phase = 0, double* rootsSend = nullptr, const double* rootsRecv = nullptr);
@@ -283,6 +286,16 @@ private:
     void blockPass(int I, int J, const std::vector<double>& mix, const double* x, int64_t ldx, bool tree,
                    const double* sig, double* out8, int64_t ldo, hipStream_t s);
     void checkBlockLimit(bool shardedCall) const;
+    // pass (I, J)'s sub-block of the mixes and its harmonic weights
+    void passMix(int I, int J, const std::vector<double>& mix, std::vector<double>& sub, HarmWeights& hw) const;
+    // ks > kMaxRhs on a shard: per input chunk one exchange and one up pass, per output
+    // chunk under it the window's near field, M2L and down pass
+    void blockOpShardedPasses(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s);
+    // the exchange of one sharded matvec (or of one input chunk of its passes) around
+    // the two phases: nb rows of x, the one- or the two-collective form
+    void shardedExchange(int nb, double* x, int64_t ldx, bool one, hipStream_t s, const std::function<void()>& phase1,
+                         const std::function<void()>& phase2);
+    bool shardPass = false;  // inside blockOpShardedPasses: phase 2 keeps the pending state for its repeats
     // mapping of a mode whose operators are not resident: one pass of the offset form
     void leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask);
     // the modes of a batched apply are usable by it: tables for the harmonic launches,

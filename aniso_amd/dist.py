@@ -243,7 +243,8 @@ def native_comm_init(op, world, backend="nccl"):
 
 def native_block_matvec(op, nb, device, which=2):
     """apply(x, y) for aniso_amd.solve.gmres_dist on this rank's owned slices over the
-    library's one-call sharded operator (aniso_block_op_sharded_dev)."""
+    library's one-call sharded operator (aniso_block_op_sharded_dev); any nb = ks
+    (more than 8 blocks: ceil(ks / 8) exchanges per matvec)."""
     import torch
 
     b, e = op.shard()
