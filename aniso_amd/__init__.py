@@ -128,6 +128,7 @@ def lib():
             "aniso_krylov_dot": [P, I64, I, P, I64, P, P, P],
             "aniso_krylov_update": [P, I64, I, P, I64, P, P, P, I, P],
             "aniso_block_op_sharded_dev": [P, I, P, I64, P, I64, P],
+            "aniso_block_solve_sharded_dev": [P, P, I64, P, I64, I, D, I, dp, I, ip, dp, P],
             "aniso_arnoldi_state_size": [I, lp],
             "aniso_arnoldi_begin": [P, I64, I, P, I64, P, P, D, P, P],
             "aniso_arnoldi_step": [P, I64, I, I, P, I64, P, P, P, P],
@@ -721,6 +722,26 @@ class Aniso:
                                                 int(x.stride(0)), ctypes.c_void_p(y.data_ptr()), int(y.stride(0)),
                                                 ctypes.c_void_p(s)))
         return y
+
+    def block_solve_sharded_dev(self, rhs_owned, x_owned, restart=400, tol=1e-11, maxit=400, stream=None):
+        """aniso.m's gmres(A, rhs, restart, tol, maxit), A = u - mforward(u), across the ranks
+        of a sharded handle (aniso_block_solve_sharded_dev; every rank together, after
+        set_shard, the caches and comm_init_*).  rhs_owned, x_owned: this rank's owned
+        slices in tree order, (ks, >= n_owned()) float64 CUDA tensors with unit column
+        stride; x_owned holds the initial guess and receives the solution.  Returns
+        (iters, hist, relres), the same on every rank."""
+        import torch
+
+        own = self.n_owned()
+        pr, px = _dev_rows(rhs_owned, self.ks, own, "rhs_owned"), _dev_rows(x_owned, self.ks, own, "x_owned")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        hist = np.zeros(max(min(int(restart) * int(maxit), 100000), 1))
+        it, rr = ctypes.c_int(), ctypes.c_double()
+        _check(lib().aniso_block_solve_sharded_dev(self.address, pr, int(rhs_owned.stride(0)), px,
+                                                   int(x_owned.stride(0)), int(restart), float(tol), int(maxit),
+                                                   _dp(hist), len(hist), ctypes.byref(it), ctypes.byref(rr),
+                                                   ctypes.c_void_p(s)))
+        return it.value, hist[: min(abs(it.value), len(hist))], rr.value
 
     def set_shard(self, rank, nranks):
         _check(lib().aniso_set_shard(self.address, int(rank), int(nranks)))

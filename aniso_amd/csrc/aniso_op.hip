@@ -2224,6 +2224,13 @@ void Operator::commInit(std::unique_ptr<Collectives> c) {
         dOxRecvBuf.alloc((size_t)std::max<int64_t>(ro, 1) * sizeof(double));
         oxReady = true;
     }
+    if (c->loopback()) {
+        // no peer ever fills the receive buffers: zeros stand in for the peers' data, so a
+        // rank's schedule runs on finite values (an iteration on it -- the sharded block
+        // solve -- would otherwise spread whatever the allocation held)
+        for (DevBuf* b : {&dHxRecvBuf, &dXRootsRecv, &dOxRecvBuf})
+            if (b->p) HIP_CHECK(hipMemset(b->p, 0, b->bytes));
+    }
     comm = std::move(c);
 }
 
@@ -2270,21 +2277,61 @@ bool Operator::oneExchangeUsable(int which) {
 void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s) {
     if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
     if (ldx < geo.N || ldy < geo.N) throw std::invalid_argument("sharded block operator: leading dimension below N");
+    blockOpShardedOwned(which, x, ldx, y + plan.ownBegin, ldy, s);
+}
+
+// the same with the output given as its owned slice: row b of the result starts at
+// yo + b * ldo (ldo >= owned).  The public call passes y + own_begin at stride ldy; the
+// sharded block solve its compact (ks, owned) vector.
+void Operator::blockOpShardedOwned(int which, double* x, int64_t ldx, double* yo, int64_t ldo, hipStream_t s) {
+    if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
+    if (ldx < geo.N || ldo < plan.ownEnd - plan.ownBegin)
+        throw std::invalid_argument("sharded block operator: leading dimension too small");
     ensureDevice();
     if (ks > kMaxRhs) {  // P input chunks, each with one exchange and P output windows
-        blockOpShardedPasses(which, x, ldx, y, ldy, s);
+        blockOpShardedPasses(which, x, ldx, yo, ldo, s);
         return;
     }
-    double* yo = y + plan.ownBegin;
     const bool one = oneExchangeUsable(which);
     shardedExchange(
         ks, x, ldx, one, s,
-        [&] { blockOpDev(which, x, ldx, yo, ldy, true, s, NAN, nullptr, 1, dXRootsSend.as<double>(), nullptr); },
-        [&] { blockOpDev(which, x, ldx, yo, ldy, true, s, NAN, nullptr, 2, nullptr, dXRootsRecv.as<double>()); });
+        [&] { blockOpDev(which, x, ldx, yo, ldo, true, s, NAN, nullptr, 1, dXRootsSend.as<double>(), nullptr); },
+        [&] { blockOpDev(which, x, ldx, yo, ldo, true, s, NAN, nullptr, 2, nullptr, dXRootsRecv.as<double>()); });
     if (one) {
         ++oneXApplies;
         if (oxUp) ++upPartialApplies;
     }
+}
+
+// What a sharded x - mforward(x) can refuse, or fail to allocate, on one rank alone --
+// raised here, before the caller's first collective (the sharded block solve): the
+// state checks of the matvec and every work buffer it would size on its way.
+void Operator::prepareShardedMatvec() {
+    if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
+    if (!coeffSet) throw std::runtime_error("block operator before setCoeff");
+    if (!cachesReady())
+        throw std::logic_error("sharded block operator before cache(): every rank caches its modes first");
+    ensureDevice();
+    const int64_t N = geo.N, own = plan.ownEnd - plan.ownBegin;
+    constexpr int K = kMaxRhs;
+    if (ks > K) {
+        if (!useAtt || plan.nearPartTotal != 0)
+            throw std::invalid_argument("sharded block operator: ks = " + std::to_string(ks) + " blocks (more than " +
+                                        std::to_string(kMaxRhs) + ") run as passes over the mode-shared caches with "
+                                        "directed near storage");
+        dPassOut.alloc((size_t)K * N * sizeof(double));
+        if (ks % K) dPassIn.alloc((size_t)K * N * sizeof(double));
+        dBlk.alloc((size_t)ks * own * sizeof(double));
+        ensureWork(K);
+        return;
+    }
+    const int Kp = rhs_supported(ks) ? ks : rhs_padded(ks);
+    if (Kp != ks) {
+        dPadIn.alloc((size_t)Kp * N * sizeof(double));
+        dPadOut.alloc((size_t)Kp * N * sizeof(double));
+    }
+    if (!(fuseSub && rhs_supported(ks) && !plan.dnDesc.empty())) dBlk.alloc((size_t)ks * own * sizeof(double));
+    ensureWork(Kp);
 }
 
 // More than kMaxRhs blocks on a shard.  The input chunk J is the
@@ -2297,7 +2344,7 @@ void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, i
 // matvec so issues P exchanges, not P^2.  Every rank takes the same route: the form
 // is commInit's all-gathered decision (oxReady), and everything that can fail on one
 // rank alone is checked, and every work buffer sized, before the first collective.
-void Operator::blockOpShardedPasses(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s) {
+void Operator::blockOpShardedPasses(int which, double* x, int64_t ldx, double* yo, int64_t ldy, hipStream_t s) {
     constexpr int K = kMaxRhs;
     const int P = (ks + K - 1) / K, nm = 2 * ks - 1;
     const int64_t N = geo.N, own = plan.ownEnd - plan.ownBegin;
@@ -2323,7 +2370,7 @@ void Operator::blockOpShardedPasses(int which, double* x, int64_t ldx, double* y
     for (int m = 0; m < nm; ++m) ids[m] = m;
     dPassOut.alloc((size_t)K * N * sizeof(double));
     if (ks % K) dPassIn.alloc((size_t)K * N * sizeof(double));
-    double* acc = y + plan.ownBegin;
+    double* acc = yo;
     int64_t lda = ldy;
     if (which == 2) {  // x - mforward(x): the passes sum into dBlk
         dBlk.alloc((size_t)ks * own * sizeof(double));
@@ -2375,7 +2422,7 @@ void Operator::blockOpShardedPasses(int which, double* x, int64_t ldx, double* y
             });
         pend.active = false;
     }
-    if (which == 2) launch_sub_slice(own, ks, x + plan.ownBegin, ldx, dBlk.as<double>(), own, y + plan.ownBegin, ldy, s);
+    if (which == 2) launch_sub_slice(own, ks, x + plan.ownBegin, ldx, dBlk.as<double>(), own, yo, ldy, s);
     if (one) {
         ++oneXApplies;
         if (oxUp) ++upPartialApplies;

@@ -144,6 +144,13 @@ public:
                      int maxOuter, int maxCycles, int* outer, double* rel, hipStream_t s);
     int blockSolveHost(const double* rhs, double* x, int restart, double tol, int maxit, double* hist, int maxhist,
                        double* relres);
+    // the same solve on a sharded handle with a communicator, every rank together
+    // (DESIGN.md §3.17): rhs / x are this rank's owned slices in tree order, ks rows of
+    // `owned` doubles at strides ldr / ldx (device).  Every branch is taken from
+    // all-reduced values, so the ranks issue the same collectives and return the same
+    // counts; a refusal or a device-side failure of one rank ends the call on all.
+    int blockSolveShardedDev(const double* rhs, int64_t ldr, double* x, int64_t ldx, int restart, double tol,
+                             int maxit, double* hist, int maxhist, double* relres, hipStream_t s);
     // config 5's fp32 operator (f32op.hip): Y = X - K_0(sigma_s .* X)
     // for 16 right-hand sides, X and Y point-major (N x 16 floats, tree order), every
     // FMM translation a 16 x 16 x 16 MFMA product on fp32 caches (built from the
@@ -290,7 +297,16 @@ private:
     void passMix(int I, int J, const std::vector<double>& mix, std::vector<double>& sub, HarmWeights& hw) const;
     // ks > kMaxRhs on a shard: per input chunk one exchange and one up pass, per output
     // chunk under it the window's near field, M2L and down pass
-    void blockOpShardedPasses(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s);
+    // (yo: the owned slice of the output, row b at yo + b * ldo)
+    void blockOpShardedPasses(int which, double* x, int64_t ldx, double* yo, int64_t ldo, hipStream_t s);
+    // blockOpShardedDev with the output as its owned slice (ldo >= owned): the sharded
+    // block solve's matvec writes its compact vector
+    void blockOpShardedOwned(int which, double* x, int64_t ldx, double* yo, int64_t ldo, hipStream_t s);
+    // the sharded matvec's rank-local checks and work buffers, ahead of any collective
+    void prepareShardedMatvec();
+    // the sharded block solve: the matvec's (ks, N) input and the all-reduce buffer,
+    // kept between solves (grown, never shrunk)
+    DevBuf dShIn, dShRed;
     // the exchange of one sharded matvec (or of one input chunk of its passes) around
     // the two phases: nb rows of x, the one- or the two-collective form
     void shardedExchange(int nb, double* x, int64_t ldx, bool one, hipStream_t s, const std::function<void()>& phase1,
@@ -389,7 +405,8 @@ private:
     bool oneExchangeLocal() const;  // this rank's (shard- and process-dependent) part, gathered at commInit
     // sticky time-out flag of the fused launch's in-kernel hand-offs, in host-visible
     // memory (the kernel stores 1 there when a wait gives up; checked at every API
-    // entry and by sync(), never read on the device)
+    // entry and by sync(); read on the device only by the sharded block solve, which
+    // sums it over the ranks inside its all-reduces)
     unsigned* topErr = nullptr;
     // ANISO_TOP_SPIN_LIMIT: polls of a tier counter (~1 us each) before a waiting block of
     // the fused launch computes the tier itself (tests: 0 makes every waiter compute)

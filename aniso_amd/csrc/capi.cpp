@@ -915,6 +915,18 @@ int aniso_block_op_sharded_dev(aniso_handle h, int which, double* x, int64_t ldx
     });
 }
 
+int aniso_block_solve_sharded_dev(aniso_handle h, const double* rhs, int64_t ldr, double* x, int64_t ldx, int restart,
+                                  double tol, int maxit, double* hist, int maxhist, int* iters, double* relres,
+                                  void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        auto& op = get(h);  // (null rhs / x: refused inside, with the other rank-local checks)
+        const int it = op.blockSolveShardedDev(rhs, ldr, x, ldx, restart, tol, maxit, hist, hist ? maxhist : 0, relres,
+                                               (hipStream_t)stream);
+        if (iters) *iters = it;
+    });
+}
+
 int aniso_memcpy(void* dst, const void* src, size_t bytes) {
     return guarded([&] {
         if (bytes == 0) return;

@@ -4,8 +4,10 @@
 // BLAS-1 reductions use a fixed two-level tree so results are deterministic.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <exception>
 #include <stdexcept>
 #include <type_traits>
 #include <vector>
@@ -737,6 +739,235 @@ int Operator::blockSolveDev(const double* rhs, double* x, int restart, double to
     HIP_CHECK(hipStreamSynchronize(s));
     ownTimeline = false;
     checkDeviceErrors();  // every apply was checked at its recovery point: a flag here is new
+    if (relresOut) *relresOut = relres;
+    return conv ? total : -std::max(total, 1);
+}
+
+// ---- the block solve across ranks: the small device pieces beside the
+// sharded matvec and the DCGS2 sweeps
+// dst[r * ldd + i] = src[r * lds + i] for i < len; blockIdx.y = the row r
+__global__ void __launch_bounds__(256) k_rows_copy(int64_t len, const double* __restrict__ src, int64_t lds,
+                                                   double* __restrict__ dst, int64_t ldd) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < len) dst[(size_t)blockIdx.y * ldd + i] = src[(size_t)blockIdx.y * lds + i];
+}
+
+// an all-reduce entry that counts the ranks in trouble: `add` plus 1 if this rank's
+// sticky device-failure word (err: the fused launch's time-out flag, may be null) is set
+__global__ void k_flag_put(const unsigned* __restrict__ err, double add, double* __restrict__ slot) {
+    if (threadIdx.x == 0) *slot = add + (err && *(const volatile unsigned*)err != 0 ? 1.0 : 0.0);
+}
+
+// n (<= 64) all-reduced words into the mapped status
+__global__ void k_words(const double* __restrict__ src, int n, double* __restrict__ dst) {
+    if ((int)threadIdx.x < n) dst[threadIdx.x] = src[threadIdx.x];
+}
+
+static void rows_copy(int rows, int64_t len, const double* src, int64_t lds, double* dst, int64_t ldd, hipStream_t s) {
+    if (rows < 1 || len < 1) return;
+    k_rows_copy<<<dim3(nblk(len), (unsigned)rows), 256, 0, s>>>(len, src, lds, dst, ldd);
+    HIP_LAUNCH_CHECK();
+}
+
+// blockSolveDev's loop on this rank's compact owned vectors (L = ks x owned, contiguous
+// rows), every rank of the communicator together.  The matvec is the one-call sharded
+// operator: V[j] goes into the own-range columns of the handle's (ks, N) input with one
+// strided copy, and the operator writes its owned output straight into w.  A step is
+//   project -> k_arn_rows -> all-reduce (j + 1) -> k_arn_coef(P = 1) -> update ->
+//   k_arn_rows -> all-reduce (j + 2 sums + the failure flag) -> k_arn_column(P = 1),
+// a cycle starts with project(V0, V0) -> all-reduce (|r|^2 + the flag) -> k_arn_begin.
+// No rank may take a branch of its own: every decision below reads all-reduced values
+// (the status words the begin / column kernels compute from the reduced sums are
+// bit-identical on every rank if the all-reduce delivers the same bits to every rank),
+// never a local norm.  What one rank alone can refuse -- arguments, cache state, the
+// allocations -- is evaluated before the first collective and summed as a flag in it:
+// either every rank starts, or every rank returns with no further collective.  A
+// device-side time-out is not recovered locally (a restart on the tier launches would
+// change one rank's collectives): the flag travels in each step's second all-reduce and
+// in each cycle start's, reaches the host with the status word, and ends the call on
+// every rank at the same step.
+int Operator::blockSolveShardedDev(const double* rhs, int64_t ldr, double* x, int64_t ldx, int restart, double tol,
+                                   int maxit, double* hist, int maxhist, double* relresOut, hipStream_t s) {
+    if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
+    ensureDevice();
+    const int64_t N = geo.N, ob = plan.ownBegin, owned = plan.ownEnd - plan.ownBegin, L = (int64_t)ks * owned;
+    const int m = restart;
+    // the all-reduce buffer first: a rank that refuses still takes part in the opening collective
+    {
+        const size_t need = (size_t)((restart >= 1 && restart < (1 << 24) ? restart : 1) + 8) * sizeof(double);
+        if (dShRed.bytes < need) dShRed.alloc(need);
+    }
+    double* red = dShRed.as<double>();
+    DevBuf bB, bX, bW, bV, bSt;
+    struct HostStat {
+        double* p = nullptr;
+        hipEvent_t ev = nullptr;
+        ~HostStat() {
+            if (p) (void)hipHostFree(p);
+            if (ev) (void)hipEventDestroy(ev);
+        }
+    } hs;
+    double* stat = nullptr;
+    unsigned* errDev = nullptr;
+    // ---- everything that can fail on this rank alone
+    std::exception_ptr refused;
+    try {
+        if (!rhs || !x) throw std::invalid_argument("sharded block solve: rhs or x is NULL");
+        if (ldr < owned || ldx < owned) throw std::invalid_argument("sharded block solve: leading dimension below the owned size");
+        if (restart < 1 || maxit < 1 || !(tol > 0.0))
+            throw std::invalid_argument("block solve needs restart >= 1, maxit >= 1, tol > 0");
+        prepareShardedMatvec();
+        checkDeviceErrors();
+        bB.alloc(L * sizeof(double));
+        bX.alloc(L * sizeof(double));
+        bW.alloc(L * sizeof(double));
+        bV.alloc((size_t)(m + 1) * L * sizeof(double));
+        bSt.alloc((size_t)arn::Layout(m).total * sizeof(double));
+        if (dShIn.bytes < (size_t)ks * N * sizeof(double)) {
+            dShIn.alloc((size_t)ks * N * sizeof(double));
+            HIP_CHECK(hipMemsetAsync(dShIn.p, 0, dShIn.bytes, s));  // outside the own range: the exchange's halo
+        }
+        arnoldiParts(m + 2);
+        HIP_CHECK(hipHostMalloc((void**)&hs.p, 4 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_CHECK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
+        HIP_CHECK(hipHostGetDevicePointer((void**)&stat, hs.p, 0));
+        HIP_CHECK(hipHostGetDevicePointer((void**)&errDev, topErr, 0));
+    } catch (...) {
+        refused = std::current_exception();
+    }
+    double *b = bB.as<double>(), *xt = bX.as<double>(), *w = bW.as<double>();
+    double* V = bV.as<double>();
+    double* st = bSt.as<double>();
+    double* xin = dShIn.as<double>();
+    // ---- the opening all-reduce: {ranks that refuse, |b|^2, |x0|^2}
+    HIP_CHECK(hipMemsetAsync(red, 0, 3 * sizeof(double), s));
+    k_flag_put<<<1, 64, 0, s>>>(nullptr, refused ? 1.0 : 0.0, red);
+    HIP_LAUNCH_CHECK();
+    if (!refused) {
+        rows_copy(ks, owned, rhs, ldr, b, owned, s);
+        rows_copy(ks, owned, x, ldx, xt, owned, s);
+        double* part = dKryPart.as<double>();
+        arn::launch_project(L, 1, b, L, b, part, s);
+        arn::k_arn_rows<<<1, arn::kThreads, sizeof(double), s>>>(part, arn::kParts, 1, red + 1);
+        arn::launch_project(L, 1, xt, L, xt, part, s);
+        arn::k_arn_rows<<<1, arn::kThreads, sizeof(double), s>>>(part, arn::kParts, 1, red + 2);
+        HIP_LAUNCH_CHECK();
+    }
+    comm->allreduce(red, 3, s);
+    double opening[3] = {0.0, 0.0, 0.0};
+    HIP_CHECK(hipMemcpyAsync(opening, red, sizeof(opening), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (refused) std::rethrow_exception(refused);
+    if (opening[0] != 0.0)
+        throw std::invalid_argument("sharded block solve: another rank refused the call (its own error says why); "
+                                    "no rank started and nothing was changed");
+    struct Restore {
+        bool& f;
+        bool v;
+        ~Restore() { f = v; }
+    } ownTl{ownTimeline, ownTimeline};
+    ownTimeline = true;  // the applies' entry checks leave the failure flag to the all-reduces below
+    auto post = [&] { HIP_CHECK(hipEventRecord(hs.ev, s)); };
+    auto failed = [&]() {
+        HIP_CHECK(hipStreamSynchronize(s));  // (a look-ahead matvec may be in flight; every rank enqueued it)
+        *(volatile unsigned*)topErr = 0;
+        throw std::runtime_error("sharded block solve: a rank reported a device-side failure (a hand-off time-out of "
+                                 "its fused top-of-tree launch); every rank left the solve at the same step and x "
+                                 "is unchanged");
+    };
+    // w = A v: v (compact) into the own-range columns of the (ks, N) input, the owned output into w
+    auto matvec = [&](const double* v) {
+        rows_copy(ks, owned, v, owned, xin + ob, N, s);
+        blockOpShardedOwned(2, xin, N, w, owned, s);
+    };
+    const double normb = std::sqrt(opening[1]);
+    bool xZero = normb > 0.0 && opening[2] == 0.0;  // A 0 = 0: no matvec for the first residual
+    // r = b - A x into V[0], |r|^2 summed over the ranks, the cycle's start; returns |r| / |b|
+    auto residual = [&] {
+        if (xZero) {
+            if (L > 0) HIP_CHECK(hipMemcpyAsync(V, b, L * sizeof(double), hipMemcpyDeviceToDevice, s));
+        } else {
+            matvec(xt);
+            if (L > 0) k_sub<<<nblk(L), 256, 0, s>>>(L, b, w, V);
+        }
+        double* part = dKryPart.as<double>();
+        arn::launch_project(L, 1, V, L, V, part, s);
+        arn::k_arn_rows<<<1, arn::kThreads, sizeof(double), s>>>(part, arn::kParts, 1, red);
+        k_flag_put<<<1, 64, 0, s>>>(errDev, 0.0, red + 1);
+        HIP_LAUNCH_CHECK();
+        comm->allreduce(red, 2, s);
+        arn::k_arn_begin<<<1, arn::kThreads, 0, s>>>(m, st, red, 1, normb, stat);
+        k_words<<<1, 64, 0, s>>>(red + 1, 1, stat + 3);
+        HIP_LAUNCH_CHECK();
+        post();
+        HIP_CHECK(hipEventSynchronize(hs.ev));
+        if (hs.p[3] != 0.0) failed();
+        return hs.p[0];
+    };
+    int nh = 0, total = 0;
+    double relres = 0.0;
+    bool conv = false;
+    if (normb == 0.0) {
+        if (L > 0) HIP_CHECK(hipMemsetAsync(xt, 0, L * sizeof(double), s));
+        conv = true;
+    } else {
+        relres = residual();
+        conv = relres <= tol;
+        std::vector<double> hrel;
+        for (int cyc = 0; cyc < maxit && !conv; ++cyc) {
+            if (hs.p[1] == 0.0) break;  // |r| = 0 in floating point
+            int used = 0;
+            bool ahead = false;  // the matvec of V[j] is already enqueued
+            hrel.clear();
+            for (int j = 0; j < m; ++j) {
+                if (!ahead) matvec(V + (size_t)j * L);
+                double* part = dKryPart.as<double>();
+                arn::launch_project(L, j + 1, V, L, w, part, s);
+                arn::k_arn_rows<<<1, arn::kThreads, (size_t)(j + 1) * sizeof(double), s>>>(part, arn::kParts, j + 1, red);
+                HIP_LAUNCH_CHECK();
+                comm->allreduce(red, (size_t)j + 1, s);
+                arn::k_arn_coef<<<1, arn::kThreads, arn::coef_lds(j), s>>>(m, j, st, red, 1);
+                HIP_LAUNCH_CHECK();
+                arn::launch_update(L, j + 1, V, L, w, st, m, part, s);
+                arn::k_arn_rows<<<1, arn::kThreads, (size_t)(j + 2) * sizeof(double), s>>>(part, arn::kParts, j + 2, red);
+                k_flag_put<<<1, 64, 0, s>>>(errDev, 0.0, red + j + 2);
+                HIP_LAUNCH_CHECK();
+                comm->allreduce(red, (size_t)j + 3, s);
+                arn::k_arn_column<<<1, arn::kThreads, arn::column_lds(j), s>>>(m, j, st, red, 1, stat);
+                k_words<<<1, 64, 0, s>>>(red + j + 2, 1, stat + 3);
+                HIP_LAUNCH_CHECK();
+                post();
+                // the look-ahead matvec and its prediction as blockSolveDev's, from the
+                // estimates every rank holds alike: all ranks enqueue it, or none
+                bool near = false;
+                if (hrel.size() >= 2) {
+                    const double q = std::min(1.0, hrel.back() / hrel[hrel.size() - 2]);
+                    near = hrel.back() * q <= 10.0 * tol;
+                } else if (!hrel.empty()) {
+                    near = hrel.back() <= 10.0 * tol;
+                }
+                ahead = j + 1 < m && !near;
+                if (ahead) matvec(V + (size_t)(j + 1) * L);
+                HIP_CHECK(hipEventSynchronize(hs.ev));
+                if (hs.p[3] != 0.0) failed();
+                const double rel = hs.p[0], rnext = hs.p[1];
+                if (hs.p[2] != (double)(j + 1))  // the column kernel of this step did not run
+                    throw std::runtime_error("block solve: Arnoldi step " + std::to_string(j) + " left no status");
+                ++total;
+                used = j + 1;
+                relres = rel;
+                hrel.push_back(rel);
+                if (hist && nh < maxhist) hist[nh++] = rel;
+                if (rel <= tol || rnext == 0.0) break;  // converged (estimate) or lucky breakdown
+            }
+            arnoldiSolution(L, m, used, V, L, st, xt, s);  // x += P T R^-1 g
+            xZero = xZero && used == 0;
+            relres = residual();
+            conv = relres <= tol;
+        }
+    }
+    rows_copy(ks, owned, xt, owned, x, ldx, s);
+    HIP_CHECK(hipStreamSynchronize(s));
     if (relresOut) *relresOut = relres;
     return conv ? total : -std::max(total, 1);
 }

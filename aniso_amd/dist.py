@@ -257,3 +257,19 @@ def native_block_matvec(op, nb, device, which=2):
         y.copy_(fy[:, b:e])
 
     return apply
+
+
+def native_block_solve(op, rhs_owned, x0_owned=None, restart=400, tol=1e-11, maxit=400):
+    """aniso.m's block solve across the ranks, wholly in the library
+    (Aniso.block_solve_sharded_dev, aniso_block_solve_sharded_dev): every rank passes its
+    owned tree-order slice of the right-hand side ((ks, n_owned) float64 CUDA tensor) and,
+    optionally, of the initial guess.  Returns (x_owned, iters, hist, relres); iters, hist
+    and relres are the same on every rank.  gmres_dist over native_block_matvec is the
+    torch-driven form of the same solve."""
+    import torch
+
+    x = torch.zeros_like(rhs_owned) if x0_owned is None else x0_owned.clone()
+    rhs = rhs_owned if rhs_owned.stride(-1) == 1 else rhs_owned.contiguous()
+    x = x if x.stride(-1) == 1 else x.contiguous()
+    iters, hist, relres = op.block_solve_sharded_dev(rhs, x, restart=restart, tol=tol, maxit=maxit)
+    return x, iters, hist, relres
