@@ -696,8 +696,9 @@ void Operator::mappingBatchedHost(const double* Q, int k, int id, double* Out) {
         for (int i = 0; i < nb; ++i) eye[(size_t)i * nb + i] = 1.0;
         HIP_CHECK(hipMemcpyAsync(dq.p, Q + (size_t)j0 * N, (size_t)nb * N * sizeof(double), hipMemcpyHostToDevice, own));
         if (plan.nranks > 1) HIP_CHECK(hipMemsetAsync(dout.p, 0, dout.bytes, own));
+        ApplyCall call;
         applyBlock(nb, dq.as<double>(), N, false, nullptr, 1, &id, eye.data(), dout.as<double>(), N, false, own,
-                   kStageAll);
+                   kStageAll, call);
         HIP_CHECK(hipMemcpyAsync(Out + (size_t)j0 * N, dout.p, (size_t)nb * N * sizeof(double), hipMemcpyDeviceToHost,
                                  own));
         HIP_CHECK(hipStreamSynchronize(own));
@@ -740,22 +741,16 @@ void Operator::leanMapping(const double* charge, int id, double* out, hipStream_
     double* const orow = dPassOut.as<double>() + (size_t)row * N;
     // a shard writes its owned targets only: the others keep the caller's values
     if (plan.nranks > 1) HIP_CHECK(hipMemcpyAsync(orow, out, N * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HarmWeights hw;
-    std::memset(&hw, 0, sizeof(hw));
-    hw.hw[0] = 1.0;
-    hw.om[row] = 1.0;
-    hw.dw[row] = id == 0 ? 1.0 : 0.0;
+    ApplyCall call;
+    call.pass = true;
+    call.win = HarmWindow{i0, 0};
+    call.hw.hw[0] = 1.0;
+    call.hw.om[row] = 1.0;
+    call.hw.dw[row] = id == 0 ? 1.0 : 0.0;
     std::vector<double> sub((size_t)K * K, 0.0);  // the correction fold: mode id, input row 0 to output row `row`
     sub[(size_t)row * K] = 1.0;
-    const HarmWindow win{i0, 0};
-    struct Restore {
-        const HarmWindow*& w;
-        ~Restore() { w = nullptr; }
-    } restore{passWin};
-    passWin = &win;
-    passHw = hw;
     applyBlock(K, dPassIn.as<double>(), N, false, nullptr, 1, &id, sub.data(), dPassOut.as<double>(), N, false, s,
-               kStageAll);
+               kStageAll, call);
     HIP_CHECK(hipMemcpyAsync(out, orow, N * sizeof(double), hipMemcpyDeviceToDevice, s));
 }
 
@@ -781,8 +776,10 @@ void Operator::forwardTreePhase(int phase, const double* xTree, double* ySlice, 
     pendingCall(phase, PendingCall{0, 0, xTree, ySlice, dSigmaT.p, geo.N, 0, 0.0});
     const double one = 1.0;
     const int id = 0;
+    ApplyCall call;
+    call.phased(phase, rootsSend, rootsRecv);
     applyBlock(1, xTree, geo.N, true, dSigmaT.as<double>(), 1, &id, &one, dTmpS.as<double>(), geo.N, true, s,
-               kStageAll, phase, rootsSend, rootsRecv);
+               kStageAll, call);
     if (phase == 1) return;
     const int64_t n = plan.ownEnd - plan.ownBegin;
     launch_sub_slice(n, 1, xTree + plan.ownBegin, n, dTmpS.as<double>(), n, ySlice, n, s);
@@ -791,7 +788,8 @@ void Operator::forwardTreePhase(int phase, const double* xTree, double* ySlice, 
 void Operator::apply(const double* charge, bool treeIn, const double* sigT, int id, double* out, bool treeOut,
                      hipStream_t s, int mask) {
     const double one = 1.0;
-    applyBlock(1, charge, geo.N, treeIn, sigT, 1, &id, &one, out, geo.N, treeOut, s, mask);
+    ApplyCall call;
+    applyBlock(1, charge, geo.N, treeIn, sigT, 1, &id, &one, out, geo.N, treeOut, s, mask, call);
 }
 
 void Operator::applyBlockDev(int nrhs, const double* x, int64_t ldx, bool treeIn, bool useSigma, int nterm,
@@ -799,8 +797,9 @@ void Operator::applyBlockDev(int nrhs, const double* x, int64_t ldx, bool treeIn
                              hipStream_t s, int mask) {
     if (useSigma && !coeffSet) throw std::runtime_error("block apply with sigma_s before setCoeff");
     ensureDevice();
+    ApplyCall call;
     applyBlock(nrhs, x, ldx, treeIn, useSigma ? dSigmaT.as<double>() : nullptr, nterm, ids, mixes, out, ldo, treeOut,
-               s, mask);
+               s, mask, call);
 }
 
 int Operator::mark(hipStream_t s) {
@@ -878,6 +877,22 @@ const CorrFold& Operator::corrTable(int K, int nterm, const int* ids, const doub
     return f;
 }
 
+// nterm K x K mixes in the top-left corners of Kp x Kp ones (zero right-hand sides pad the rest)
+static std::vector<double> padMixes(int K, int Kp, int nterm, const double* mixes) {
+    std::vector<double> mp((size_t)nterm * Kp * Kp, 0.0);
+    for (int t = 0; t < nterm; ++t)
+        for (int i = 0; i < K; ++i)
+            for (int b = 0; b < K; ++b) mp[((size_t)t * Kp + i) * Kp + b] = mixes[((size_t)t * K + i) * K + b];
+    return mp;
+}
+
+// the mode ids 0 .. nm - 1 of a block operator's terms
+static std::vector<int> modeIds(int nm) {
+    std::vector<int> ids(nm);
+    for (int m = 0; m < nm; ++m) ids[m] = m;
+    return ids;
+}
+
 // One batched apply: the up pass over the K base vectors, then per term t (mode
 // ids[t], mix mixes[t]) the near field, the corrections, the M2L stream and its
 // gather, each accumulating; then one down pass.  sigT (sigma_s in tree order, or
@@ -888,20 +903,23 @@ const CorrFold& Operator::corrTable(int K, int nterm, const int* ids, const doub
 // (plan.xT0Tasks), packs its roots into rootsSend and starts the near field and
 // corrections (they need only the weighted charges of the rank's own and halo
 // points); phase 2 scatters rootsRecv, runs the upper tiers (every rank), the M2L
-// and the down pass.
+// and the down pass.  `call` says which of these, and what else, this call is (ApplyCall).
 void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, const double* sigT, int nterm,
                           const int* ids, const double* mixes, double* out, int64_t ldo, bool treeOut, hipStream_t s,
-                          int mask, int phase, double* rootsSend, const double* rootsRecv) {
+                          int mask, ApplyCall& call) {
+    const int phase = call.phase;
+    double* const rootsSend = call.rootsSend;
+    const double* const rootsRecv = call.rootsRecv;
     if (K < 1 || K > 8) throw std::invalid_argument("block apply supports 1..8 right-hand sides, got " + std::to_string(K));
     checkDeviceErrors();
     if (nterm < 1) throw std::invalid_argument("block apply needs at least one mode term");
-    checkModes(K, nterm, ids, mixes);
+    checkModes(K, nterm, ids, mixes, call);
     if (phase != 0 && !treeIn) throw std::invalid_argument("a sharded (two-phase) apply takes tree-order input");
     if (phase == 1 && plan.xRootChunk > 0 && !rootsSend) throw std::invalid_argument("sharded apply: null roots_send");
     if (phase == 2 && plan.xRootChunk > 0 && !rootsRecv) throw std::invalid_argument("sharded apply: null roots_recv");
     if (phase >= 2 && !(pend.active && pend.K == rootRhs(K)))
         throw std::logic_error("sharded apply: end without a matching begin");
-    if (phase == 3 && !(shardPass && passWin)) throw std::logic_error("sharded apply: a repeated phase 2 outside a pass");
+    if (phase == 3 && !(call.shardedPass && call.pass)) throw std::logic_error("sharded apply: a repeated phase 2 outside a pass");
     ensureDevice();
     const int64_t nOut = treeOut ? plan.ownEnd - plan.ownBegin : geo.N;
     if (ldx < geo.N || ldo < nOut) throw std::invalid_argument("block apply: leading dimension too small");
@@ -914,12 +932,9 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
             HIP_CHECK(hipMemcpy2DAsync(dPadIn.p, geo.N * sizeof(double), x, ldx * sizeof(double),
                                        geo.N * sizeof(double), K, hipMemcpyDeviceToDevice, s));
         }
-        std::vector<double> mp((size_t)nterm * Kp * Kp, 0.0);
-        for (int t = 0; t < nterm; ++t)
-            for (int i = 0; i < K; ++i)
-                for (int b = 0; b < K; ++b) mp[((size_t)t * Kp + i) * Kp + b] = mixes[((size_t)t * K + i) * K + b];
+        const std::vector<double> mp = padMixes(K, Kp, nterm, mixes);
         applyBlock(Kp, dPadIn.as<double>(), geo.N, treeIn, sigT, nterm, ids, mp.data(), dPadOut.as<double>(), geo.N,
-                   treeOut, s, mask, phase, rootsSend, rootsRecv);
+                   treeOut, s, mask, call);
         if (phase != 1)
             HIP_CHECK(hipMemcpy2DAsync(out, ldo * sizeof(double), dPadOut.p, geo.N * sizeof(double),
                                        nOut * sizeof(double), K, hipMemcpyDeviceToDevice, s));
@@ -942,9 +957,9 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     // one pass of a block operator of more than kMaxRhs blocks (blockPass): its weights
     // come with it, and it runs the plain harmonic launches in their offset form; without
     // the mode-shared caches the pass's sub-mixes take the per-mode stream like any mix
-    const HarmWindow* const win = passWin && useAtt && attReady && plan.nearPartTotal == 0 ? passWin : nullptr;
-    if (win) hw = passHw;
-    if (shardPass && !(win && phase != 0)) throw std::logic_error("sharded pass: not the offset harmonic form");
+    const HarmWindow* const win = call.pass && useAtt && attReady && plan.nearPartTotal == 0 ? &call.win : nullptr;
+    if (win) hw = call.hw;
+    if (call.shardedPass && !(win && phase != 0)) throw std::logic_error("sharded pass: not the offset harmonic form");
     const bool harmonic = win ? true : harmonicWeights(K, nterm, ids, mixes, hw);
     // the harmonic block apply runs its near field + corrections (they write `out`)
     // on a side stream beside the M2L (it writes the locals), forked as soon as the
@@ -957,7 +972,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     // a sharded one-collective matvec with the upper multipoles as partial sums
     // (blockOpShardedDev, Plan::xUpPartial): phase 1 forms this rank's records, the
     // exchange's unpack sums them, phase 2 runs no up tier
-    const bool upPartial = oneXActive && upActive && phase != 0;
+    const bool upPartial = call.exch.oneX && call.exch.upPartial && phase != 0;
     // the upper tiers ride in the M2L launch (k_top_m2l_hc) when every leaf is in the
     // bottom tier: the near field then forks after it
     const bool topFused = harmonic && (mask & kStageFar) && topFusedOn() && !upPartial && !win;
@@ -981,7 +996,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
                                         dNearLoc.as<uint16_t>(), &nc, mask);
     // the one-collective exchange (blockOpShardedDev): phase 1 runs the own tier-0
     // tasks only and leaves the near field to phase 2, after the exchange
-    const bool oneX = oneXActive && phase != 0;
+    const bool oneX = call.exch.oneX && phase != 0;
     if (oneX && !(harmonic && nearIn))
         throw std::logic_error("one-collective exchange: the apply is not the harmonic one with its near field from the input");
     double* const fTw = nearIn ? nullptr : dFT.as<double>();
@@ -994,9 +1009,9 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     // one up tier; a sharded apply's bottom tier runs this rank's tasks only (list)
     // and stores its tier-0 roots into send, its next tier reads the gathered ones
     // the partial tasks of the upper multipoles ride as tails of the own tier-0 launch
-    // (blockOpShardedDev decides: upTailActive; they write into the send buffer)
+    // (shardedExchange decides: ExchangeForm::upTails; they write into the send buffer)
     UpTail tail;
-    if (upPartial && upTailActive) {
+    if (upPartial && call.exch.upTails) {
         tail.partOf = dXT0Part.as<int2>();
         const size_t sb = plan.xUpRoots.size() * 16 * kRank * K * sizeof(double);
         if (dXUpStage.bytes < sb) dXUpStage.alloc(sb);
@@ -1141,7 +1156,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         e0 = tm ? mark(s) : -1;
         eStart = e0;
         const bool nearEarlyGroups = nearIn && oneX && !plan.nearGrpEarly.empty() && shardNearEarly && !passShard;
-        const bool earlyAfterPack = nearEarlyGroups && phase == 1 && ntier >= 1 && packHook;
+        const bool earlyAfterPack = nearEarlyGroups && phase == 1 && ntier >= 1 && call.exch.pack;
         auto nearEarlyStage = [&] {
             // one-collective form: the groups that read only the own range start now,
             // beside the own tier-0 tasks (or after the pack); the rest waits for the
@@ -1177,8 +1192,8 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
                        tail.partOf ? &tail : nullptr);
             else upTier(0, dXT0Tasks.as<int>(), (int)plan.xT0Tasks.size(), nullptr, rootsSend);
             if (earlyAfterPack) {  // the pack's partial tasks take their slots before the near groups do
-                packHook(s);
-                packIssued = true;
+                call.exch.pack(s);
+                call.exch.issued = true;
                 nearEarlyStage();
             }
         }
@@ -1208,7 +1223,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         e0 = pend.e0;
         eStart = pend.eStart;
         nearDone = pend.nearDone;
-        pend.active = shardPass;  // a sharded pass repeats its phase 2 per output window (phase 3)
+        pend.active = call.shardedPass;  // a sharded pass repeats its phase 2 per output window (phase 3)
         const int ex = tm ? mark(s) : -1;
         if (phase == 2) span(0, pend.ePack, ex);  // the caller's root exchange
         else eStart = ex;                         // a repeat's total span is its own
@@ -1312,7 +1327,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
                          dPyT.as<double>(), operm, obase, ldo, dDnNearOff.as<int>(), plan.dnMaxNear,
                          // the near partials: a single-RHS symmetric plan, or the harmonic one's
                          (harmonic ? hsSym : plan.nearPartTotal > 0) ? dNearPart.as<double>() : nullptr,
-                         dDnChain.as<int2>(), plan.dnMaxChain, mask, scale, out, subX, subLd,
+                         dDnChain.as<int2>(), plan.dnMaxChain, mask, scale, out, call.minuend, call.minuendLd,
                          s, halo && clustered ? dHmPart.as<double>() : nullptr, dDnChainFold.as<int>());
     if (tr) {
         const int e2 = tm ? mark(s) : -1;
@@ -1325,7 +1340,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
 // The modes of a batched apply: every one needs its correction tables; the per-mode
 // stream (any apply that is not the harmonic one or a pass) needs their operators too.
 // Raised before anything is staged or launched.
-void Operator::checkModes(int K, int nterm, const int* ids, const double* mixes) const {
+void Operator::checkModes(int K, int nterm, const int* ids, const double* mixes, const ApplyCall& call) const {
     bool lean = false;
     for (int t = 0; t < nterm; ++t) {
         if (ids[t] < 0 || ids[t] >= kernelSize) throw std::out_of_range("kernel id out of range");
@@ -1334,18 +1349,14 @@ void Operator::checkModes(int K, int nterm, const int* ids, const double* mixes)
         lean = lean || !modes[ids[t]].resident;
     }
     if (!lean) return;
-    if (passWin && useAtt && attReady && plan.nearPartTotal == 0) return;  // a pass: the mode-shared caches
+    if (call.pass && useAtt && attReady && plan.nearPartTotal == 0) return;  // a pass: the mode-shared caches
     HarmWeights hw;
     bool harmonic = false;
     if (rhs_supported(K)) {
         harmonic = harmonicWeights(K, nterm, ids, mixes, hw);
     } else if (K >= 1 && K <= kMaxRhs) {  // as applyBlock pads it
         const int Kp = rhs_padded(K);
-        std::vector<double> mp((size_t)nterm * Kp * Kp, 0.0);
-        for (int t = 0; t < nterm; ++t)
-            for (int i = 0; i < K; ++i)
-                for (int b = 0; b < K; ++b) mp[((size_t)t * Kp + i) * Kp + b] = mixes[((size_t)t * K + i) * K + b];
-        harmonic = harmonicWeights(Kp, nterm, ids, mp.data(), hw);
+        harmonic = harmonicWeights(Kp, nterm, ids, padMixes(K, Kp, nterm, mixes).data(), hw);
     }
     if (harmonic) return;
     for (int t = 0; t < nterm; ++t) needResident(ids[t], "a block apply down the per-mode operator stream");
@@ -1383,15 +1394,22 @@ void Operator::blockOpDev(int which, const double* x, int64_t ldx, double* out, 
                       sigT ? sigT : dSigmaT.as<double>());
         return;
     }
+    ApplyCall call;
+    call.phased(phase, rootsSend, rootsRecv);
+    blockOp(which, x, ldx, out, ldo, treeIo, s, gval, sigT, call);
+}
+
+void Operator::blockOp(int which, const double* x, int64_t ldx, double* out, int64_t ldo, bool treeIo, hipStream_t s,
+                       double gval, const double* sigT, ApplyCall& call) {
+    const int phase = call.phase;
     const int nb = ks, nm = 2 * ks - 1;
     const auto mix = blockMixes(nb, std::isnan(gval) ? g : gval, which != 0);
     const double* sig = sigT ? sigT : dSigmaT.as<double>();
     pendingCall(phase, PendingCall{1, which, x, out, sig, ldx, ldo, std::isnan(gval) ? g : gval});
-    std::vector<int> ids(nm);
-    for (int m = 0; m < nm; ++m) ids[m] = m;
+    const std::vector<int> ids = modeIds(nm);
     if (which < 2) {
         applyBlock(nb, x, ldx, treeIo, which != 0 ? sig : nullptr, nm, ids.data(), mix.data(), out, ldo, treeIo, s,
-                   kStageAll, phase, rootsSend, rootsRecv);
+                   kStageAll, call);
         return;
     }
     // x - mforward(x) on the owned targets (aniso.m:155)
@@ -1400,21 +1418,14 @@ void Operator::blockOpDev(int which, const double* x, int64_t ldx, double* out, 
     const double* xo = x + (treeIo ? plan.ownBegin : 0);  // x at the output positions
     if (fuseSub && rhs_supported(nb) && !plan.dnDesc.empty()) {
         // the down pass, last writer of every owned point, stores x - (near + corr + far)
-        subX = xo;
-        subLd = ldx;
-        try {
-            applyBlock(nb, x, ldx, treeIo, sig, nm, ids.data(), mix.data(), out, ldo, treeIo, s, kStageAll, phase,
-                       rootsSend, rootsRecv);
-        } catch (...) {
-            subX = nullptr;
-            throw;
-        }
-        subX = nullptr;
+        call.minuend = xo;
+        call.minuendLd = ldx;
+        applyBlock(nb, x, ldx, treeIo, sig, nm, ids.data(), mix.data(), out, ldo, treeIo, s, kStageAll, call);
         return;
     }
     if (phase != 2) dBlk.alloc((size_t)nb * nOut * sizeof(double));
     applyBlock(nb, x, ldx, treeIo, sig, nm, ids.data(), mix.data(), dBlk.as<double>(), nOut, treeIo, s, kStageAll,
-               phase, rootsSend, rootsRecv);
+               call);
     if (phase != 1) launch_sub_slice(nOut, nb, xo, ldx, dBlk.as<double>(), nOut, out, ldo, s);
 }
 
@@ -1474,30 +1485,27 @@ void Operator::blockPass(int I, int J, const std::vector<double>& mix, const dou
     const int64_t N = geo.N;
     if (ldx < N || ldo < N) throw std::invalid_argument("block apply: leading dimension too small");
     std::vector<double> sub;
-    HarmWeights hw;
-    passMix(I, J, mix, sub, hw);
-    std::vector<int> ids(nm);
-    for (int m = 0; m < nm; ++m) ids[m] = m;
-    // the chunk's rows of x; the last chunk zero-padded to 8
+    ApplyCall call;
+    call.pass = true;
+    call.win = HarmWindow{i0, b0};
+    passMix(I, J, mix, sub, call.hw);
+    const std::vector<int> ids = modeIds(nm);
+    const std::pair<double*, int64_t> in = stagePassInput(const_cast<double*>(x), ldx, b0, s);  // (read only)
+    applyBlock(K, in.first, in.second, tree, sig, nm, ids.data(), sub.data(), out8, ldo, tree, s, kStageAll, call);
+}
+
+// The chunk's rows of x (from row b0); the last chunk zero-padded to kMaxRhs rows in dPassIn.
+std::pair<double*, int64_t> Operator::stagePassInput(double* x, int64_t ldx, int b0, hipStream_t s) {
+    constexpr int K = kMaxRhs;
+    const int64_t N = geo.N;
     const int nin = std::min(K, ks - b0);
-    const double* xin = x + (size_t)b0 * ldx;
-    int64_t ldin = ldx;
-    if (nin < K) {
-        dPassIn.alloc((size_t)K * N * sizeof(double));
-        HIP_CHECK(hipMemsetAsync(dPassIn.p, 0, dPassIn.bytes, s));
-        HIP_CHECK(hipMemcpy2DAsync(dPassIn.p, N * sizeof(double), xin, ldx * sizeof(double), N * sizeof(double), nin,
-                                   hipMemcpyDeviceToDevice, s));
-        xin = dPassIn.as<double>();
-        ldin = N;
-    }
-    const HarmWindow win{i0, b0};
-    struct Restore {
-        const HarmWindow*& w;
-        ~Restore() { w = nullptr; }
-    } restore{passWin};
-    passWin = &win;
-    passHw = hw;
-    applyBlock(K, xin, ldin, tree, sig, nm, ids.data(), sub.data(), out8, ldo, tree, s, kStageAll);
+    double* const xin = x + (size_t)b0 * ldx;
+    if (nin == K) return {xin, ldx};
+    dPassIn.alloc((size_t)K * N * sizeof(double));
+    HIP_CHECK(hipMemsetAsync(dPassIn.p, 0, dPassIn.bytes, s));
+    HIP_CHECK(hipMemcpy2DAsync(dPassIn.p, N * sizeof(double), xin, ldx * sizeof(double), N * sizeof(double), nin,
+                               hipMemcpyDeviceToDevice, s));
+    return {dPassIn.as<double>(), N};
 }
 
 void Operator::blockOpPasses(int which, const double* x, int64_t ldx, double* out, int64_t ldo, bool treeIo,
@@ -2263,15 +2271,11 @@ bool Operator::cachesReady() const {
 }
 
 bool Operator::oneExchangeUsable(int which) {
-    if (!oxReady) return false;
-    if (!attReady)  // mode caches differ between ranks would split the decision: refuse before any collective
-        throw std::logic_error("sharded block operator before cache(): every rank caches its modes first");
+    if (!oxReady) return false;  // (the mode caches are ready on every rank: prepareShardedMatvec)
     const int nm = 2 * ks - 1;
     const auto mix = blockMixes(ks, g, which != 0);
-    std::vector<int> ids(nm);
-    for (int m = 0; m < nm; ++m) ids[m] = m;
     HarmWeights hw;
-    return harmonicWeights(ks, nm, ids.data(), mix.data(), hw);
+    return harmonicWeights(ks, nm, modeIds(nm).data(), mix.data(), hw);
 }
 
 void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s) {
@@ -2284,53 +2288,58 @@ void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, i
 // yo + b * ldo (ldo >= owned).  The public call passes y + own_begin at stride ldy; the
 // sharded block solve its compact (ks, owned) vector.
 void Operator::blockOpShardedOwned(int which, double* x, int64_t ldx, double* yo, int64_t ldo, hipStream_t s) {
-    if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
-    if (ldx < geo.N || ldo < plan.ownEnd - plan.ownBegin)
-        throw std::invalid_argument("sharded block operator: leading dimension too small");
-    ensureDevice();
-    if (ks > kMaxRhs) {  // P input chunks, each with one exchange and P output windows
-        blockOpShardedPasses(which, x, ldx, yo, ldo, s);
-        return;
-    }
-    const bool one = oneExchangeUsable(which);
-    shardedExchange(
-        ks, x, ldx, one, s,
-        [&] { blockOpDev(which, x, ldx, yo, ldo, true, s, NAN, nullptr, 1, dXRootsSend.as<double>(), nullptr); },
-        [&] { blockOpDev(which, x, ldx, yo, ldo, true, s, NAN, nullptr, 2, nullptr, dXRootsRecv.as<double>()); });
+    prepareShardedMatvec(which);
+    checkDeviceErrors();
+    const bool one = ks > kMaxRhs ? oxReady : oneExchangeUsable(which);
+    auto phase = [&](ApplyCall& call, int ph) {
+        call.phased(ph, ph == 1 ? dXRootsSend.as<double>() : nullptr, ph == 2 ? dXRootsRecv.as<double>() : nullptr);
+        blockOp(which, x, ldx, yo, ldo, true, s, NAN, nullptr, call);
+    };
+    if (ks > kMaxRhs)  // P input chunks, each with one exchange and P output windows
+        blockOpShardedPasses(which, x, ldx, yo, ldo, one, s);
+    else
+        shardedExchange(
+            ks, x, ldx, one, s, [&](ApplyCall& call) { phase(call, 1); }, [&](ApplyCall& call) { phase(call, 2); });
     if (one) {
         ++oneXApplies;
         if (oxUp) ++upPartialApplies;
     }
 }
 
-// What a sharded x - mforward(x) can refuse, or fail to allocate, on one rank alone --
-// raised here, before the caller's first collective (the sharded block solve): the
-// state checks of the matvec and every work buffer it would size on its way.
-void Operator::prepareShardedMatvec() {
+// What a sharded block matvec (blockOpShardedOwned; `which` as blockOpDev's) can refuse,
+// or fail to allocate, on one rank alone -- raised here, before its first collective (or,
+// for the sharded block solve, before the caller's): the state checks of the matvec and
+// every work buffer it sizes on its way.
+void Operator::prepareShardedMatvec(int which) {
     if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
+    if (which < 0 || which > 2) throw std::invalid_argument("block operator: which must be 0, 1 or 2");
     if (!coeffSet) throw std::runtime_error("block operator before setCoeff");
-    if (!cachesReady())
+    constexpr int K = kMaxRhs;
+    if (ks > K && useAtt && !attReady)
+        throw std::logic_error("sharded block operator before cache(): every rank caches its modes first");
+    if (ks > K && (!useAtt || plan.nearPartTotal != 0))
+        throw std::invalid_argument("sharded block operator: ks = " + std::to_string(ks) + " blocks (more than " +
+                                    std::to_string(kMaxRhs) + ") run as passes over the mode-shared caches with directed "
+                                    "near storage; this handle has " +
+                                    (!useAtt ? "no mode-shared caches (ANISO_HARMONIC=0)" : "symmetric near storage"));
+    if (!cachesReady())  // (a set_coeff since comm_init: the applies would fail in checkModes, between two collectives)
         throw std::logic_error("sharded block operator before cache(): every rank caches its modes first");
     ensureDevice();
     const int64_t N = geo.N, own = plan.ownEnd - plan.ownBegin;
-    constexpr int K = kMaxRhs;
+    const int Kp = ks > K ? K : rootRhs(ks);  // the right-hand sides of one apply
+    if (up_tier_lds(plan.upMaxTask, Kp) > 160 * 1024 ||
+        down_tier_lds(plan.dnMaxTask, plan.dnMaxLeaves, plan.dnMaxNear, plan.dnMaxChain, Kp) > 160 * 1024)
+        throw std::logic_error("up/down pass task exceeds one workgroup's LDS at " + std::to_string(Kp) + " right-hand sides");
     if (ks > K) {
-        if (!useAtt || plan.nearPartTotal != 0)
-            throw std::invalid_argument("sharded block operator: ks = " + std::to_string(ks) + " blocks (more than " +
-                                        std::to_string(kMaxRhs) + ") run as passes over the mode-shared caches with "
-                                        "directed near storage");
         dPassOut.alloc((size_t)K * N * sizeof(double));
         if (ks % K) dPassIn.alloc((size_t)K * N * sizeof(double));
-        dBlk.alloc((size_t)ks * own * sizeof(double));
-        ensureWork(K);
-        return;
-    }
-    const int Kp = rhs_supported(ks) ? ks : rhs_padded(ks);
-    if (Kp != ks) {
+    } else if (Kp != ks) {
         dPadIn.alloc((size_t)Kp * N * sizeof(double));
         dPadOut.alloc((size_t)Kp * N * sizeof(double));
     }
-    if (!(fuseSub && rhs_supported(ks) && !plan.dnDesc.empty())) dBlk.alloc((size_t)ks * own * sizeof(double));
+    // x - mforward(x) where the down pass does not subtract: the operator's value goes to dBlk
+    if (which == 2 && !(ks <= K && fuseSub && rhs_supported(ks) && !plan.dnDesc.empty()))
+        dBlk.alloc((size_t)ks * own * sizeof(double));
     ensureWork(Kp);
 }
 
@@ -2342,187 +2351,143 @@ void Operator::prepareShardedMatvec() {
 // the down pass (phase 2 for I = 0, its repeat -- phase 3 -- after it), into the
 // (8, owned) scratch that k_add_rows sums into the owned slice of rows 8 I ...  A
 // matvec so issues P exchanges, not P^2.  Every rank takes the same route: the form
-// is commInit's all-gathered decision (oxReady), and everything that can fail on one
-// rank alone is checked, and every work buffer sized, before the first collective.
-void Operator::blockOpShardedPasses(int which, double* x, int64_t ldx, double* yo, int64_t ldy, hipStream_t s) {
+// is commInit's all-gathered decision (`one` = oxReady), and everything that can fail on one
+// rank alone was checked, and every work buffer sized, by prepareShardedMatvec.
+void Operator::blockOpShardedPasses(int which, double* x, int64_t ldx, double* yo, int64_t ldy, bool one,
+                                    hipStream_t s) {
     constexpr int K = kMaxRhs;
     const int P = (ks + K - 1) / K, nm = 2 * ks - 1;
     const int64_t N = geo.N, own = plan.ownEnd - plan.ownBegin;
-    if (which < 0 || which > 2) throw std::invalid_argument("block operator: which must be 0, 1 or 2");
-    if (!coeffSet) throw std::runtime_error("block operator before setCoeff");
-    if (useAtt && !attReady)
-        throw std::logic_error("sharded block operator before cache(): every rank caches its modes first");
-    if (!useAtt || plan.nearPartTotal != 0)
-        throw std::invalid_argument("sharded block operator: ks = " + std::to_string(ks) + " blocks (more than " +
-                                    std::to_string(kMaxRhs) + ") run as passes over the mode-shared caches with directed "
-                                    "near storage; this handle has " +
-                                    (!useAtt ? "no mode-shared caches (ANISO_HARMONIC=0)" : "symmetric near storage"));
-    if (!cachesReady())  // (a set_coeff since comm_init: the passes would fail in checkModes, between two collectives)
-        throw std::logic_error("sharded block operator before cache(): every rank caches its modes first");
-    if (up_tier_lds(plan.upMaxTask, K) > 160 * 1024 ||
-        down_tier_lds(plan.dnMaxTask, plan.dnMaxLeaves, plan.dnMaxNear, plan.dnMaxChain, K) > 160 * 1024)
-        throw std::logic_error("up/down pass task exceeds one workgroup's LDS at " + std::to_string(K) + " right-hand sides");
-    checkDeviceErrors();
-    const bool one = oxReady;
     const auto mix = blockMixes(ks, g, which != 0);
     const double* sig = which != 0 ? dSigmaT.as<double>() : nullptr;
-    std::vector<int> ids(nm);
-    for (int m = 0; m < nm; ++m) ids[m] = m;
-    dPassOut.alloc((size_t)K * N * sizeof(double));
-    if (ks % K) dPassIn.alloc((size_t)K * N * sizeof(double));
+    const std::vector<int> ids = modeIds(nm);
     double* acc = yo;
     int64_t lda = ldy;
     if (which == 2) {  // x - mforward(x): the passes sum into dBlk
-        dBlk.alloc((size_t)ks * own * sizeof(double));
         acc = dBlk.as<double>();
         lda = own;
     }
-    ensureWork(K);
-    struct Restore {
-        Operator& o;
-        ~Restore() {
-            o.passWin = nullptr;
-            o.shardPass = false;
-            o.pend.active = false;
-        }
-    } restore{*this};
-    shardPass = true;
-    HarmWindow win{0, 0};
+    struct ClearPending {  // phase 2 of a pass leaves the pending state active for its repeats
+        Pending& p;
+        ~ClearPending() { p.active = false; }
+    } clearPending{pend};
     std::vector<double> sub;
     for (int J = 0; J < P; ++J) {
         const int b0 = J * K, nin = std::min(K, ks - b0);
-        double* xin = x + (size_t)b0 * ldx;
-        int64_t ldin = ldx;
-        if (nin < K) {  // the last chunk zero-padded; the exchange fills the copy's halo
-            HIP_CHECK(hipMemsetAsync(dPassIn.p, 0, dPassIn.bytes, s));
-            HIP_CHECK(hipMemcpy2DAsync(dPassIn.p, N * sizeof(double), xin, ldx * sizeof(double), N * sizeof(double), nin,
-                                       hipMemcpyDeviceToDevice, s));
-            xin = dPassIn.as<double>();
-            ldin = N;
-        }
-        auto pass = [&](int I, int phase) {
-            passMix(I, J, mix, sub, passHw);
-            win = HarmWindow{I * K, b0};
-            passWin = &win;
+        // (the last chunk zero-padded: the exchange fills the copy's halo)
+        const std::pair<double*, int64_t> in = stagePassInput(x, ldx, b0, s);
+        double* const xin = in.first;
+        const int64_t ldin = in.second;
+        auto pass = [&](ApplyCall& call, int I, int phase) {
+            call.phased(phase, phase == 1 ? dXRootsSend.as<double>() : nullptr,
+                        phase == 2 ? dXRootsRecv.as<double>() : nullptr);
+            call.pass = true;
+            call.shardedPass = true;
+            call.win = HarmWindow{I * K, b0};
+            passMix(I, J, mix, sub, call.hw);
             applyBlock(K, xin, ldin, true, sig, nm, ids.data(), sub.data(), dPassOut.as<double>(), own, true, s,
-                       kStageAll, phase, phase == 1 ? dXRootsSend.as<double>() : nullptr,
-                       phase == 2 ? dXRootsRecv.as<double>() : nullptr);
+                       kStageAll, call);
         };
         shardedExchange(
-            K, xin, ldin, one, s, [&] { pass(0, 1); },
-            [&] {
+            K, xin, ldin, one, s, [&](ApplyCall& call) { pass(call, 0, 1); },
+            [&](ApplyCall& call) {
                 if (nin < K)  // the caller's x has its halo filled for every row
                     HIP_CHECK(hipMemcpy2DAsync(x + (size_t)b0 * ldx, ldx * sizeof(double), xin, N * sizeof(double),
                                                N * sizeof(double), nin, hipMemcpyDeviceToDevice, s));
                 for (int I = 0; I < P; ++I) {
-                    pass(I, I == 0 ? 2 : 3);
+                    pass(call, I, I == 0 ? 2 : 3);
                     launch_add_rows(own, std::min(K, ks - I * K), dPassOut.as<double>(), own, acc + (size_t)I * K * lda,
                                     lda, J > 0 ? 1 : 0, s);
                 }
             });
-        pend.active = false;
     }
     if (which == 2) launch_sub_slice(own, ks, x + plan.ownBegin, ldx, dBlk.as<double>(), own, yo, ldy, s);
-    if (one) {
-        ++oneXApplies;
-        if (oxUp) ++upPartialApplies;
-    }
 }
 
 void Operator::shardedExchange(int nb, double* x, int64_t ldx, bool one, hipStream_t s,
-                               const std::function<void()>& phase1, const std::function<void()>& phase2) {
+                               const PhaseFn& phase1, const PhaseFn& phase2) {
     const int64_t rec = (int64_t)plan.xRootChunk * kRank * rootRhs(nb);
+    ApplyCall call;
     if (one) {
         // phase 1 (own tier-0 subtrees), then ONE grouped exchange: the roots to every
         // rank, and from each owner the input positions and multipoles this rank reads;
         // then phase 2 (near field, upper tiers + M2L, down pass)
-        oneXActive = true;
-        upActive = oxUp;
-        upTailActive = oxUp && upTailsOn && !plan.xUpRoots.empty();
-        packIssued = false;
+        ExchangeForm& form = call.exch;
+        form.oneX = true;
+        form.upPartial = oxUp;
+        form.upTails = oxUp && upTailsOn && !plan.xUpRoots.empty();
         if (oxUp && oxRootParts > 63) throw std::logic_error("partial-sum records: more than 63 peer parts");
-        try {
-            const int RK = kRank * rootRhs(nb);
-            // one pack launch (this rank's roots -- or its partial-sum records -- into
-            // every peer's part, the input positions and the multipole rows each peer
-            // reads), one all-to-all-v, one unpack launch (the peers' roots into the slot
-            // layout and the own roots -- or every upper node's records summed -- the
-            // input's halo, the multipoles)
-            // (built when the pack is enqueued: phase 1 may size the work buffers, dMult)
-            OxArgs pk;
-            auto packArgs = [&] {
-                pk.nRoot = oxRootParts;
-                pk.rec = oxUp ? (int64_t)plan.xUpRecNode.size() * RK : rec;
-                pk.rootOff = dOxRootSend.as<int64_t>();
-                pk.roots = oxUp ? dXUpRec.as<double>() : dXRootsSend.as<double>();
-                pk.nPts = oxNsendPts;
-                pk.nb = nb;
-                pk.pos = dOxSendPos.as<int64_t>();
-                pk.base = dOxSendBase.as<int64_t>();
-                pk.stride = dOxSendStride.as<int64_t>();
-                pk.x = x;
-                pk.ldx = ldx;
-                pk.nNode = oxNsendNodes;
-                pk.len = RK;
-                pk.node = dOxSendNode.as<int>();
-                pk.nodeBase = dOxSendNodeBase.as<int64_t>();
-                pk.mult = dMult.as<double>();
-                pk.buf = dOxSendBuf.as<double>();
-            };
-            auto pack = [&](hipStream_t st) {
-                packArgs();
-                if (oxUp) {  // the pack launch forms this rank's records (its first workgroups) unless the
-                             // bottom tier's tails already did
-                    OxArgs pr = pk;
-                    pr.nRoot = 0;
-                    launch_ox_pack_up(rootRhs(nb), upTailActive ? 0 : (int)(plan.xUpTask.size() / Plan::kUpTaskInts),
-                                      dXUpTask.as<int>(), dMult.as<double>(), dParams.as<Params>(),
-                                      dXUpRec.as<double>(), (int)oxRootParts, dOxRootSend.as<int64_t>(), pr, st);
-                } else {
-                    launch_ox(pk, true, st);
-                }
-            };
-            if (nearAfterPack) packHook = pack;
-            phase1();
-            packHook = nullptr;
-            if (!packIssued) pack(s);
-            comm->alltoallv(dOxSendBuf.as<double>(), oxScount.data(), oxSoff.data(), dOxRecvBuf.as<double>(),
-                            oxRcount.data(), oxRoff.data(), s);
-            OxArgs uk = pk;
-            uk.rootOff = dOxRootRecv.as<int64_t>();
-            uk.rootDst = dOxRootDst.as<int64_t>();
-            uk.roots = dXRootsRecv.as<double>();
-            uk.ownRoots = rec > 0 ? dXRootsSend.as<double>() : nullptr;
-            uk.ownDst = (int64_t)plan.rank * rec;
-            uk.nPts = oxNrecvPts;
-            uk.pos = dOxRecvPos.as<int64_t>();
-            uk.base = dOxRecvBase.as<int64_t>();
-            uk.stride = dOxRecvStride.as<int64_t>();
-            uk.nNode = oxNrecvNodes;
-            uk.node = dOxRecvNode.as<int>();
-            uk.nodeBase = dOxRecvNodeBase.as<int64_t>();
-            uk.buf = dOxRecvBuf.as<double>();
-            if (oxUp) {
-                uk.nRoot = 0;
-                uk.ownRoots = nullptr;
-                uk.nSum = oxUpSums;
-                uk.sumNode = dOxUpSumNode.as<int>();
-                uk.sumPtr = dOxUpSumPtr.as<int>();
-                uk.sumSrc = dOxUpSumSrc.as<int64_t>();
-                uk.ownRec = dXUpRec.as<double>();
+        const int RK = kRank * rootRhs(nb);
+        // one pack launch (this rank's roots -- or its partial-sum records -- into
+        // every peer's part, the input positions and the multipole rows each peer
+        // reads), one all-to-all-v, one unpack launch (the peers' roots into the slot
+        // layout and the own roots -- or every upper node's records summed -- the
+        // input's halo, the multipoles)
+        // (built when the pack is enqueued: phase 1 may size the work buffers, dMult)
+        OxArgs pk;
+        auto packArgs = [&] {
+            pk.nRoot = oxRootParts;
+            pk.rec = oxUp ? (int64_t)plan.xUpRecNode.size() * RK : rec;
+            pk.rootOff = dOxRootSend.as<int64_t>();
+            pk.roots = oxUp ? dXUpRec.as<double>() : dXRootsSend.as<double>();
+            pk.nPts = oxNsendPts;
+            pk.nb = nb;
+            pk.pos = dOxSendPos.as<int64_t>();
+            pk.base = dOxSendBase.as<int64_t>();
+            pk.stride = dOxSendStride.as<int64_t>();
+            pk.x = x;
+            pk.ldx = ldx;
+            pk.nNode = oxNsendNodes;
+            pk.len = RK;
+            pk.node = dOxSendNode.as<int>();
+            pk.nodeBase = dOxSendNodeBase.as<int64_t>();
+            pk.mult = dMult.as<double>();
+            pk.buf = dOxSendBuf.as<double>();
+        };
+        auto pack = [&](hipStream_t st) {
+            packArgs();
+            if (oxUp) {  // the pack launch forms this rank's records (its first workgroups) unless the
+                         // bottom tier's tails already did
+                OxArgs pr = pk;
+                pr.nRoot = 0;
+                launch_ox_pack_up(rootRhs(nb), form.upTails ? 0 : (int)(plan.xUpTask.size() / Plan::kUpTaskInts),
+                                  dXUpTask.as<int>(), dMult.as<double>(), dParams.as<Params>(),
+                                  dXUpRec.as<double>(), (int)oxRootParts, dOxRootSend.as<int64_t>(), pr, st);
+            } else {
+                launch_ox(pk, true, st);
             }
-            launch_ox(uk, false, s);
-            phase2();
-        } catch (...) {
-            oneXActive = false;
-            upActive = false;
-            upTailActive = false;
-            packHook = nullptr;
-            throw;
+        };
+        if (nearAfterPack) form.pack = pack;
+        phase1(call);
+        form.pack = nullptr;
+        if (!form.issued) pack(s);
+        comm->alltoallv(dOxSendBuf.as<double>(), oxScount.data(), oxSoff.data(), dOxRecvBuf.as<double>(),
+                        oxRcount.data(), oxRoff.data(), s);
+        OxArgs uk = pk;
+        uk.rootOff = dOxRootRecv.as<int64_t>();
+        uk.rootDst = dOxRootDst.as<int64_t>();
+        uk.roots = dXRootsRecv.as<double>();
+        uk.ownRoots = rec > 0 ? dXRootsSend.as<double>() : nullptr;
+        uk.ownDst = (int64_t)plan.rank * rec;
+        uk.nPts = oxNrecvPts;
+        uk.pos = dOxRecvPos.as<int64_t>();
+        uk.base = dOxRecvBase.as<int64_t>();
+        uk.stride = dOxRecvStride.as<int64_t>();
+        uk.nNode = oxNrecvNodes;
+        uk.node = dOxRecvNode.as<int>();
+        uk.nodeBase = dOxRecvNodeBase.as<int64_t>();
+        uk.buf = dOxRecvBuf.as<double>();
+        if (oxUp) {
+            uk.nRoot = 0;
+            uk.ownRoots = nullptr;
+            uk.nSum = oxUpSums;
+            uk.sumNode = dOxUpSumNode.as<int>();
+            uk.sumPtr = dOxUpSumPtr.as<int>();
+            uk.sumSrc = dOxUpSumSrc.as<int64_t>();
+            uk.ownRec = dXUpRec.as<double>();
         }
-        oneXActive = false;
-        upActive = false;
-        upTailActive = false;
+        launch_ox(uk, false, s);
+        phase2(call);
         return;
     }
     // the input's halo from its owners
@@ -2533,9 +2498,9 @@ void Operator::shardedExchange(int nb, double* x, int64_t ldx, bool one, hipStre
     launch_halo_unpack(hxNrecv, nb, dHxRecvPos.as<int64_t>(), dHxRecvBase.as<int64_t>(), dHxRecvStride.as<int64_t>(),
                        dHxRecvBuf.as<double>(), x, ldx, s);
     // phase 1, the tier-0 root all-gather, phase 2 (the owned slice of y)
-    phase1();
+    phase1(call);
     if (rec > 0) comm->allgather(dXRootsSend.as<double>(), dXRootsRecv.as<double>(), (size_t)rec, s);
-    phase2();
+    phase2(call);
 }
 
 void Operator::checkDeviceErrors() {

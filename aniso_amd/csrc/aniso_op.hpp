@@ -13,6 +13,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "comm.hpp"
@@ -55,6 +56,41 @@ struct CorrFold {
 
 struct StageTimes {
     float exch = 0, up = 0, m2l = 0, gather = 0, near = 0, down = 0, corr = 0, total = 0;
+};
+
+// The exchange form of a one-collective sharded matvec, filled in by
+// shardedExchange for the applies of its two phase callbacks.
+struct ExchangeForm {
+    bool oneX = false;       // the two phases run around the one grouped exchange
+    bool upPartial = false;  // the upper multipoles travel as partial sums (Plan::xUpPartial on every rank)
+    bool upTails = false;    // ... their partial tasks as tails of the bottom tier (ANISO_UP_TAILS=1)
+    // ANISO_NEAR_AFTER_PACK=1: the pack launch, which phase 1 enqueues right after the own
+    // tier-0 launch (and sets `issued`) when the near field's early groups fork after it
+    std::function<void(hipStream_t)> pack;
+    bool issued = false;
+};
+
+// Everything about one applyBlock call that is not the operator's state (default: a
+// whole apply, no pass, no exchange).
+struct ApplyCall {
+    // phase 0: the whole apply (input valid everywhere, every up task); 1 / 2: the
+    // two halves of a sharded apply (forwardTreeBegin / End); 3: phase 2 again for
+    // another output window of a sharded pass (blockOpShardedPasses), on the
+    // multipoles already in dMult: no unpack, no upper tier
+    int phase = 0;
+    double* rootsSend = nullptr;        // phase 1: this rank's tier-0 root records
+    const double* rootsRecv = nullptr;  // phase 2: every rank's
+    void phased(int ph, double* send, const double* recv) { phase = ph; rootsSend = send; rootsRecv = recv; }
+    // x - mforward(x) fused into the down pass (blockOpDev, which = 2): x at the output positions
+    const double* minuend = nullptr;
+    int64_t minuendLd = 0;
+    // one pass of a block operator of more than kMaxRhs blocks, or a lean mapping
+    // (blockPass, leanMapping, blockOpShardedPasses): its window and harmonic weights
+    bool pass = false;
+    HarmWindow win{0, 0};
+    HarmWeights hw{};
+    bool shardedPass = false;  // inside blockOpShardedPasses: phase 2 keeps the pending state for its repeats
+    ExchangeForm exch;
 };
 
 class Operator {
@@ -263,13 +299,13 @@ public:
 private:
     void apply(const double* charge, bool treeIn, const double* sigT, int id, double* out, bool treeOut, hipStream_t s,
                int mask);
-    // phase 0: the whole apply (input valid everywhere, every up task); 1 / 2: the
-    // two halves of a sharded apply (forwardTreeBegin / End); 3: phase 2 again for
-    // another output window of a sharded pass (blockOpShardedPasses), on the
-    // multipoles already in dMult: no unpack, no upper tier
+    // (writes call.exch.issued; everything else of the call is read only)
     void applyBlock(int K, const double* x, int64_t ldx, bool treeIn, const double* sigT, int nterm, const int* ids,
                     const double* mixes, double* out, int64_t ldo, bool treeOut, hipStream_t s, int mask,
-                    int phase = 0, double* rootsSend = nullptr, const double* rootsRecv = nullptr);
+                    ApplyCall& call);
+    // blockOpDev at ks <= kMaxRhs on a call description (a sharded matvec's carries its exchange form)
+    void blockOp(int which, const double* x, int64_t ldx, double* out, int64_t ldo, bool treeIo, hipStream_t s,
+                 double gval, const double* sigT, ApplyCall& call);
     struct Pending {  // state between the two phases of a sharded apply
         bool active = false, nearDone = false;
         int K = 0, e0 = -1, ePack = -1, eStart = -1;
@@ -298,28 +334,29 @@ private:
     // ks > kMaxRhs on a shard: per input chunk one exchange and one up pass, per output
     // chunk under it the window's near field, M2L and down pass
     // (yo: the owned slice of the output, row b at yo + b * ldo)
-    void blockOpShardedPasses(int which, double* x, int64_t ldx, double* yo, int64_t ldo, hipStream_t s);
+    void blockOpShardedPasses(int which, double* x, int64_t ldx, double* yo, int64_t ldo, bool one, hipStream_t s);
     // blockOpShardedDev with the output as its owned slice (ldo >= owned): the sharded
     // block solve's matvec writes its compact vector
     void blockOpShardedOwned(int which, double* x, int64_t ldx, double* yo, int64_t ldo, hipStream_t s);
     // the sharded matvec's rank-local checks and work buffers, ahead of any collective
-    void prepareShardedMatvec();
+    void prepareShardedMatvec(int which = 2);
     // the sharded block solve: the matvec's (ks, N) input and the all-reduce buffer,
     // kept between solves (grown, never shrunk)
     DevBuf dShIn, dShRed;
     // the exchange of one sharded matvec (or of one input chunk of its passes) around
-    // the two phases: nb rows of x, the one- or the two-collective form
-    void shardedExchange(int nb, double* x, int64_t ldx, bool one, hipStream_t s, const std::function<void()>& phase1,
-                         const std::function<void()>& phase2);
-    bool shardPass = false;  // inside blockOpShardedPasses: phase 2 keeps the pending state for its repeats
+    // the two phases: nb rows of x, the one- or the two-collective form.  The phases get
+    // the call description with the exchange form filled in and add their own part.
+    using PhaseFn = std::function<void(ApplyCall&)>;
+    void shardedExchange(int nb, double* x, int64_t ldx, bool one, hipStream_t s, const PhaseFn& phase1,
+                         const PhaseFn& phase2);
     // mapping of a mode whose operators are not resident: one pass of the offset form
     void leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask);
     // the modes of a batched apply are usable by it: tables for the harmonic launches,
     // resident operators for the per-mode stream (checked before anything is launched)
-    void checkModes(int K, int nterm, const int* ids, const double* mixes) const;
-    const HarmWindow* passWin = nullptr;  // set by blockPass for its applyBlock
-    HarmWeights passHw{};
+    void checkModes(int K, int nterm, const int* ids, const double* mixes, const ApplyCall& call) const;
     DevBuf dPassIn, dPassOut;  // a pass's zero-padded input chunk, its 8 output rows
+    // a pass's input chunk, rows b0 .. of x: {pointer, leading dimension}, in place or in dPassIn
+    std::pair<double*, int64_t> stagePassInput(double* x, int64_t ldx, int b0, hipStream_t s);
     void ensureWork(int K);  // work arrays for K right-hand sides
     const ModeArgs* modeTable(int K, int nterm, const int* ids, const double* mixes);
     // harmonic (mode-shared) block apply, DESIGN.md §3.9: the E caches of every
@@ -373,8 +410,7 @@ private:
     // the one-collective exchange (Plan::xOneOk; ANISO_ONE_EXCHANGE=0 keeps the halo
     // all-to-all before phase 1): per peer one buffer part = the tier-0 root records,
     // its input positions (block-major, as the halo exchange), its multipole rows
-    // (16 x K each);
-    // oneXActive marks the two phases of such a matvec for applyBlock
+    // (16 x K each)
     DevBuf dOxSendPos, dOxSendBase, dOxSendStride, dOxRecvPos, dOxRecvBase, dOxRecvStride;
     DevBuf dOxSendNode, dOxSendNodeBase, dOxRecvNode, dOxRecvNodeBase, dOxSendBuf, dOxRecvBuf, dXOwnT0Tasks;
     DevBuf dOxRootSend, dOxRootRecv, dOxRootDst;  // the root records' place in each peer part
@@ -382,21 +418,20 @@ private:
     int64_t oxRootParts = 0;
     std::vector<int64_t> oxScount, oxSoff, oxRcount, oxRoff;
     int64_t oxNsendPts = 0, oxNrecvPts = 0, oxNsendNodes = 0, oxNrecvNodes = 0;
-    bool oxReady = false, oneXActive = false, oneXOn = true;
+    bool oxReady = false, oneXOn = true;
     // the upper multipoles as partial sums (Plan::xUpPartial on every rank): the parts
     // carry every rank's records instead of the roots; the unpack sums each upper
     // node's records (oxUpSumNode / Ptr / Src: >= 0 an offset into the receive buffer,
-    // < 0 ~offset into this rank's own records); upActive marks such a matvec
-    bool oxUp = false, upActive = false;
+    // < 0 ~offset into this rank's own records)
+    bool oxUp = false;
     // the partial tasks as tails of the bottom tier (ANISO_UP_TAILS=1; default: in the
     // pack launch, measured faster on a rank of 8: r06h)
-    bool upTailsOn = false, upTailActive = false;
+    bool upTailsOn = false;
     // the one-collective exchange's pack launch, enqueued by phase 1 right after the own
     // tier-0 launch when the near field's early groups fork after it
-    // (ANISO_NEAR_AFTER_PACK=1): packHook set by blockOpShardedDev, packIssued by phase 1
-    bool nearAfterPack = false, packIssued = false;
+    // (ANISO_NEAR_AFTER_PACK=1; ExchangeForm::pack)
+    bool nearAfterPack = false;
     int sidePrio = 0;  // ANISO_SIDE_PRIO: the side stream's priority (-1 lowest, 0 default, 1 highest)
-    std::function<void(hipStream_t)> packHook;
     DevBuf dXT0Part, dXUpRoots, dXUpCnt, dXUpStage;
     DevBuf dXUpTask, dXUpRec, dOxUpSumNode, dOxUpSumPtr, dOxUpSumSrc;
     int64_t oxUpSums = 0;
@@ -431,10 +466,8 @@ private:
     // the M2L (both HBM-bound, neither saturates alone)
     hipStream_t side = nullptr;
     hipEvent_t evFork = nullptr, evJoin = nullptr;
-    // x - mforward(x) fused into the down pass (blockOpDev sets subX for one apply)
+    // x - mforward(x) fused into the down pass (ApplyCall::minuend)
     bool fuseSub = true;
-    const double* subX = nullptr;
-    int64_t subLd = 0;
     // the near field beside the up pass and the M2L on a side stream: -1 (default) on a
     // shard only -- one GPU runs them serially, 1.190 against 1.202 ms per block matvec
     // (same-process A/B, r05r; 1.148 against 1.162, r04ar): each kernel alone keeps

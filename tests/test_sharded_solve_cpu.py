@@ -2,6 +2,7 @@
 §3.17): the symbol and its place in the public header, the Python wrapper's argument
 checks, and the refusal that needs no device."""
 import ctypes
+import gc
 import os
 import re
 
@@ -61,6 +62,10 @@ def test_sharded_handle_before_set_coeff_is_a_state_error_without_a_device():
     """No communicator, no coefficients: ANISO_ERR_STATE (the error of
     aniso_block_op_sharded_dev there) before any device call -- the dummy pointers are
     never read."""
+    # a handle of an earlier test that is garbage in a reference cycle is destroyed when the
+    # collector next runs, and aniso_destroy, like every call, resets this thread's last
+    # error: collect now, so that none can fall between a call below and its aniso_last_error
+    gc.collect()
     ks = 3
     h = aniso_amd.Aniso(8, 1, ks, 0.8, 10, 4, 20)
     h.set_shard(1, 2)
