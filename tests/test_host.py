@@ -42,7 +42,8 @@ def test_library_contains_gfx950_code_object():
         assert k in blob, k
 
 
-@pytest.mark.parametrize("sz,d,ns", [(1, 1, 8), (3, 2, 8), (16, 3, 8), (13, 3, 10)])
+@pytest.mark.parametrize("sz,d,ns", [(1, 1, 8), (3, 2, 8), (16, 3, 8), (13, 3, 10),
+                                     (5, 4, 8), (4, 5, 8), (6, 6, 8), (3, 6, 10), (1, 6, 8)])
 def test_geometry_matches_oracle_bit_exact(sz, d, ns):
     a = aniso_amd.Aniso(sz, d, 1, 0.5, ns, 4, 20)
     o = Oracle(sz, d, 1, 0.5, ns, 4, 20)
@@ -53,7 +54,8 @@ def test_geometry_matches_oracle_bit_exact(sz, d, ns):
 
 
 @pytest.mark.parametrize("sz,d,ml", [(1, 1, 20), (2, 1, 20), (16, 3, 20), (120, 3, 5), (7, 3, 20), (37, 2, 20),
-                                     (50, 1, 3), (8, 2, 0), (97, 1, 20)])
+                                     (50, 1, 3), (8, 2, 0), (97, 1, 20),
+                                     (9, 4, 20), (7, 5, 20), (6, 6, 20), (3, 6, 1)])
 def test_tree_and_lists_bit_exact_vs_oracle(sz, d, ml):
     a = aniso_amd.Aniso(sz, d, 1, 0.5, 8, 4, ml)
     xy = a.getNodes()
@@ -102,6 +104,10 @@ def test_errors_are_reported_not_swallowed():
         aniso_amd.Aniso(0, 3, 1, 0.5, 8, 4, 20)
     with pytest.raises(aniso_amd.AnisoError):
         aniso_amd.Aniso(4, 30, 1, 0.5, 8, 4, 20)  # quadrature degree not implemented
+    for d in (0, 7):  # the edges of the accepted quadRule range 1..6
+        with pytest.raises(aniso_amd.AnisoError) as e:
+            aniso_amd.Aniso(4, d, 1, 0.5, 8, 4, 20)
+        assert e.value.code == 1, d
     a = aniso_amd.Aniso(4, 1, 2, 0.5, 8, 4, 20)
     with pytest.raises(aniso_amd.AnisoError) as e:
         a.cache(3)  # kernel ids 0..2

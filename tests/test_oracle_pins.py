@@ -73,10 +73,12 @@ def test_oracle_gmres_matches_reference_iteration_count():
     assert fr < c["tol"]
 
 
-def test_oracle_line_integral_is_partition_independent():
+@pytest.mark.parametrize("d", [3, 4, 5, 6])
+def test_oracle_line_integral_is_partition_independent(d):
     """tau is the exact integral of a per-square polynomial: splitting a segment at
-    any interior point must not change it (basis of the GPU DDA walk)."""
-    o = Oracle(9, 3, 1, 0.5, 8, 4, 20)
+    any interior point must not change it (basis of the GPU DDA walk).  The d-point
+    rule is exact for the degree 2d-2 integrand at every accepted d."""
+    o = Oracle(9, d, 1, 0.5, 8, 4, 20)
     xy = o.getNodes()
     rng = np.random.default_rng(3)
     o.setCoeff(*(rng.uniform(0.5, 3.0, (2, o.N))))
