@@ -96,6 +96,7 @@ def lib():
             "aniso_block_solve": [P, dp, dp, I, D, I, dp, I, ip, dp],
             "aniso_block_solve_dev": [P, P, P, I, D, I, dp, I, ip, dp, P],
             "aniso_solve16_mixed_dev": [P, P, I64, P, I64, I, D, D, I, I, ip, ip, dp, P],
+            "aniso_solve_mixed_dev": [P, I, P, I64, P, I64, I, D, D, I, I, ip, ip, ip, dp, P],
             "aniso_apply_block_dev": [P, I, P, I64, I, I, ip, dp, P, I64, I, P],
             "aniso_block_op_dev": [P, I, P, I64, P, I64, I, P],
             "aniso_block_mixes": [I, D, I, dp],
@@ -137,6 +138,10 @@ def lib():
             "aniso_arnoldi_update": [P, I64, I, I, P, I64, P, P, P, P],
             "aniso_arnoldi_column": [P, I, I, P, P, P, P],
             "aniso_arnoldi_solution": [P, I64, I, I, P, I64, P, P, P],
+            "aniso_arnoldi16_work_size": [I, lp, lp],
+            "aniso_arnoldi16_begin": [P, I64, I, P, P, P, P, P, P, P],
+            "aniso_arnoldi16_step": [P, I64, I, I, P, I64, P, P, P, P, P],
+            "aniso_arnoldi16_solution": [P, I64, I, I, P, I64, P, P, P],
             "aniso_mapped_alloc": [ctypes.c_size_t, ctypes.POINTER(P), ctypes.POINTER(P)],
             "aniso_mapped_free": [P],
             "aniso_memcpy": [P, P, ctypes.c_size_t],
@@ -584,6 +589,115 @@ class Aniso:
                                              float(inner_tol), int(max_outer), int(max_cycles), ctypes.byref(outer),
                                              ctypes.byref(inner), _dp(rel), ctypes.c_void_p(s)))
         return outer.value, inner.value, rel
+
+    def solve_mixed_dev(self, B, X, m=80, tol=1e-12, inner_tol=1e-6, max_outer=30, max_cycles=20, stream=None):
+        """The same solve for any number of right-hand sides and a restart up to 400
+        (aniso_solve_mixed_dev; main.cpp:141 runs GMRES(80)): B and X are (nrhs, N) float64
+        CUDA tensors with unit inner stride, solved in groups of 16 rows (a short last
+        group is padded inside the library).  Returns (outer refinements, inner steps,
+        the most steps of any inner cycle, the nrhs final relative residuals)."""
+        import torch
+
+        for t, name in ((B, "B"), (X, "X")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 2
+                    and t.shape[0] >= 1 and t.shape[1] == self.N and t.stride(1) == 1):
+                raise ValueError(f"{name}: (nrhs, N) float64 CUDA tensor with unit inner stride")
+        if B.shape[0] != X.shape[0]:
+            raise ValueError("B and X must have the same number of rows")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        outer, inner, longest = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        rel = np.zeros(B.shape[0])
+        _check(lib().aniso_solve_mixed_dev(self.address, int(B.shape[0]), ctypes.c_void_p(B.data_ptr()),
+                                           int(B.stride(0)), ctypes.c_void_p(X.data_ptr()), int(X.stride(0)), int(m),
+                                           float(tol), float(inner_tol), int(max_outer), int(max_cycles),
+                                           ctypes.byref(outer), ctypes.byref(inner), ctypes.byref(longest), _dp(rel),
+                                           ctypes.c_void_p(s)))
+        return outer.value, inner.value, longest.value, rel
+
+    # ---- the 16-column fp32 Arnoldi of the mixed solves with the caller's operator
+    # (aniso_arnoldi16_*; DESIGN.md §3.14).  Vectors are point-major: n16 = 16 x points.
+    # V: (>= m + 1, n16) float32 CUDA with unit inner stride; r, x: n16 float64; w: n16
+    # float32; scale: 16 float64; state, part: from arnoldi16_work(m); status: 64 float64
+    # (a CUDA tensor or a MappedStatus(64), or None).
+    @staticmethod
+    def arnoldi16_work(m):
+        """(state, part): zeroed float64 CUDA work tensors of aniso_arnoldi16_work_size(m)."""
+        import torch
+
+        ns, npart = ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().aniso_arnoldi16_work_size(int(m), ctypes.byref(ns), ctypes.byref(npart)))
+        return (torch.zeros(ns.value, dtype=torch.float64, device="cuda"),
+                torch.zeros(npart.value, dtype=torch.float64, device="cuda"))
+
+    @staticmethod
+    def _arn16_t(t, n, dtype, name):
+        import torch
+
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+                and t.numel() >= n):
+            raise ValueError(f"{name}: contiguous {dtype} CUDA tensor of >= {n} entries")
+        return ctypes.c_void_p(t.data_ptr())
+
+    @staticmethod
+    def _arn16_v(V, rows, n16):
+        import torch
+
+        if not (isinstance(V, torch.Tensor) and V.is_cuda and V.dtype == torch.float32 and V.dim() == 2
+                and V.stride(1) == 1 and V.shape[0] >= rows and V.shape[1] == n16 and n16 % 16 == 0):
+            raise ValueError(f"V: float32 CUDA (>= {rows}, n16) with unit inner stride")
+        return ctypes.c_void_p(V.data_ptr()), int(V.stride(0))
+
+    @staticmethod
+    def _arn16_work(m, state, part):
+        import torch
+
+        ns, npart = ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().aniso_arnoldi16_work_size(int(m), ctypes.byref(ns), ctypes.byref(npart)))
+        return (Aniso._arn16_t(state, ns.value, torch.float64, "state"),
+                Aniso._arn16_t(part, npart.value, torch.float64, "part"))
+
+    @staticmethod
+    def _arn16_status(status):
+        import torch
+
+        if status is None:
+            return None
+        if isinstance(status, MappedStatus):
+            if status.n < 64:
+                raise ValueError("status: a MappedStatus of >= 64 doubles")
+            return status.dev
+        return Aniso._arn16_t(status, 64, torch.float64, "status")
+
+    def arnoldi16_begin(self, V, m, r, scale, state, part, status=None, stream=None):
+        import torch
+
+        n16 = int(V.shape[1]) if isinstance(V, torch.Tensor) and V.dim() == 2 else -1
+        pv, _ = self._arn16_v(V, int(m) + 1, n16)
+        ps, pp = self._arn16_work(m, state, part)
+        _check(lib().aniso_arnoldi16_begin(self.address, n16, int(m), self._arn16_t(r, n16, torch.float64, "r"),
+                                           self._arn16_t(scale, 16, torch.float64, "scale"), pv, ps, pp,
+                                           self._arn16_status(status), self._arn_s(stream)))
+
+    def arnoldi16_step(self, V, m, j, w, state, part, status=None, stream=None):
+        import torch
+
+        n16 = int(V.shape[1]) if isinstance(V, torch.Tensor) and V.dim() == 2 else -1
+        pv, ld = self._arn16_v(V, int(m) + 1, n16)
+        ps, pp = self._arn16_work(m, state, part)
+        _check(lib().aniso_arnoldi16_step(self.address, n16, int(m), int(j), pv, ld,
+                                          self._arn16_t(w, n16, torch.float32, "w"), ps, pp,
+                                          self._arn16_status(status), self._arn_s(stream)))
+
+    def arnoldi16_solution(self, V, m, used, state, x, stream=None):
+        import torch
+
+        n16 = int(V.shape[1]) if isinstance(V, torch.Tensor) and V.dim() == 2 else -1
+        pv, ld = self._arn16_v(V, int(m) + 1, n16)
+        ns, npart = ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().aniso_arnoldi16_work_size(int(m), ctypes.byref(ns), ctypes.byref(npart)))
+        _check(lib().aniso_arnoldi16_solution(self.address, n16, int(m), int(used), pv, ld,
+                                              self._arn16_t(state, ns.value, torch.float64, "state"),
+                                              self._arn16_t(x, n16, torch.float64, "x"), self._arn_s(stream)))
 
     # ---- the library's own multi-GPU exchange (aniso_comm_*; DESIGN.md §5)
     def comm_init_rccl(self, unique_id):

@@ -38,8 +38,18 @@ void DevBuf::alloc(size_t nbytes) {
         HIP_CHECK(hipFree(p));
         p = nullptr;
     }
+    // a failed allocation leaves an empty buffer (p = null, bytes = 0), never a size without
+    // memory behind it: callers that grow a kept buffer compare `bytes` only
+    bytes = 0;
+    if (nbytes) {
+        const hipError_t e = hipMalloc(&p, nbytes);
+        if (e != hipSuccess) {
+            p = nullptr;
+            (void)hipGetLastError();  // the next launch check must not report this again
+            throw_hip(e, __FILE__, __LINE__);
+        }
+    }
     bytes = nbytes;
-    if (nbytes) HIP_CHECK(hipMalloc(&p, nbytes));
 }
 
 void DevBuf::upload(const void* host, size_t nbytes) {
@@ -125,6 +135,8 @@ Operator::~Operator() {
         if (side) (void)hipStreamDestroy(side);
         if (own) (void)hipStreamDestroy(own);
         if (topErr) (void)hipHostFree(topErr);
+        if (s16Stat) (void)hipHostFree(s16Stat);
+        if (s16Ev) (void)hipEventDestroy(s16Ev);
         if (prev >= 0) (void)hipSetDevice(prev);
     }
 }

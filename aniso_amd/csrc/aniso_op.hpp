@@ -23,6 +23,8 @@
 namespace aniso {
 
 int64_t arn_state_doubles(int m);  // the Arnoldi state block of restart length m (arnoldi.hpp)
+// the 16-column Arnoldi's state blocks and sweep partials at restart m (arnoldi16.hpp), in doubles
+void arn16_work_doubles(int m, int64_t* state, int64_t* part);
 
 struct DevBuf {
     void* p = nullptr;
@@ -178,6 +180,20 @@ public:
                       double* relres, hipStream_t s);
     int solve16Mixed(const double* B, int64_t ldb, double* X, int64_t ldx, int m, double tol, double innerTol,
                      int maxOuter, int maxCycles, int* outer, double* rel, hipStream_t s);
+    // the same for nrhs >= 1 rows in groups of 16 and a restart up to 400 (main.cpp:141's
+    // GMRES(80)); *longest: the most steps of any inner cycle; rel: nrhs entries
+    int solveMixed(int nrhs, const double* B, int64_t ldb, double* X, int64_t ldx, int m, double tol, double innerTol,
+                   int maxOuter, int maxCycles, int* outer, int* longest, double* rel, hipStream_t s);
+    // the 16-column DCGS2 Arnoldi of the mixed solves on a caller's buffers (arnoldi16.hpp;
+    // aniso_arnoldi16_*): vectors point-major, n16 = 16 x points; st / part sized by
+    // arn16_work_doubles(m); status: 64 doubles, per column {estimate, r', steps, -}
+    void arnoldi16Ready();  // the device current and the small kernels' LDS limit raised: once per call
+    void arnoldi16Begin(int64_t n16, int m, const double* r, const float* sub, const double* scale, float* V,
+                        double* st, double* part, double* status, hipStream_t s);
+    void arnoldi16Step(int64_t n16, int m, int j, float* V, int64_t ldv, const float* w, double* st, double* part,
+                       double* status, hipStream_t s);
+    void arnoldi16Solution(int64_t n16, int m, int used, const float* V, int64_t ldv, double* st, double* x,
+                           hipStream_t s);
     int blockSolveHost(const double* rhs, double* x, int restart, double tol, int maxit, double* hist, int maxhist,
                        double* relres);
     // the same solve on a sharded handle with a communicator, every rank together
@@ -376,6 +392,17 @@ private:
     // config 5's library solve (solve16Mixed): its vectors and fp32 basis, kept between
     // solves (grown, never shrunk: a hipFree synchronises the device)
     DevBuf s16B, s16X, s16R, s16W, s16D, s16Df, s16W32, s16V, s16St, s16Part, s16R0;
+    double* s16Stat = nullptr;   // their mapped status block (80 doubles) and its event
+    hipEvent_t s16Ev = nullptr;
+    void mixedCheckState(const char* what, const char* entry) const;
+    void mixedCheckArgs(const char* what, int mMax, int m, double tol, double innerTol, int maxOuter, int maxCycles,
+                        int64_t ldb, int64_t ldx) const;
+    void mixedPrepare(int m);
+    int mixedGroup(const double* B, int64_t ldb, double* X, int64_t ldx, int nrows, int m, double tol,
+                   double innerTol, int maxOuter, int maxCycles, int* outer, int* longest, double* rel, hipStream_t s);
+    int mixedGroupRun(const double* B, int64_t ldb, double* X, int64_t ldx, int nrows, int m, double tol,
+                      double innerTol, int maxOuter, int maxCycles, int* outer, int* longest, double* rel,
+                      hipStream_t s);
     void arnoldiParts(int rows);  // dKryPart for sweeps of `rows` rows
     bool topTraceOn = false;
     int hmRing = 0;  // the cluster M2L's LDS ring depth (ANISO_HM_RING; 0: the one-block-in-flight form)

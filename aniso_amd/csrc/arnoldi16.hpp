@@ -7,7 +7,11 @@
 // accumulate in fp64; the stored direction p_{j+1} is rounded to fp32 and its inner
 // products are taken with the rounded values, so T (Q = P T) describes the stored
 // basis exactly.  The small per-column kernels are arnoldi.hpp's, one block per column
-// (ColArgs).  Partials: part[(row * 16 + c) * kParts + b].
+// (ColArgs).  Partials: part[(row * 16 + c) * kParts + b].  Up to kMaxRows stored rows a
+// sweep holds them in registers (k16_project / k16_update, two reads of the basis per
+// step); past them, up to kMaxBasis, sweep A runs per block of kMaxRows rows and sweep B
+// is k16_update_wide followed by sweep A on the new row (launch_project16 /
+// launch_update16, three reads).
 #pragma once
 
 #include "arnoldi.hpp"
@@ -115,6 +119,69 @@ __global__ void __launch_bounds__(kT) k16_update(int64_t n16, int nv, float* __r
     block_store16<NA>(acc, nv, nv, red, part, blockIdx.x);
 }
 
+// sweep B past kMaxRows stored rows, first part: p = w inv_r - sum_k e_k V_k over all nv
+// rows in ascending k (k16_update's order), rounded once to fp32 into V[nv].  A thread
+// holds kWideRows rows of kWideElems elements in registers at a time, every load of
+// such a group issued before its first use; the coefficients sit in LDS, padded with
+// zeros to a whole group (the rows of the padding re-read row nv - 1, as k16_update's
+// do).  The partials V_k . p and p . p then come from k16_project over rows 0 .. nv with
+// w = the new row: three reads of the basis per step instead of two, and no row count
+// in a register array.  LDS: wide_lds(nv), 51,328 B at nv = kMaxBasis.
+constexpr int kMaxBasis = 400;   // the longest restart of the 16-column solve
+constexpr int kWideRows = 16;    // rows per register group
+constexpr int kWideElems = 2;    // elements per thread and round
+constexpr int kWideBlocks = 4 * kParts;
+inline __host__ __device__ int wide_rows(int nv) { return (nv + kWideRows - 1) / kWideRows * kWideRows; }
+inline size_t wide_lds(int nv) { return (size_t)(wide_rows(nv) + 1) * KC * sizeof(double); }
+
+__global__ void __launch_bounds__(kT) k16_update_wide(int64_t n16, int nv, float* __restrict__ V, int64_t ldv,
+                                                      const float* __restrict__ w, const double* __restrict__ st,
+                                                      int64_t sts, int m) {
+    extern __shared__ double cw[];  // -e_c[0 .. nvp) rows (0 from nv on), then inv_r_c
+    const int nvp = wide_rows(nv);
+    const arn::Layout L(m);
+    for (int f = threadIdx.x; f < (nvp + 1) * KC; f += kT) {
+        const int k = f / KC, c = f % KC;
+        const double* sc = st + c * sts;
+        cw[f] = k < nvp ? (k < nv ? -sc[L.e + k] : 0.0) : sc[L.sc + arn::kInvR];
+    }
+    __syncthreads();
+    const int c = threadIdx.x % KC;
+    const double ir = cw[nvp * KC + c];
+    int64_t j0, j1;
+    arn::block_range(n16, blockIdx.x, j0, j1);
+    float* __restrict__ Vn = V + (size_t)nv * ldv;
+    for (int64_t e0 = j0 + threadIdx.x; e0 < j1; e0 += kWideElems * kT) {
+        int64_t e[kWideElems];  // past the range: the round's first element again, not stored
+        double p[kWideElems];
+#pragma unroll
+        for (int u = 0; u < kWideElems; ++u) {
+            const int64_t eu = e0 + (int64_t)u * kT;
+            e[u] = eu < j1 ? eu : e0;
+        }
+#pragma unroll
+        for (int u = 0; u < kWideElems; ++u) p[u] = (double)w[e[u]] * ir;
+        for (int k0 = 0; k0 < nvp; k0 += kWideRows) {
+            float v[kWideRows][kWideElems];
+#pragma unroll
+            for (int k = 0; k < kWideRows; ++k) {
+                const size_t row = (size_t)(k0 + k < nv ? k0 + k : nv - 1) * ldv;
+#pragma unroll
+                for (int u = 0; u < kWideElems; ++u) v[k][u] = V[row + e[u]];
+            }
+#pragma unroll
+            for (int k = 0; k < kWideRows; ++k) {
+                const double ck = cw[(k0 + k) * KC + c];
+#pragma unroll
+                for (int u = 0; u < kWideElems; ++u) p[u] = __builtin_fma(ck, (double)v[k][u], p[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kWideElems; ++u)
+            if (e0 + (int64_t)u * kT < j1) Vn[e[u]] = (float)p[u];
+    }
+}
+
 // out = a - b (b may be null) per element, fp64 and/or rounded to fp32 (either output
 // may be null), and the partials of |out|^2 per column (of the fp32 value when vf is
 // written: the norm of the stored vector); part[c * kParts + b]
@@ -193,20 +260,23 @@ __global__ void __launch_bounds__(256) k16_round(int64_t n, const double* __rest
     if (e < n) y[e] = (float)x[e];
 }
 
-// rows (16 vectors of N, original order, stride ld) <-> N x 16 point-major tree order
+// rows (nrows <= 16 vectors of N, original order, stride ld) <-> N x 16 point-major tree
+// order; the columns from nrows on are zero (a short last group of right-hand sides)
 __global__ void __launch_bounds__(256) k16_gather(int64_t N, const int* __restrict__ perm, const double* __restrict__ rows,
-                                                  int64_t ld, double* __restrict__ pm) {
+                                                  int64_t ld, int nrows, double* __restrict__ pm) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= N * KC) return;
     const int64_t k = e / KC;
-    pm[e] = rows[(size_t)(e % KC) * ld + perm[k]];
+    const int c = (int)(e % KC);
+    pm[e] = c < nrows ? rows[(size_t)c * ld + perm[k]] : 0.0;
 }
 __global__ void __launch_bounds__(256) k16_scatter(int64_t N, const int* __restrict__ perm, const double* __restrict__ pm,
-                                                   double* __restrict__ rows, int64_t ld) {
+                                                   double* __restrict__ rows, int64_t ld, int nrows) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= N * KC) return;
     const int64_t k = e / KC;
-    rows[(size_t)(e % KC) * ld + perm[k]] = pm[e];
+    const int c = (int)(e % KC);
+    if (c < nrows) rows[(size_t)c * ld + perm[k]] = pm[e];
 }
 
 template <typename F>
@@ -217,6 +287,33 @@ inline void rows_dispatch(int nv, F&& f) {
     else if (nv <= 32) f(std::integral_constant<int, 32>{});
     else if (nv <= 40) f(std::integral_constant<int, 40>{});
     else f(std::integral_constant<int, kMaxRows>{});
+}
+
+// sweep A over nv rows: the row blocks are independent, so past kMaxRows rows k16_project
+// runs once per block of <= kMaxRows rows (w re-read per block)
+inline void launch_project16(int64_t n16, int nv, const float* V, int64_t ldv, const float* w, double* part,
+                             hipStream_t s) {
+    for (int k0 = 0; k0 < nv; k0 += kMaxRows) {
+        const int g = nv - k0 < kMaxRows ? nv - k0 : kMaxRows;
+        const float* Vg = V + (size_t)k0 * ldv;
+        double* pg = part + (size_t)k0 * KC * kParts;
+        rows_dispatch(g, [&](auto c) {
+            k16_project<decltype(c)::value><<<kParts, kT, 0, s>>>(n16, g, Vg, ldv, w, pg);
+        });
+    }
+}
+
+// sweep B of step j (nv = j + 1 stored rows): V[nv] written, part rows 0 .. nv
+inline void launch_update16(int64_t n16, int nv, float* V, int64_t ldv, const float* w, const double* st, int64_t sts,
+                            int m, double* part, hipStream_t s) {
+    if (nv <= kMaxRows) {
+        rows_dispatch(nv, [&](auto c) {
+            k16_update<decltype(c)::value><<<kParts, kT, 0, s>>>(n16, nv, V, ldv, w, st, sts, m, part);
+        });
+        return;
+    }
+    k16_update_wide<<<kWideBlocks, kT, wide_lds(nv), s>>>(n16, nv, V, ldv, w, st, sts, m);
+    launch_project16(n16, nv + 1, V, ldv, V + (size_t)nv * ldv, part, s);
 }
 
 }  // namespace arn16

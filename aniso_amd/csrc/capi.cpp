@@ -446,6 +446,70 @@ int aniso_solve16_mixed_dev(aniso_handle h, const double* b, int64_t ldb, double
     });
 }
 
+int aniso_solve_mixed_dev(aniso_handle h, int nrhs, const double* b, int64_t ldb, double* x, int64_t ldx, int m,
+                          double tol, double inner_tol, int max_outer, int max_cycles, int* outer, int* inner,
+                          int* longest_cycle, double* relres, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(b);
+        CHECK_PTR(x);
+        int o = 0, lc = 0;
+        const int it = get(h).solveMixed(nrhs, b, ldb, x, ldx, m, tol, inner_tol, max_outer, max_cycles, &o, &lc, relres,
+                                         (hipStream_t)stream);
+        if (outer) *outer = o;
+        if (inner) *inner = it;
+        if (longest_cycle) *longest_cycle = lc;
+    });
+}
+
+int aniso_arnoldi16_work_size(int m, int64_t* state_doubles, int64_t* part_doubles) {
+    return guarded([&] {
+        CHECK_PTR(state_doubles);
+        CHECK_PTR(part_doubles);
+        if (m < 1 || m > 400) throw std::invalid_argument("arnoldi16: restart must be in [1, 400]");
+        aniso::arn16_work_doubles(m, state_doubles, part_doubles);
+    });
+}
+
+int aniso_arnoldi16_begin(aniso_handle h, int64_t n16, int m, const double* r, const double* scale, float* V,
+                          double* state, double* part, double* status, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(r);
+        CHECK_PTR(scale);
+        CHECK_PTR(V);
+        CHECK_PTR(state);
+        CHECK_PTR(part);
+        get(h).arnoldi16Ready();
+        get(h).arnoldi16Begin(n16, m, r, nullptr, scale, V, state, part, status, (hipStream_t)stream);
+    });
+}
+
+int aniso_arnoldi16_step(aniso_handle h, int64_t n16, int m, int j, float* V, int64_t ldv, const float* w,
+                         double* state, double* part, double* status, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(V);
+        CHECK_PTR(w);
+        CHECK_PTR(state);
+        CHECK_PTR(part);
+        get(h).arnoldi16Ready();
+        get(h).arnoldi16Step(n16, m, j, V, ldv, w, state, part, status, (hipStream_t)stream);
+    });
+}
+
+int aniso_arnoldi16_solution(aniso_handle h, int64_t n16, int m, int used, const float* V, int64_t ldv,
+                             double* state, double* x, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(V);
+        CHECK_PTR(state);
+        CHECK_PTR(x);
+        get(h).arnoldi16Ready();
+        get(h).arnoldi16Solution(n16, m, used, V, ldv, state, x, (hipStream_t)stream);
+    });
+}
+
 int aniso_set_shard(aniso_handle h, int rank, int nranks) {
     ENTER(h);
     return guarded([&] { get(h).setShard(rank, nranks); });

@@ -972,6 +972,80 @@ int Operator::blockSolveShardedDev(const double* rhs, int64_t ldr, double* x, in
     return conv ? total : -std::max(total, 1);
 }
 
+// ---- the 16-column Arnoldi of arnoldi16.hpp as functions on a caller's buffers: the
+// mixed solves below and the development entries aniso_arnoldi16_* run these.  They
+// only check and launch: the device and the small kernels' LDS limit are made ready
+// once per call by arnoldi16Ready (the entries) or mixedPrepare (the solves), not per step
+void Operator::arnoldi16Ready() {
+    ensureDevice();
+    arn_small_kernel_attrs();
+}
+
+void arn16_work_doubles(int m, int64_t* state, int64_t* part) {
+    *state = (int64_t)arn16::KC * arn::Layout(m).total;
+    *part = (int64_t)arn16::kParts * arn16::KC * (m + 2);
+}
+
+static void check_arnoldi16(int64_t n16, int m, int j, int64_t ldv) {
+    if (m < 1 || m > arn16::kMaxBasis)
+        throw std::invalid_argument("arnoldi16: restart must be in [1, " + std::to_string(arn16::kMaxBasis) + "]");
+    if (j < 0 || j >= m) throw std::invalid_argument("arnoldi16: need 0 <= j < m");
+    if (n16 < 0 || n16 % arn16::KC != 0 || ldv < n16)
+        throw std::invalid_argument("arnoldi16: n16 must be 16 x the points and the row stride at least n16");
+}
+
+static arn::ColArgs cols16(int m) {
+    arn::ColArgs ca = arn16::kCols;
+    ca.sts = arn::Layout(m).total;
+    return ca;
+}
+
+// cycle start: V[0] = fp32(r - sub) (sub: fp32, may be null), its norm per column against
+// scale[c]; status (may be null): per column {|V0_c| / scale_c, |V0_c|, 0, -}
+void Operator::arnoldi16Begin(int64_t n16, int m, const double* r, const float* sub, const double* scale, float* V,
+                              double* st, double* part, double* status, hipStream_t s) {
+    using namespace arn16;
+    check_arnoldi16(n16, m, 0, n16);
+    if (sub) k16_sub_norm<float><<<kParts, kT, 0, s>>>(n16, r, sub, nullptr, V, part);
+    else k16_sub_norm<double><<<kParts, kT, 0, s>>>(n16, r, nullptr, nullptr, V, part);
+    HIP_LAUNCH_CHECK();
+    arn::k_arn_begin<<<KC, arn::kThreads, 0, s>>>(m, st, part, kParts, 1.0, status, cols16(m), scale);
+    HIP_LAUNCH_CHECK();
+}
+
+// step j with w = A V[j] (not row j + 1 of V): row j + 1 written; status per column {estimate, r', j + 1, -}
+void Operator::arnoldi16Step(int64_t n16, int m, int j, float* V, int64_t ldv, const float* w, double* st,
+                             double* part, double* status, hipStream_t s) {
+    using namespace arn16;
+    check_arnoldi16(n16, m, j, ldv);
+    // sweep B writes row j + 1 while it reads w
+    const float* vn = V + (size_t)(j + 1) * ldv;
+    if (w < vn + n16 && vn < w + n16) throw std::invalid_argument("arnoldi16: w overlaps row j + 1 of V");
+    const arn::ColArgs ca = cols16(m);
+    launch_project16(n16, j + 1, V, ldv, w, part, s);
+    HIP_LAUNCH_CHECK();
+    arn::k_arn_coef<<<KC, arn::kThreads, arn::coef_lds(j), s>>>(m, j, st, part, kParts, ca);
+    HIP_LAUNCH_CHECK();
+    launch_update16(n16, j + 1, V, ldv, w, st, ca.sts, m, part, s);
+    HIP_LAUNCH_CHECK();
+    arn::k_arn_column<<<KC, arn::kThreads, arn::column_lds(j), s>>>(m, j, st, part, kParts, status, ca);
+    HIP_LAUNCH_CHECK();
+}
+
+// x += the cycle's correction over its first `used` steps (x: n16 doubles, point-major)
+void Operator::arnoldi16Solution(int64_t n16, int m, int used, const float* V, int64_t ldv, double* st, double* x,
+                                 hipStream_t s) {
+    using namespace arn16;
+    check_arnoldi16(n16, m, 0, ldv);
+    if (used < 0 || used > m) throw std::invalid_argument("arnoldi16: need 0 <= used <= m");
+    if (used == 0 || n16 == 0) return;
+    const int64_t sts = arn::Layout(m).total;
+    arn::k_arn_solve<<<KC, arn::kThreads, arn::solve_lds(used), s>>>(m, used, st, sts);
+    HIP_LAUNCH_CHECK();
+    k16_axpy<<<nblk(n16), 256, (size_t)used * KC * sizeof(double), s>>>(n16, used, V, ldv, st, sts, m, x);
+    HIP_LAUNCH_CHECK();
+}
+
 // Config 5 (main.cpp:121-141 for 16 right-hand sides): A X = B with
 // A(u) = u - K_0(sigma_s .* u), fp64 iterative refinement over fp32 inner GMRES(m)
 // solves -- the algorithm of aniso_amd.solve.gmres_mixed, every step in the library:
@@ -985,25 +1059,81 @@ int Operator::blockSolveShardedDev(const double* rhs, int64_t ldr, double* x, in
 // refinements; rel: the 16 final relative residuals.
 int Operator::solve16Mixed(const double* B, int64_t ldb, double* X, int64_t ldx, int m, double tol, double innerTol,
                            int maxOuter, int maxCycles, int* outerOut, double* rel, hipStream_t s) {
-    using namespace arn16;
-    if (plan.nranks != 1) throw std::logic_error("16-RHS solve on a sharded handle");
-    if (!coeffSet) throw std::runtime_error("16-RHS solve before setCoeff");
-    needResident(0, "aniso_solve16_mixed_dev");
-    if (!modes[0].resident) throw std::runtime_error("16-RHS solve before cache(0)");
-    if (m < 1 || m >= kMaxRows) throw std::invalid_argument("16-RHS solve: restart must be in [1, 47]");
+    mixedCheckState("16-RHS solve", "aniso_solve16_mixed_dev");
+    mixedCheckArgs("16-RHS solve", arn16::kMaxRows - 1, m, tol, innerTol, maxOuter, maxCycles, ldb, ldx);
+    mixedPrepare(m);
+    int longest = 0;
+    return mixedGroup(B, ldb, X, ldx, arn16::KC, m, tol, innerTol, maxOuter, maxCycles, outerOut, &longest, rel, s);
+}
+
+// The same for any number of right-hand sides and any restart up to arn16::kMaxBasis
+// (main.cpp:141 runs GMRES(80)): the rows are solved in groups of 16, in order, on the
+// work buffers of one group; a short last group is padded with zero columns (a zero
+// column's solution is 0 and its relres 0).  *outerOut: the largest refinement count
+// of a group; returns the sum of the groups' inner steps; *longest: the most steps any
+// inner cycle took; rel: nrhs entries (may be null).  Arguments are checked before the
+// handle's state, both before the device is touched.
+int Operator::solveMixed(int nrhs, const double* B, int64_t ldb, double* X, int64_t ldx, int m, double tol,
+                         double innerTol, int maxOuter, int maxCycles, int* outerOut, int* longest, double* rel,
+                         hipStream_t s) {
+    if (nrhs < 1) throw std::invalid_argument("mixed solve: nrhs must be at least 1");
+    mixedCheckArgs("mixed solve", arn16::kMaxBasis, m, tol, innerTol, maxOuter, maxCycles, ldb, ldx);
+    mixedCheckState("mixed solve", "aniso_solve_mixed_dev");
+    mixedPrepare(m);
+    int outer = 0, inner = 0, longestAll = 0;
+    for (int r0 = 0; r0 < nrhs; r0 += arn16::KC) {
+        const int rows = std::min(arn16::KC, nrhs - r0);
+        int o = 0, lc = 0;
+        double rel16[arn16::KC];
+        inner += mixedGroup(B + (size_t)r0 * ldb, ldb, X + (size_t)r0 * ldx, ldx, rows, m, tol, innerTol, maxOuter,
+                            maxCycles, &o, &lc, rel16, s);
+        outer = std::max(outer, o);
+        longestAll = std::max(longestAll, lc);
+        if (rel) std::copy(rel16, rel16 + rows, rel + r0);
+    }
+    if (outerOut) *outerOut = outer;
+    if (longest) *longest = longestAll;
+    return inner;
+}
+
+// what one rank's handle must be for the mixed solves, and their arguments (mMax: the
+// entry's restart bound); neither touches the device
+void Operator::mixedCheckState(const char* what, const char* entry) const {
+    const std::string w(what);
+    if (plan.nranks != 1) throw std::logic_error(w + " on a sharded handle");
+    if (!coeffSet) throw std::runtime_error(w + " before setCoeff");
+    needResident(0, entry);
+    if (!modes[0].resident) throw std::runtime_error(w + " before cache(0)");
+}
+
+void Operator::mixedCheckArgs(const char* what, int mMax, int m, double tol, double innerTol, int maxOuter,
+                              int maxCycles, int64_t ldb, int64_t ldx) const {
+    const std::string w(what);
+    if (m < 1 || m > mMax) throw std::invalid_argument(w + ": restart must be in [1, " + std::to_string(mMax) + "]");
     if (!(tol > 0.0) || !(innerTol > 0.0) || maxOuter < 0 || maxCycles < 1)
-        throw std::invalid_argument("16-RHS solve needs tol, inner_tol > 0, max_outer >= 0, max_cycles >= 1");
-    const int64_t N = geo.N, n16 = KC * N;
-    if (ldb < N || ldx < N) throw std::invalid_argument("16-RHS solve: leading dimension below N");
+        throw std::invalid_argument(w + " needs tol, inner_tol > 0, max_outer >= 0, max_cycles >= 1");
+    if (ldb < geo.N || ldx < geo.N) throw std::invalid_argument(w + ": leading dimension below N");
+}
+
+// the work buffers of one group of 16 columns at restart m, the mapped status block and
+// its event: kept on the handle between solves (grown, never shrunk), allocated before
+// anything is launched
+void Operator::mixedPrepare(int m) {
+    using namespace arn16;
     ensureDevice();
     checkDeviceErrors();
-    const arn::Layout lay(m);
-    const int64_t sts = lay.total;
-    arn::ColArgs ca = kCols;
-    ca.sts = sts;
+    const int64_t n16 = KC * geo.N;
     auto grow = [](DevBuf& b, size_t bytes) {
         if (b.bytes < bytes) b.alloc(bytes);
     };
+    const size_t basis = (size_t)(m + 1) * n16 * sizeof(float);
+    try {
+        grow(s16V, basis);
+    } catch (const std::exception& e) {
+        throw std::runtime_error("mixed solve: the fp32 Krylov basis of (m + 1) x 16 x N = " + std::to_string(m + 1) +
+                                 " x 16 x " + std::to_string(geo.N) + " floats (" + std::to_string(basis) +
+                                 " bytes) could not be allocated: " + e.what());
+    }
     grow(s16B, n16 * sizeof(double));
     grow(s16X, n16 * sizeof(double));
     grow(s16R, n16 * sizeof(double));
@@ -1011,26 +1141,45 @@ int Operator::solve16Mixed(const double* B, int64_t ldb, double* X, int64_t ldx,
     grow(s16D, n16 * sizeof(double));
     grow(s16Df, n16 * sizeof(float));
     grow(s16W32, n16 * sizeof(float));
-    grow(s16V, (size_t)(m + 1) * n16 * sizeof(float));
-    grow(s16St, (size_t)KC * sts * sizeof(double));
-    grow(s16Part, (size_t)kParts * KC * (m + 2) * sizeof(double));
+    int64_t stDoubles = 0, partDoubles = 0;
+    arn16_work_doubles(m, &stDoubles, &partDoubles);
+    grow(s16St, (size_t)stDoubles * sizeof(double));
+    grow(s16Part, (size_t)partDoubles * sizeof(double));
     grow(s16R0, KC * sizeof(double));
+    // status words in mapped host memory: per column {relres, r', steps, -}, then 16 sums
+    if (!s16Stat)
+        HIP_CHECK(hipHostMalloc((void**)&s16Stat, 5 * KC * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    if (!s16Ev) HIP_CHECK(hipEventCreateWithFlags(&s16Ev, hipEventDisableTiming));
     arn_small_kernel_attrs();
+}
+
+// one group: `nrows` <= 16 rows of B and X, the columns from nrows on zero (mixedPrepare
+// before it).  An exception leaves after the stream has drained: no kernel still writes
+// to the handle's buffers when the caller sees the error.
+int Operator::mixedGroup(const double* B, int64_t ldb, double* X, int64_t ldx, int nrows, int m, double tol,
+                         double innerTol, int maxOuter, int maxCycles, int* outerOut, int* longest, double* rel,
+                         hipStream_t s) {
+    try {
+        return mixedGroupRun(B, ldb, X, ldx, nrows, m, tol, innerTol, maxOuter, maxCycles, outerOut, longest, rel, s);
+    } catch (...) {
+        (void)hipStreamSynchronize(s);
+        throw;
+    }
+}
+
+int Operator::mixedGroupRun(const double* B, int64_t ldb, double* X, int64_t ldx, int nrows, int m, double tol,
+                            double innerTol, int maxOuter, int maxCycles, int* outerOut, int* longest, double* rel,
+                            hipStream_t s) {
+    using namespace arn16;
+    const int64_t N = geo.N, n16 = KC * N;
     double *Bt = s16B.as<double>(), *Xt = s16X.as<double>(), *R = s16R.as<double>(), *W = s16W.as<double>();
     double *D = s16D.as<double>(), *st = s16St.as<double>(), *part = s16Part.as<double>(), *r0d = s16R0.as<double>();
     float *Df = s16Df.as<float>(), *W32 = s16W32.as<float>(), *V = s16V.as<float>();
     const int* perm = dPerm.as<int>();
-    // status words in mapped host memory: per column {relres, r', steps, -}, then 16 sums
-    struct HostStat {
-        double* p = nullptr;
-        hipEvent_t ev = nullptr;
-        ~HostStat() {
-            if (p) (void)hipHostFree(p);
-            if (ev) (void)hipEventDestroy(ev);
-        }
-    } hs;
-    HIP_CHECK(hipHostMalloc((void**)&hs.p, 5 * KC * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_CHECK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
+    struct {
+        double* p;
+        hipEvent_t ev;
+    } hs{s16Stat, s16Ev};
     double* stat = nullptr;
     HIP_CHECK(hipHostGetDevicePointer((void**)&stat, hs.p, 0));
     double* sums = stat + 4 * KC;
@@ -1045,14 +1194,14 @@ int Operator::solve16Mixed(const double* B, int64_t ldb, double* X, int64_t ldx,
         wait();
     };
     const unsigned g16 = nblk(n16);
-    k16_gather<<<g16, 256, 0, s>>>(N, perm, B, ldb, Bt);
+    k16_gather<<<g16, 256, 0, s>>>(N, perm, B, ldb, nrows, Bt);
     k16_sub_norm<double><<<kParts, kT, 0, s>>>(n16, Bt, nullptr, R, nullptr, part);  // R = B (X = 0)
     HIP_LAUNCH_CHECK();
     HIP_CHECK(hipMemsetAsync(Xt, 0, n16 * sizeof(double), s));
     colsums();
     double bn[KC], rn[KC], r0[KC];
     for (int c = 0; c < KC; ++c) bn[c] = std::sqrt(hsums[c]);
-    int outer = 0, inner = 0;
+    int outer = 0, inner = 0, longestCycle = 0;
     for (;; ++outer) {
         if (outer > 0) {
             mrhs64Dev(0, true, Xt, W, s);  // W = X - K_0(sigma_s .* X), fp64
@@ -1076,13 +1225,8 @@ int Operator::solve16Mixed(const double* B, int64_t ldb, double* X, int64_t ldx,
             if (its > 0) {
                 k16_round<<<g16, 256, 0, s>>>(n16, D, Df);
                 forwardF32Dev(Df, W32, s);
-                k16_sub_norm<float><<<kParts, kT, 0, s>>>(n16, R, W32, nullptr, V, part);
-            } else {
-                k16_sub_norm<double><<<kParts, kT, 0, s>>>(n16, R, nullptr, nullptr, V, part);
             }
-            HIP_LAUNCH_CHECK();
-            arn::k_arn_begin<<<KC, arn::kThreads, 0, s>>>(m, st, part, kParts, 1.0, stat, ca, r0d);
-            HIP_LAUNCH_CHECK();
+            arnoldi16Begin(n16, m, R, its > 0 ? W32 : nullptr, r0d, V, st, part, stat, s);
             wait();
             bool done = true;
             for (int c = 0; c < KC; ++c) done = done && hs.p[4 * c] <= innerTol;
@@ -1093,18 +1237,7 @@ int Operator::solve16Mixed(const double* B, int64_t ldb, double* X, int64_t ldx,
             for (int j = 0; j < m; ++j) {
                 float* vj = V + (size_t)j * n16;
                 if (!ahead) forwardF32Dev(vj, W32, s);
-                rows_dispatch(j + 1, [&](auto c) {
-                    k16_project<decltype(c)::value><<<kParts, kT, 0, s>>>(n16, j + 1, V, n16, W32, part);
-                });
-                HIP_LAUNCH_CHECK();
-                arn::k_arn_coef<<<KC, arn::kThreads, arn::coef_lds(j), s>>>(m, j, st, part, kParts, ca);
-                HIP_LAUNCH_CHECK();
-                rows_dispatch(j + 1, [&](auto c) {
-                    k16_update<decltype(c)::value><<<kParts, kT, 0, s>>>(n16, j + 1, V, n16, W32, st, sts, m, part);
-                });
-                HIP_LAUNCH_CHECK();
-                arn::k_arn_column<<<KC, arn::kThreads, arn::column_lds(j), s>>>(m, j, st, part, kParts, stat, ca);
-                HIP_LAUNCH_CHECK();
+                arnoldi16Step(n16, m, j, V, n16, W32, st, part, stat, s);
                 HIP_CHECK(hipEventRecord(hs.ev, s));
                 // the next step's matvec before the host reads the estimates (as blockSolveDev)
                 bool near = false;
@@ -1124,20 +1257,19 @@ int Operator::solve16Mixed(const double* B, int64_t ldb, double* X, int64_t ldx,
                 hrel.push_back(worst);
                 if (worst <= innerTol) break;
             }
-            arn::k_arn_solve<<<KC, arn::kThreads, arn::solve_lds(used), s>>>(m, used, st, sts);
-            HIP_LAUNCH_CHECK();
-            k16_axpy<<<g16, 256, (size_t)used * KC * sizeof(double), s>>>(n16, used, V, n16, st, sts, m, D);
-            HIP_LAUNCH_CHECK();
+            longestCycle = std::max(longestCycle, used);
+            arnoldi16Solution(n16, m, used, V, n16, st, D, s);
         }
         k16_add<<<g16, 256, 0, s>>>(n16, D, Xt);
         HIP_LAUNCH_CHECK();
         inner += its;
     }
-    k16_scatter<<<g16, 256, 0, s>>>(N, perm, Xt, X, ldx);
+    k16_scatter<<<g16, 256, 0, s>>>(N, perm, Xt, X, ldx, nrows);
     HIP_LAUNCH_CHECK();
     HIP_CHECK(hipStreamSynchronize(s));
     checkDeviceErrors();
     if (outerOut) *outerOut = outer;
+    if (longest) *longest = longestCycle;
     return inner;
 }
 

@@ -193,6 +193,10 @@ def gmres_mixed(op, B, tol=1e-12, m=40, inner_tol=1e-6, max_outer=30, max_cycles
     Arnoldi of the block solve on an fp32 basis, no torch op and no host round trip
     inside a step).  native=False keeps the torch-orchestrated loop below (the
     reference the library's solve is tested against).
+    With native, fp32_op and fp64_mfma all left at None, any other float64 CUDA B on an
+    unsharded handle with 1 <= m <= 400 (another number of rows, or 16 rows at a restart
+    past 47 such as main.cpp:141's 80) runs in the library too (Aniso.solve_mixed_dev:
+    groups of 16 rows, the last one padded); everything else takes the torch loop.
 
     fp32_op (default: when B has 16 rows): the inner solves run on the fp32 MFMA
     operator (Aniso.forward_f32_dev, fp32 caches) in tree order, point-major; the
@@ -201,12 +205,24 @@ def gmres_mixed(op, B, tol=1e-12, m=40, inner_tol=1e-6, max_outer=30, max_cycles
     MFMA operator (Aniso.forward16_f64_dev) instead of two 8-row VALU batches."""
     import torch
 
+    # the library's general solve (any number of rows, restart up to 400): where the caller
+    # left the routing and both operators to the defaults, for every float64 CUDA B on an
+    # unsharded handle that the 16-row entry below does not take
+    general = (native is None and fp32_op is None and fp64_mfma is None and B.is_cuda and B.dtype == torch.float64
+               and B.dim() == 2 and B.shape[0] >= 1 and 1 <= m <= 400 and hasattr(op, "solve_mixed_dev")
+               and not (B.shape[0] == 16 and m <= 47 and hasattr(op, "solve16_mixed_dev"))
+               and op.n_owned() == op.N)
+    if general:
+        X = torch.zeros_like(B)
+        outer, inner, _, rel = op.solve_mixed_dev(B.contiguous(), X, m=m, tol=tol, inner_tol=inner_tol,
+                                                  max_outer=max_outer, max_cycles=max_cycles)
+        return X, outer, inner, rel
     if fp32_op is None:
         fp32_op = B.shape[0] == 16
     if fp64_mfma is None:
         fp64_mfma = B.shape[0] == 16 and hasattr(op, "forward16_f64_dev")
     if native is None:
-        native = fp32_op and fp64_mfma and hasattr(op, "solve16_mixed_dev") and B.is_cuda
+        native = fp32_op and fp64_mfma and hasattr(op, "solve16_mixed_dev") and B.is_cuda and 1 <= m <= 47
     if native:
         X = torch.zeros_like(B)
         outer, inner, rel = op.solve16_mixed_dev(B.contiguous(), X, m=m, tol=tol, inner_tol=inner_tol,

@@ -116,6 +116,27 @@ int aniso_block_pass_plan(int ks, int *chunk, int *nchunks);
  * (ANISO_ERR_INVALID otherwise). */
 int aniso_block_pass_dev(aniso_handle h, int which, int I, int J, const double *x, int64_t ldx, double *out,
                          int64_t ldo, void *stream);
+/* ---- the 16-column Arnoldi of the mixed solves ---- */
+/* The inner Krylov process of aniso_solve16_mixed_dev / aniso_solve_mixed_dev with the
+ * operator supplied by the caller (the fp32 counterpart of aniso_arnoldi_begin / _step /
+ * _solution): 16 columns in lockstep, vectors point-major (element 16 i + c = point i
+ * of column c), n16 = 16 x points, an fp32 basis V of (m + 1) rows, 1 <= m <= 400.  The
+ * solves call the same functions.  Device pointers, on `stream`.
+ * work_size: the doubles of the state (16 blocks) and of the sweeps' partials at m. */
+int aniso_arnoldi16_work_size(int m, int64_t *state_doubles, int64_t *part_doubles);
+/* cycle start: row 0 of V = r (n16 doubles) rounded to fp32, the state initialised;
+ * scale: 16 doubles > 0 (device), the norms the estimates are relative to; status (64
+ * doubles, may be NULL): per column {|V0_c| / scale_c, |V0_c|, 0, -} */
+int aniso_arnoldi16_begin(aniso_handle h, int64_t n16, int m, const double *r, const double *scale, float *V,
+                          double *state, double *part, double *status, void *stream);
+/* step j (0 <= j < m) with w = A V[j] (n16 floats, not overlapping row j + 1 of V:
+ * ANISO_ERR_INVALID): writes row j + 1 of V (row stride ldv >= n16) and status: per column {residual estimate, r', j + 1, -}.  Up to 48 stored
+ * rows two sweeps over the basis, past them three. */
+int aniso_arnoldi16_step(aniso_handle h, int64_t n16, int m, int j, float *V, int64_t ldv, const float *w,
+                         double *state, double *part, double *status, void *stream);
+/* x (n16 doubles) += the cycle's correction over its first `used` steps */
+int aniso_arnoldi16_solution(aniso_handle h, int64_t n16, int m, int used, const float *V, int64_t ldv,
+                             double *state, double *x, void *stream);
 
 #ifdef __cplusplus
 }
