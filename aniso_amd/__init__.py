@@ -104,6 +104,10 @@ def lib():
             "aniso_block_pass_dev": [P, I, I, I, P, I64, P, I64, P],
             "aniso_block_op": [P, I, dp, dp],
             "aniso_apply_block": [P, dp, dp, D, dp],
+            "aniso_mapping_direct_dev": [P, P, I, lp, I64, P, P],
+            "aniso_mapping_direct": [P, dp, I, lp, I64, dp],
+            "aniso_block_op_direct_dev": [P, I, P, I64, lp, I64, P, I64, P],
+            "aniso_block_op_direct": [P, I, dp, lp, I64, dp],
             "aniso_shard_cuts": [P, I, lp],
             "aniso_forward_f32_dev": [P, P, P, P],
             "aniso_forward16_f64_dev": [P, P, P, P],
@@ -194,6 +198,19 @@ def _dev_vec(t, n, name, at_least=False):
             and (t.numel() >= n if at_least else t.numel() == n)):
         raise AnisoError(1, f"{name} must be a contiguous float64 CUDA tensor of {'>= ' if at_least else ''}{n} entries")
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _targets(targets):
+    """The target list of the direct evaluations as a contiguous int64 host array (the
+    library checks the range)."""
+    t = np.ascontiguousarray(np.asarray(targets).reshape(-1))
+    if t.size and not np.issubdtype(t.dtype, np.integer):
+        raise AnisoError(1, "targets must be integers (original-order point indices)")
+    return np.ascontiguousarray(t, dtype=np.int64)
+
+
+def _lp(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
 
 
 def _krylov_args(V, w, out, nout):
@@ -526,6 +543,81 @@ class Aniso:
         out = np.zeros(self.ks * self.N)
         _check(lib().aniso_block_op(self.address, int(which), _dp(u), _dp(out)))
         return out.reshape(self.ks, self.N)
+
+    # ---- direct evaluation at chosen targets (DESIGN.md "Accuracy of the method")
+    def mapping_direct(self, charge, id_, targets):
+        """Exact (direct-sum) entries of mapping(charge, id_) at the original-order point
+        indices `targets` (any order, repeats allowed): what a handle built with
+        maxLevel = 0 returns there.  len(targets) x N line integrals; returns (nt,)."""
+        c = _f64(charge, self.N, "charge")
+        t = _targets(targets)
+        out = np.zeros(t.size)
+        _check(lib().aniso_mapping_direct(self.address, _dp(c), int(id_), _lp(t), t.size, _dp(out)))
+        return out
+
+    def mapping_direct_dev(self, charge, id_, targets, out, stream=None):
+        """The same on device tensors: charge (N,), out (nt,); targets stays a host list."""
+        import torch
+
+        t = _targets(targets)
+        _dev_vec(charge, self.N, "charge")
+        po = _dev_vec(out, t.size, "out") if t.size else None
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _check(lib().aniso_mapping_direct_dev(self.address, ctypes.c_void_p(charge.data_ptr()), int(id_), _lp(t),
+                                              t.size, po, ctypes.c_void_p(s)))
+        return out
+
+    def block_op_direct(self, which, u, targets):
+        """Exact entries of block_op(which, u) at `targets`: returns (ks, nt).  One line
+        integral per (target, source) pair serves every mode."""
+        u = _f64(u, self.ks * self.N, "u")
+        t = _targets(targets)
+        out = np.zeros(self.ks * t.size)
+        _check(lib().aniso_block_op_direct(self.address, int(which), _dp(u), _lp(t), t.size, _dp(out)))
+        return out.reshape(self.ks, t.size)
+
+    def block_op_direct_dev(self, which, x, targets, out, stream=None):
+        """The same on device tensors: x (ks, N), out (ks, >= nt) with unit column stride;
+        only the first nt entries of every row of out are written."""
+        import torch
+
+        t = _targets(targets)
+        _dev_rows(x, self.ks, self.N, "x")
+        _dev_rows(out, self.ks, t.size, "out")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _check(lib().aniso_block_op_direct_dev(self.address, int(which), ctypes.c_void_p(x.data_ptr()),
+                                               int(x.stride(0)), _lp(t), t.size, ctypes.c_void_p(out.data_ptr()),
+                                               int(out.stride(0)) if self.ks > 1 else int(out.shape[1]),
+                                               ctypes.c_void_p(s)))
+        return out
+
+    def draw_targets(self, ntargets, seed=0):
+        """`ntargets` distinct point indices drawn with `seed`, ascending (None, or N and
+        more: every point): the targets of fmm_error / block_fmm_error."""
+        n = self.N if ntargets is None else min(int(ntargets), self.N)
+        if n == self.N:
+            return np.arange(self.N, dtype=np.int64)
+        return np.sort(np.random.default_rng(seed).choice(self.N, size=n, replace=False)).astype(np.int64)
+
+    def fmm_error(self, charge, id_, ntargets=256, seed=0):
+        """The FMM error of mapping(charge, id_) on this handle's tree, measured against
+        the direct sum at `ntargets` distinct targets drawn with `seed` (None, or N and
+        more: every point).  Returns (rel_l2, rel_max, targets): the l2 and the largest
+        difference over the targets, relative to the direct values' l2 norm and largest
+        magnitude."""
+        t = self.draw_targets(ntargets, seed)
+        ref = self.mapping_direct(charge, id_, t)
+        got = self.mapping(charge, id_)[t]
+        return (float(np.linalg.norm(got - ref) / np.linalg.norm(ref)),
+                float(np.abs(got - ref).max() / np.abs(ref).max()), t)
+
+    def block_fmm_error(self, which, u, ntargets=256, seed=0):
+        """fmm_error for the block operator block_op(which, u), over all ks rows."""
+        t = self.draw_targets(ntargets, seed)
+        ref = self.block_op_direct(which, u, t)
+        got = self.block_op(which, u)[:, t]
+        return (float(np.linalg.norm(got - ref) / np.linalg.norm(ref)),
+                float(np.abs(got - ref).max() / np.abs(ref).max()), t)
 
     def apply_block(self, u, sigma_s, g):
         """A(u) = u - mforward(u) with explicit sigma_s and g."""

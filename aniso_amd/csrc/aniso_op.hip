@@ -115,6 +115,7 @@ Operator::Operator(int sz, int d, int ks_, double g_, int ns_, int np_, int maxL
     if (const char* e = std::getenv("ANISO_HM_WPE")) hmWpe = std::atoi(e);
     if (const char* e = std::getenv("ANISO_NEAR_WPE")) nearWpe = std::atoi(e);
     if (const char* e = std::getenv("ANISO_TOP_FUSED")) topFusedMode = std::atoi(e) != 0 ? 1 : 0;
+    if (const char* e = std::getenv("ANISO_DIRECT_TARGETS")) directChunk = std::min(std::max(std::atoi(e), 1), 65535);
     sigma_s.assign(geo.N, 0.0);
     sigma_t.assign(geo.N, 0.0);
     modes.resize(kernelSize);
@@ -132,6 +133,7 @@ Operator::~Operator() {
         for (auto& e : evPool) (void)hipEventDestroy(e);
         if (evFork) (void)hipEventDestroy(evFork);
         if (evJoin) (void)hipEventDestroy(evJoin);
+        if (evDirect) (void)hipEventDestroy(evDirect);
         if (side) (void)hipStreamDestroy(side);
         if (own) (void)hipStreamDestroy(own);
         if (topErr) (void)hipHostFree(topErr);
@@ -188,6 +190,7 @@ void Operator::ensureDevice() {
     }
     HIP_CHECK(hipEventCreateWithFlags(&evFork, hipEventDisableTiming));
     HIP_CHECK(hipEventCreateWithFlags(&evJoin, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&evDirect, hipEventDisableTiming));
     HIP_CHECK(hipHostMalloc((void**)&topErr, sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
     *(volatile unsigned*)topErr = 0;
     // tree-order coordinates
@@ -1591,6 +1594,211 @@ void Operator::blockOpHost(int which, const double* u, const double* sigmaS, dou
         HIP_CHECK(hipMemcpyAsync(out, dHostOut.p, bytes, hipMemcpyDeviceToHost, own));
         HIP_CHECK(hipStreamSynchronize(own));
     }
+    checkDeviceErrors();
+}
+
+// ---- direct evaluation at chosen targets (direct.hip) ----
+//
+// The direct sum over all N sources gives the near field a one-leaf tree would compute;
+// the stencil and singular corrections do not depend on the tree, so they come from the
+// apply's own correction kernel (launch_corr on the charges launch_prepare forms, at all
+// N points) and are read out at the targets by the direct kernel's reduction.
+
+bool Operator::directCheck(const char* what, bool block, int id, int which, const void* in, const char* inName,
+                           int64_t ldx, const int64_t* targets, int64_t nt, const void* out, int64_t ldo) const {
+    const std::string w(what);
+    if (plan.nranks > 1)
+        throw std::logic_error(w + " on a sharded handle: a direct sum needs every source (use an unsharded handle)");
+    if (block) {
+        if (which < 0 || which > 2) throw std::invalid_argument(w + ": which must be 0, 1 or 2");
+    } else if (id < 0 || id >= kernelSize) {
+        throw std::out_of_range(w + ": kernel id " + std::to_string(id) + " out of range [0, " + std::to_string(kernelSize) + ")");
+    }
+    if (nt < 0) throw std::invalid_argument(w + ": nt must be >= 0, got " + std::to_string(nt));
+    if (block && ldo < nt)
+        throw std::invalid_argument(w + ": ldo = " + std::to_string(ldo) + " is below nt = " + std::to_string(nt));
+    if (block && nt > 0 && ldx < geo.N)
+        throw std::invalid_argument(w + ": ldx = " + std::to_string(ldx) + " is below N = " + std::to_string(geo.N));
+    if (nt == 0) return false;
+    if (!in) throw std::invalid_argument(w + ": " + inName + " is NULL");
+    if (!targets) throw std::invalid_argument(w + ": targets is NULL");
+    if (!out) throw std::invalid_argument(w + ": out is NULL");
+    for (int64_t t = 0; t < nt; ++t)
+        if (targets[t] < 0 || targets[t] >= geo.N)
+            throw std::invalid_argument(w + ": targets[" + std::to_string(t) + "] = " + std::to_string(targets[t]) +
+                                        " is outside [0, N = " + std::to_string(geo.N) + ")");
+    if (!coeffSet) throw std::runtime_error(w + " before setCoeff");
+    for (int m = block ? 0 : id; m < (block ? kernelSize : id + 1); ++m)
+        if (!modes[m].tables)
+            throw std::runtime_error(w + " on kernel id " + std::to_string(m) + " before cache(" + std::to_string(m) +
+                                     ") or aniso_cache_block");
+    return true;
+}
+
+// The call's device state: the targets, the weights (hw then dw) and room for one
+// launch's partials.  The buffers are the handle's, so the previous direct call's
+// launches (on whatever stream) are waited for first.
+void Operator::directBegin(const int64_t* targets, int64_t nt, const std::vector<double>& weights, int KO) {
+    HIP_CHECK(hipEventSynchronize(evDirect));
+    if (dDirTg.bytes < (size_t)nt * sizeof(int64_t)) dDirTg.alloc((size_t)nt * sizeof(int64_t));
+    HIP_CHECK(hipMemcpy(dDirTg.p, targets, (size_t)nt * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (dDirW.bytes < weights.size() * sizeof(double)) dDirW.alloc(weights.size() * sizeof(double));
+    HIP_CHECK(hipMemcpy(dDirW.p, weights.data(), weights.size() * sizeof(double), hipMemcpyHostToDevice));
+    const size_t pb = (size_t)std::min<int64_t>(nt, directChunk) * direct_blocks(geo.N) * KO * sizeof(double);
+    if (dDirPart.bytes < pb) dDirPart.alloc(pb);
+}
+
+// corr (K rows of N, original order) += the stencil and singular corrections of the K
+// input rows under the terms' mixes: the apply's charges and its correction kernel.
+void Operator::directCorr(int K, const double* x, int64_t ldx, const double* sig, int nterm, const int* ids,
+                          const double* mixes, double* corr, hipStream_t s) {
+    const int64_t N = geo.N;
+    const size_t cb = (size_t)N * rhs_stride(K) * sizeof(double);
+    if (dDirF.bytes < cb) {
+        dDirF.alloc(cb);
+        dDirC.alloc(cb);
+    }
+    const CorrFold& cf = corrTable(K, nterm, ids, mixes);
+    launch_prepare(K, N, x, ldx, 0, dPerm.as<int>(), sig, dWT.as<double>(), dDirF.as<double>(), dDirC.as<double>(), s);
+    launch_corr(K, geo.d, 0, N, dPerm.as<int>(), dIperm.as<int>(), dDirC.as<double>(), dDirF.as<double>(),
+                cf.Wc.as<double>(), cf.Wm.as<double>(), dParams.as<Params>(), kStageStencil | kStageSing,
+                M_1_PI / 2.0, false, N, corr, s);
+}
+
+// One window's rows for every target, a bounded number of targets per launch.
+void Operator::directSweep(int KO, DirectArgs a, int64_t nt, hipStream_t s) {
+    a.N = geo.N;
+    a.perm = dPerm.as<int>();
+    a.iperm = dIperm.as<int>();
+    a.wT = dWT.as<double>();
+    a.pxT = dPxT.as<double>();
+    a.pyT = dPyT.as<double>();
+    a.stcoef = dStCoef.as<double>();
+    a.P = dParams.as<Params>();
+    a.tg = dDirTg.as<int64_t>();
+    a.part = dDirPart.as<double>();
+    a.scale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
+    a.corr = dDirCorr.as<double>();
+    a.ldc = geo.N;
+    for (int64_t t0 = 0; t0 < nt; t0 += directChunk) {
+        a.t0 = t0;
+        launch_direct(KO, (int)std::min<int64_t>(directChunk, nt - t0), a, s);
+    }
+}
+
+void Operator::mappingDirectDev(const double* charge, int id, const int64_t* targets, int64_t nt, double* out,
+                                hipStream_t s) {
+    if (!directCheck("aniso_mapping_direct", false, id, 0, charge, "charge", geo.N, targets, nt, out, nt)) return;
+    ensureDevice();
+    checkDeviceErrors();
+    const int64_t N = geo.N;
+    directBegin(targets, nt, {1.0, id == 0 ? 1.0 : 0.0}, 1);
+    if (dDirCorr.bytes < (size_t)N * sizeof(double)) dDirCorr.alloc((size_t)N * sizeof(double));
+    HIP_CHECK(hipMemsetAsync(dDirCorr.p, 0, (size_t)N * sizeof(double), s));
+    const double one = 1.0;
+    directCorr(1, charge, N, nullptr, 1, &id, &one, dDirCorr.as<double>(), s);
+    DirectArgs a;
+    a.nb = 1;
+    a.m0 = id;
+    a.nout = 1;
+    a.x = charge;
+    a.ldx = N;
+    a.hw = dDirW.as<double>();
+    a.dw = dDirW.as<double>() + 1;
+    a.out = out;
+    a.ldo = nt;
+    directSweep(1, a, nt, s);
+    HIP_CHECK(hipEventRecord(evDirect, s));
+}
+
+void Operator::mappingDirectHost(const double* charge, int id, const int64_t* targets, int64_t nt, double* out) {
+    if (!directCheck("aniso_mapping_direct", false, id, 0, charge, "charge", geo.N, targets, nt, out, nt)) return;
+    ensureDevice();
+    HIP_CHECK(hipMemcpyAsync(dCharge.p, charge, geo.N * sizeof(double), hipMemcpyHostToDevice, own));
+    HIP_CHECK(hipEventSynchronize(evDirect));  // dDirOut may still be written
+    if (dDirOut.bytes < (size_t)nt * sizeof(double)) dDirOut.alloc((size_t)nt * sizeof(double));
+    mappingDirectDev(dCharge.as<double>(), id, targets, nt, dDirOut.as<double>(), own);
+    HIP_CHECK(hipMemcpyAsync(out, dDirOut.p, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, own));
+    HIP_CHECK(hipStreamSynchronize(own));
+    checkDeviceErrors();
+}
+
+void Operator::blockOpDirectDev(int which, const double* x, int64_t ldx, const int64_t* targets, int64_t nt,
+                                double* out, int64_t ldo, hipStream_t s) {
+    if (!directCheck("aniso_block_op_direct", true, 0, which, x, "x", ldx, targets, nt, out, ldo)) return;
+    ensureDevice();
+    checkDeviceErrors();
+    constexpr int K = kMaxRhs;
+    const int64_t N = geo.N;
+    const int nm = 2 * ks - 1, P = (ks + K - 1) / K;
+    const auto mix = blockMixes(ks, g, which != 0);
+    const double* sig = which != 0 ? dSigmaT.as<double>() : nullptr;
+    // the harmonic weights from the mixes, as passMix reads them: row 0 holds hw_b at
+    // mode b, the mode-0 weight of output row i is its diagonal weight
+    std::vector<double> wts(2 * (size_t)ks);
+    for (int b = 0; b < ks; ++b) {
+        wts[b] = mix[((size_t)b * ks + 0) * ks + b];
+        wts[ks + b] = mix[((size_t)0 * ks + b) * ks + b];
+    }
+    const int KO = direct_rows(std::min(ks, 32));
+    directBegin(targets, nt, wts, KO);
+    // the corrections, chunk by chunk of 8 rows (any ks): input chunk J into output chunk I
+    const size_t cb = (size_t)P * K * N * sizeof(double);
+    if (dDirCorr.bytes < cb) dDirCorr.alloc(cb);
+    HIP_CHECK(hipMemsetAsync(dDirCorr.p, 0, cb, s));
+    const std::vector<int> ids = modeIds(nm);
+    std::vector<double> sub;
+    HarmWeights unused;
+    for (int J = 0; J < P; ++J) {
+        const int nin = std::min(K, ks - J * K);
+        const double* xin = x + (size_t)J * K * ldx;
+        int64_t ldi = ldx;
+        if (nin < K) {  // the last chunk zero-padded to 8 rows
+            if (dDirIn.bytes < (size_t)K * N * sizeof(double)) dDirIn.alloc((size_t)K * N * sizeof(double));
+            HIP_CHECK(hipMemsetAsync(dDirIn.p, 0, (size_t)K * N * sizeof(double), s));
+            HIP_CHECK(hipMemcpy2DAsync(dDirIn.p, N * sizeof(double), xin, ldx * sizeof(double), N * sizeof(double), nin,
+                                       hipMemcpyDeviceToDevice, s));
+            xin = dDirIn.as<double>();
+            ldi = N;
+        }
+        for (int I = 0; I < P; ++I) {
+            passMix(I, J, mix, sub, unused);
+            if (std::all_of(sub.begin(), sub.end(), [](double v) { return v == 0.0; })) continue;
+            directCorr(K, xin, ldi, sig, nm, ids.data(), sub.data(), dDirCorr.as<double>() + (size_t)I * K * N, s);
+        }
+    }
+    // the direct sums: every output row from ONE line integral per pair (windows of up to
+    // 32 rows: more than 32 blocks repeat the walk per window)
+    for (int i0 = 0; i0 < ks; i0 += KO) {
+        DirectArgs a;
+        a.nb = ks;
+        a.m0 = a.drow0 = a.orow0 = a.crow0 = i0;
+        a.nout = std::min(KO, ks - i0);
+        a.x = x;
+        a.ldx = ldx;
+        a.sigT = sig;
+        a.hw = dDirW.as<double>();
+        a.dw = dDirW.as<double>() + ks + i0;
+        a.minuend = which == 2 ? x : nullptr;  // x - mforward(x) (aniso.m:155)
+        a.ldm = ldx;
+        a.out = out;
+        a.ldo = ldo;
+        directSweep(KO, a, nt, s);
+    }
+    HIP_CHECK(hipEventRecord(evDirect, s));
+}
+
+void Operator::blockOpDirectHost(int which, const double* u, const int64_t* targets, int64_t nt, double* out) {
+    if (!directCheck("aniso_block_op_direct", true, 0, which, u, "u", geo.N, targets, nt, out, nt)) return;
+    ensureDevice();
+    const int64_t N = geo.N;
+    dHostIn.alloc((size_t)ks * N * sizeof(double));
+    HIP_CHECK(hipMemcpyAsync(dHostIn.p, u, (size_t)ks * N * sizeof(double), hipMemcpyHostToDevice, own));
+    HIP_CHECK(hipEventSynchronize(evDirect));  // dDirOut may still be written
+    if (dDirOut.bytes < (size_t)ks * nt * sizeof(double)) dDirOut.alloc((size_t)ks * nt * sizeof(double));
+    blockOpDirectDev(which, dHostIn.as<double>(), N, targets, nt, dDirOut.as<double>(), nt, own);
+    HIP_CHECK(hipMemcpyAsync(out, dDirOut.p, (size_t)ks * nt * sizeof(double), hipMemcpyDeviceToHost, own));
+    HIP_CHECK(hipStreamSynchronize(own));
     checkDeviceErrors();
 }
 

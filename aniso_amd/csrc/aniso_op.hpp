@@ -148,6 +148,20 @@ public:
     // N points each (block b at b * N, original order); sigmaS (N, or nullptr: the
     // handle's sigma_s) and gval (NaN: the handle's g) as aniso.m's mforward reads them
     void blockOpHost(int which, const double* u, const double* sigmaS, double gval, double* out);
+    // --- direct evaluation at chosen targets (direct.hip; DESIGN.md "Accuracy of the
+    // method"): what mapping / the block operator return on a one-leaf tree (maxLevel = 0),
+    // at the nt points `targets` (host array of original indices, any order, repeats
+    // allowed), from all N sources -- nt x N line integrals, no tree and no cache.  The
+    // stencil and singular corrections come from the apply's own correction kernel, read
+    // out at the targets.  out: nt entries per row (block form: ks rows at stride ldo).
+    // Unsharded handles; every argument and the state are checked before the device is
+    // touched, and nt = 0 returns at once.
+    void mappingDirectDev(const double* charge, int id, const int64_t* targets, int64_t nt, double* out,
+                          hipStream_t s);
+    void mappingDirectHost(const double* charge, int id, const int64_t* targets, int64_t nt, double* out);
+    void blockOpDirectDev(int which, const double* x, int64_t ldx, const int64_t* targets, int64_t nt, double* out,
+                          int64_t ldo, hipStream_t s);
+    void blockOpDirectHost(int which, const double* u, const int64_t* targets, int64_t nt, double* out);
     // the (2 nb - 1) mode mixes of forward (chi = false) or mforward (chi = true)
     static std::vector<double> blockMixes(int nb, double g, bool chi);
     // More than kMaxRhs blocks: the block operator runs as
@@ -371,6 +385,24 @@ private:
     // resident operators for the per-mode stream (checked before anything is launched)
     void checkModes(int K, int nterm, const int* ids, const double* mixes, const ApplyCall& call) const;
     DevBuf dPassIn, dPassOut;  // a pass's zero-padded input chunk, its 8 output rows
+    // direct evaluation: the checks shared by its entries (false: nt = 0, nothing to do),
+    // the per-call device state (targets, weights, partials; the previous call's launches
+    // are waited for before it is overwritten), the corrections of an input at all N points
+    bool directCheck(const char* what, bool block, int id, int which, const void* in, const char* inName,
+                     int64_t ldx, const int64_t* targets, int64_t nt, const void* out, int64_t ldo) const;
+    void directBegin(const int64_t* targets, int64_t nt, const std::vector<double>& weights, int KO);
+    void directCorr(int K, const double* x, int64_t ldx, const double* sig, int nterm, const int* ids,
+                    const double* mixes, double* corr, hipStream_t s);
+    void directSweep(int KO, DirectArgs a, int64_t nt, hipStream_t s);
+    DevBuf dDirTg, dDirW, dDirPart, dDirCorr, dDirF, dDirC, dDirIn, dDirOut;
+    hipEvent_t evDirect = nullptr;
+    // Targets per launch.  One launch is targets x ceil(N / 1024) workgroups, each walking
+    // 1,024 line integrals.  Measured at 1M points (sz = 1024, d = 1), 256 targets per call,
+    // mode form: 4 per launch 1.00 s, 16 0.93 s, 32 0.916 s, 64 0.911 s, all 256 in one
+    // launch 0.873 s.  32 keeps a launch at 0.11 s for 5 % over the single launch of 0.87 s
+    // (DESIGN.md "Accuracy of the method").  ANISO_DIRECT_TARGETS, read when the handle is
+    // created, overrides it (tests: a small value exercises the chunking at small N).
+    int directChunk = 32;
     // a pass's input chunk, rows b0 .. of x: {pointer, leading dimension}, in place or in dPassIn
     std::pair<double*, int64_t> stagePassInput(double* x, int64_t ldx, int b0, hipStream_t s);
     void ensureWork(int K);  // work arrays for K right-hand sides

@@ -375,6 +375,30 @@ int aniso_block_op(aniso_handle h, int which, const double* u, double* out) {
     });
 }
 
+int aniso_mapping_direct_dev(aniso_handle h, const double* charge, int id, const int64_t* targets, int64_t nt,
+                             double* out, void* stream) {
+    ENTER(h);
+    return guarded([&] { get(h).mappingDirectDev(charge, id, targets, nt, out, (hipStream_t)stream); });
+}
+
+int aniso_mapping_direct(aniso_handle h, const double* charge, int id, const int64_t* targets, int64_t nt,
+                         double* out) {
+    ENTER(h);
+    return guarded([&] { get(h).mappingDirectHost(charge, id, targets, nt, out); });
+}
+
+int aniso_block_op_direct_dev(aniso_handle h, int which, const double* x, int64_t ldx, const int64_t* targets,
+                              int64_t nt, double* out, int64_t ldo, void* stream) {
+    ENTER(h);
+    return guarded([&] { get(h).blockOpDirectDev(which, x, ldx, targets, nt, out, ldo, (hipStream_t)stream); });
+}
+
+int aniso_block_op_direct(aniso_handle h, int which, const double* u, const int64_t* targets, int64_t nt,
+                          double* out) {
+    ENTER(h);
+    return guarded([&] { get(h).blockOpDirectHost(which, u, targets, nt, out); });
+}
+
 int aniso_apply_block(aniso_handle h, const double* u, const double* sigma_s, double g, double* out) {
     ENTER(h);
     return guarded([&] {

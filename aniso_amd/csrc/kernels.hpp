@@ -451,6 +451,42 @@ void launch_ox_pack_up(int K, int ntask, const int* task, const double* mult, co
                        int nPeer, const int64_t* peerOff, const OxArgs& a, hipStream_t s);
 
 
+// ---- direct evaluation at chosen targets (direct.hip)
+// One launch: targets tg[t0 .. t0 + ntl) (original indices, device) against all N
+// sources, the live output rows of one window.  Input rows x[b * ldx + original index],
+// b < nb, weighted by hw[b]; output row r of the window has Chebyshev degree m0 + r, the
+// r = 0 weight dw[r] on input row drow0 + r, and goes to out[(orow0 + r) * ldo + t] as
+//   scale * sum + corr[(crow0 + r) * ldc + tg[t]],  or minuend[(orow0 + r) * ldm + tg[t]] - that.
+struct DirectArgs {
+    int64_t N = 0;
+    int nb = 0, m0 = 0, drow0 = 0, nout = 0, orow0 = 0, crow0 = 0;
+    const double* x = nullptr;
+    int64_t ldx = 0;
+    const double* hw = nullptr;  // device, nb entries
+    const double* dw = nullptr;  // device, nout entries
+    const int* perm = nullptr;
+    const int* iperm = nullptr;
+    const double* sigT = nullptr;  // sigma_s in tree order, or nullptr
+    const double* wT = nullptr;
+    const double* pxT = nullptr;
+    const double* pyT = nullptr;
+    const double* stcoef = nullptr;
+    const Params* P = nullptr;
+    const int64_t* tg = nullptr;
+    int64_t t0 = 0;
+    double* part = nullptr;  // ntl x direct_blocks(N) x KO doubles
+    double scale = 0.0;
+    const double* corr = nullptr;
+    int64_t ldc = 0;
+    const double* minuend = nullptr;
+    int64_t ldm = 0;
+    double* out = nullptr;
+    int64_t ldo = 0;
+};
+int64_t direct_blocks(int64_t N);  // source blocks (partials per target and row)
+int direct_rows(int nout);         // the compiled window (1, 2, 4, 8, 16, 32) holding nout rows, at most 32
+void launch_direct(int KO, int ntl, const DirectArgs& a, hipStream_t s);
+
 // host-callable device helpers used by tests through the C ABI
 void launch_line_integrals(int n, const double* seg, const double* stcoef, const Params* P, double* out,
                            hipStream_t s);
