@@ -264,7 +264,9 @@ class Aniso:
     """Aniso(ds, qr, ks, as, sr, fn, fm) -- class/@Aniso/Aniso.m:8-11.
 
     ds: squares per side, qr: quadrature rule, ks: kernel size (modes 0..2ks-2),
-    as: anisotropy g, sr: singular rule, fn: FMM np (4), fm: FMM maxLevel.
+    as: anisotropy g, sr: singular rule, fn: FMM np (4, or 6 / 8: a high-order handle,
+    which runs mapping, the block operator and its solve on the mode-shared caches only),
+    fm: FMM maxLevel.
     """
 
     def __init__(self, ds, qr, ks, as_, sr, fn, fm):

@@ -70,7 +70,9 @@ static int host_threads() {
 Operator::Operator(int sz, int d, int ks_, double g_, int ns_, int np_, int maxLevel_)
     : ks(ks_), ns(ns_), np(np_), maxLevel(maxLevel_), g(g_) {
     if (ks < 1) throw std::invalid_argument("kernel size must be >= 1");
-    if (np != kNP) throw std::invalid_argument("np must be 4 on the MI355X path (rank-16 Chebyshev)");
+    if (np != 4 && np != 6 && np != 8)
+        throw std::invalid_argument("np must be 4, 6 or 8 on the MI355X path (Chebyshev rank 16, 36 or 64), got " +
+                                    std::to_string(np));
     if (d < 1 || d > kMaxD) throw std::invalid_argument("quadRule must be in 1..6 on the MI355X path");
     if (maxLevel < 0) throw std::invalid_argument("maxLevel must be >= 0");
     kernelSize = 2 * ks - 1;
@@ -90,13 +92,20 @@ Operator::Operator(int sz, int d, int ks_, double g_, int ns_, int np_, int maxL
     // ANISO_UPPER_PARTIAL=0: a sharded one-collective matvec exchanges the tier-0 roots
     // and runs the upper up tiers on every rank (the round-4 form)
     if (const char* e = std::getenv("ANISO_UPPER_PARTIAL")) plan.xUpPartialIn = std::atoi(e) != 0;
+    if (highOrder()) {  // the mode-shared caches only (ks = 1 too), directed near lists, no rank-16 schedules
+        plan.nearSymmetric = plan.nearSymHs = false;
+        plan.listsOnly = true;
+    }
     plan.build(tree, np, 0, 1);
-    plan.buildExchange(tree, geo.sz, geo.d2);
-    plan.buildTopWait(tree);
+    if (!highOrder()) {
+        plan.buildExchange(tree, geo.sz, geo.d2);
+        plan.buildTopWait(tree);
+    }
     // block handles apply aniso.m's operator through the mode-shared E caches
     // (DESIGN.md §3.9); ANISO_HARMONIC=0 keeps the per-mode operator stream
     useAtt = ks > 1 && !plan.nearSymmetric;
     if (const char* e = std::getenv("ANISO_HARMONIC")) useAtt = useAtt && e[0] != '0';
+    if (highOrder()) useAtt = true;
     if (const char* e = std::getenv("ANISO_OVERLAP")) overlap = std::atoi(e);
     if (const char* e = std::getenv("ANISO_FUSE_SUB")) fuseSub = e[0] != '0';
     if (const char* e = std::getenv("ANISO_TOP_SPIN_LIMIT")) topSpinLimit = (unsigned)std::strtoul(e, nullptr, 10);
@@ -151,14 +160,19 @@ void Operator::getNodes(double* xy) const {
 }
 
 void Operator::setShard(int rank, int nranks) {
+    if (highOrder() && nranks > 1)
+        throw std::invalid_argument("aniso_set_shard: a high-order handle (np = " + std::to_string(np) +
+                                    ") is unsharded only, got nranks = " + std::to_string(nranks));
     if (comm) {  // a communicator belongs to one shard layout; drain its collectives first
         if (device >= 0) HIP_CHECK(hipDeviceSynchronize());
         comm.reset();
         oxReady = false;
     }
     plan.build(tree, np, rank, nranks);
-    plan.buildExchange(tree, geo.sz, geo.d2);
-    plan.buildTopWait(tree);
+    if (!highOrder()) {
+        plan.buildExchange(tree, geo.sz, geo.d2);
+        plan.buildTopWait(tree);
+    }
     pend = Pending();
     for (auto& m : modes) {
         m.Knear.alloc(0);
@@ -292,6 +306,51 @@ void Operator::ensureDevice() {
     dTmpS.alloc(geo.N * sizeof(double));
     ensureWork(1);
     uploadPlan();
+    if (highOrder()) uploadHighPlan();
+}
+
+// The order-dependent tables and the level lists of a high-order handle's far field
+// (high_order.hip): per node its children (-1: empty or none), the parents of each level
+// bottom-up (M2M), the nodes of each level >= 2 top-down (L2L).  The levels are those of
+// the 16-right-hand-side plan (buildMrhsPlan); the leaves, the M2L targets and their
+// pairs are the plan's own lists.
+void Operator::uploadHighPlan() {
+    HoTables tab;
+    ho_tables(np, &tab);
+    dHoTab.upload(&tab, sizeof(tab));
+    const Tree& t = tree;
+    std::vector<int4> ch(t.nn);
+    for (int i = 0; i < t.nn; ++i) {
+        int c[4];
+        for (int q = 0; q < 4; ++q) {
+            c[q] = t.isLeaf[i] ? -1 : t.child[i][q];
+            if (c[q] >= 0 && t.isEmpty[c[q]]) c[q] = -1;
+            if (c[q] >= 0 && (t.parent[c[q]] != i || t.slot[c[q]] != q))
+                throw std::logic_error("high-order plan: child slot mismatch");
+        }
+        ch[i] = make_int4(c[0], c[1], c[2], c[3]);
+    }
+    up(dHoChild, ch);
+    const int D = t.maxLevel;
+    std::vector<std::vector<int>> m2m(D + 1), l2l(D + 1);
+    for (int i = 0; i < t.nn; ++i) {
+        if (t.isEmpty[i] || t.parent[i] < 0) continue;
+        if (!t.isLeaf[i]) m2m[t.level[i]].push_back(i);
+        if (t.level[i] >= 2) l2l[t.level[i]].push_back(i);
+    }
+    std::vector<int> a, b;
+    hoM2mPtr.assign(1, 0);
+    for (int l = D; l >= 1; --l) {
+        a.insert(a.end(), m2m[l].begin(), m2m[l].end());
+        hoM2mPtr.push_back((int)a.size());
+    }
+    hoL2lPtr.assign(1, 0);
+    for (int l = 2; l <= D; ++l) {
+        b.insert(b.end(), l2l[l].begin(), l2l[l].end());
+        hoL2lPtr.push_back((int)b.size());
+    }
+    up(dHoM2m, a);
+    up(dHoL2l, b);
 }
 
 // Per-right-hand-side work arrays, sized for the largest K used so far:
@@ -473,6 +532,19 @@ void Operator::cache(int id) {
     if (!coeffSet) throw std::runtime_error("cache called before setCoeff");
     ensureDevice();
     ModeCache& mc = modes[id];
+    if (highOrder()) {  // the mode's tables on the mode-shared caches: no Km2l / Knear
+        if (!attReady) buildAttCache();
+        HIP_CHECK(hipDeviceSynchronize());  // queued work may still read the folded tables
+        CorrTables ct;
+        ct.build(geo, id);
+        up(mc.C, ct.C);
+        up(mc.mu, ct.mu);
+        mc.hostC = ct.C;
+        mc.hostMu = ct.mu;
+        corrTabs.clear();
+        mc.tables = true;
+        return;
+    }
     if (id == 0) f32Ready = false;  // rebuilt from the new mode-0 operators at the next fp32 apply
     m64.erase(id);
     mc.Knear.alloc((size_t)plan.nearKTotal * sizeof(double));
@@ -505,7 +577,7 @@ void Operator::cache(int id) {
 // by an earlier setCoeff) are freed, so afterwards a mode holds operators only if
 // cache(id) built them since the last setCoeff.
 void Operator::cacheBlock() {
-    if (ks < 2) throw std::invalid_argument("aniso_cache_block: a handle of one block (ks = 1) has no block operator on the mode-shared caches; use aniso_cache(id)");
+    if (ks < 2 && !highOrder()) throw std::invalid_argument("aniso_cache_block: a handle of one block (ks = 1) has no block operator on the mode-shared caches; use aniso_cache(id)");
     if (plan.nearSymmetric)
         throw std::invalid_argument("aniso_cache_block: symmetric near storage (ANISO_NEAR_SYMMETRIC=1) runs the block operator on the per-mode operators; use aniso_cache(id)");
     if (!useAtt)
@@ -540,7 +612,15 @@ void Operator::cacheBytes(int64_t bytes[2]) const {
     bytes[1] = (int64_t)(dAttM2L.bytes + dAttNear.bytes + dSigDiag.bytes);
 }
 
+void Operator::refuseHighOrder(const char* what) const {
+    if (highOrder())
+        throw std::logic_error(std::string(what) + ": a high-order handle (np = " + std::to_string(np) +
+                               ") runs on the mode-shared caches only (aniso_mapping, the block operator, its passes and "
+                               "solve, the direct forms); use an np = 4 handle");
+}
+
 void Operator::needResident(int id, const char* what) const {
+    refuseHighOrder(what);
     if (id < 0 || id >= kernelSize || !modes[id].tables || modes[id].resident) return;
     throw std::logic_error(std::string(what) + " needs the operators of kernel id " + std::to_string(id) +
                            " resident: aniso_cache_block builds none, call aniso_cache(" + std::to_string(id) +
@@ -553,7 +633,8 @@ void Operator::needResident(int id, const char* what) const {
 void Operator::buildAttCache() {
     const Params* P = dParams.as<Params>();
     const int64_t npairs = (int64_t)(plan.attOwner.size() + plan.hmCopyOwner.size());  // stored blocks + copies
-    dAttM2L.alloc((size_t)npairs * 256 * sizeof(double));
+    const size_t rank = (size_t)np * np;
+    dAttM2L.alloc((size_t)npairs * rank * rank * sizeof(double));
     // the near blocks in the layout the harmonic near field reads: directed, or with
     // symmetric U storage its own lists (Plan::buildNearHs)
     const bool hs = plan.nearSymHsOn;
@@ -562,16 +643,23 @@ void Operator::buildAttCache() {
     dSigDiag.alloc((size_t)geo.N * sizeof(double));
     int maxSrc = 1;
     for (size_t li = 0; li < plan.leaves.size(); ++li) maxSrc = std::max<int>(maxSrc, (int)(nptr[li + 1] - nptr[li]));
-    launch_cache_att_m2l(npairs, dAttOwner.as<int>(), dAttOther.as<int>(), dNcx.as<double>(), dNcy.as<double>(),
-                         dNrx.as<double>(), dNry.as<double>(), dStCoef.as<double>(), P, dAttM2L.as<double>(), own);
+    if (highOrder())
+        launch_ho_cache_att(np, npairs, dAttOwner.as<int>(), dAttOther.as<int>(), dNcx.as<double>(), dNcy.as<double>(),
+                            dNrx.as<double>(), dNry.as<double>(), dStCoef.as<double>(), P, dHoTab.as<HoTables>(),
+                            dAttM2L.as<double>(), own);
+    else
+        launch_cache_att_m2l(npairs, dAttOwner.as<int>(), dAttOther.as<int>(), dNcx.as<double>(), dNcy.as<double>(),
+                             dNrx.as<double>(), dNry.as<double>(), dStCoef.as<double>(), P, dAttM2L.as<double>(), own);
     launch_cache_near((int)plan.leaves.size(), dLeaves.as<int>(), (hs ? dHsSrcPtr : dNearPtr).as<int64_t>(),
                       (hs ? dHsSrc : dNearSrc).as<int>(), (hs ? dHsKOff : dNearKOff).as<int64_t>(),
                       dBegin.as<int64_t>(), dCount.as<int64_t>(), dPxT.as<double>(), dPyT.as<double>(),
                       dStCoef.as<double>(), P, kAttMode, maxSrc, dAttNear.as<double>(), own);
     launch_sigma_diag(geo.N, dPxT.as<double>(), dPyT.as<double>(), dStCoef.as<double>(), P, dSigDiag.as<double>(),
                       own);
-    if (!dAttMax.bytes) dAttMax.alloc(sizeof(double));
-    launch_abs_max(npairs * 256, dAttM2L.as<double>(), dAttMax.as<double>(), own);
+    if (!highOrder()) {  // the deterministic sums' bound: rank 16 only
+        if (!dAttMax.bytes) dAttMax.alloc(sizeof(double));
+        launch_abs_max(npairs * 256, dAttM2L.as<double>(), dAttMax.as<double>(), own);
+    }
     HIP_CHECK(hipStreamSynchronize(own));
     attReady = true;
 }
@@ -666,6 +754,7 @@ void Operator::mappingHost(const double* charge, int id, double* out) {
 // mode at 1M points, 24 GB at 4M), freed by setCoeff / cache(id): it is used only
 // when that copy fits in the free HBM, else the 8-column batches run.
 void Operator::mappingBatchedHost(const double* Q, int k, int id, double* Out) {
+    refuseHighOrder("aniso_mapping_batched");
     if (k == 0) return;
     needResident(id, "aniso_mapping_batched");
     ensureDevice();
@@ -741,6 +830,7 @@ void Operator::mappingDev(const double* charge, int id, double* out, hipStream_t
 // supported on this route.
 void Operator::leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask) {
     constexpr int K = kMaxRhs;
+    if (mask != kStageAll) refuseHighOrder("a per-stage apply");
     if (mask != kStageAll)
         throw std::logic_error("mapping stages on kernel id " + std::to_string(id) +
                                ": its operators are not resident (aniso_cache_block builds none); call aniso_cache(" +
@@ -785,6 +875,7 @@ void Operator::forwardTreeDev(const double* xTree, double* ySlice, hipStream_t s
 
 void Operator::forwardTreePhase(int phase, const double* xTree, double* ySlice, double* rootsSend,
                                 const double* rootsRecv, hipStream_t s) {
+    refuseHighOrder("the forward operator");
     needResident(0, "the forward operator");
     if (!modeCached(0)) throw std::runtime_error("forward operator before cache(0)");
     ensureDevice();
@@ -938,8 +1029,10 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     ensureDevice();
     const int64_t nOut = treeOut ? plan.ownEnd - plan.ownBegin : geo.N;
     if (ldx < geo.N || ldo < nOut) throw std::invalid_argument("block apply: leading dimension too small");
-    if (!rhs_supported(K)) {  // pad with zero right-hand sides to the next compiled count
-        const int Kp = rhs_padded(K);
+    // (a high-order handle's harmonic launches start at 2 blocks: ks = 1 runs as 2 with a zero one)
+    const bool padHigh = highOrder() && K == 1 && !call.pass;
+    if (!rhs_supported(K) || padHigh) {  // pad with zero right-hand sides to the next compiled count
+        const int Kp = padHigh ? 2 : rhs_padded(K);
         dPadIn.alloc((size_t)Kp * geo.N * sizeof(double));
         dPadOut.alloc((size_t)Kp * geo.N * sizeof(double));
         if (phase != 2) {  // phase 2 reads what phase 1 staged
@@ -956,6 +1049,10 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         return;
     }
     ensureWork(K);
+    if (highOrder()) {
+        applyBlockHigh(K, x, ldx, treeIn, sigT, nterm, ids, mixes, out, ldo, treeOut, s, mask, call);
+        return;
+    }
     if (up_tier_lds(plan.upMaxTask, K) > 160 * 1024 ||
         down_tier_lds(plan.dnMaxTask, plan.dnMaxLeaves, plan.dnMaxNear, plan.dnMaxChain, K) > 160 * 1024)
         throw std::logic_error("up/down pass task exceeds one workgroup's LDS at " + std::to_string(K) + " right-hand sides");
@@ -1352,6 +1449,82 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     }
 }
 
+// applyBlock on a high-order handle (np = 6, 8): the harmonic block
+// apply with the far field of high_order.hip.  launch_prepare forms the weighted
+// charges, the unstaged harmonic near field stores `out` and the corrections add to it
+// (neither depends on the order); then P2M and M2M level by level, one M2L launch that
+// reads every stored E block once for all modes, L2L level by level and L2P, the last
+// writer (call.minuend: x - mforward(x)).  One stream, every sum in a fixed order.
+void Operator::applyBlockHigh(int K, const double* x, int64_t ldx, bool treeIn, const double* sigT, int nterm,
+                              const int* ids, const double* mixes, double* out, int64_t ldo, bool treeOut,
+                              hipStream_t s, int mask, const ApplyCall& call) {
+    if (call.phase != 0 || plan.nranks > 1) refuseHighOrder("a sharded apply");
+    if (mask != kStageAll) refuseHighOrder("a per-stage apply");
+    if (!attReady) throw std::runtime_error("high-order apply before cache()");
+    HarmWeights hw;
+    const HarmWindow* const win = call.pass ? &call.win : nullptr;
+    if (win) hw = call.hw;
+    else if (!harmonicWeights(K, nterm, ids, mixes, hw))
+        refuseHighOrder("a block apply whose mixes are not aniso.m's forward / mforward");
+    const Params* P = dParams.as<Params>();
+    const HoTables* T = dHoTab.as<HoTables>();
+    const size_t R = (size_t)np * np;
+    if (K > hoWorkK) {
+        dHoMult.alloc((size_t)tree.nn * R * K * sizeof(double));
+        dHoLocal.alloc((size_t)tree.nn * R * K * sizeof(double));
+        hoWorkK = K;
+    }
+    // nodes that are no M2L target (the root, empty nodes) keep zero locals; a smaller K
+    // re-uses the buffers with its own strides
+    HIP_CHECK(hipMemsetAsync(dHoLocal.p, 0, (size_t)tree.nn * R * K * sizeof(double), s));
+    const CorrFold& cf = corrTable(K, nterm, ids, mixes);
+    const bool tr = timeStages != 0, tm = timeStages == 1;
+    auto span = [&](int stage, int a, int b) {
+        if (a >= 0 && b >= 0) spans.push_back({stage, a, b});
+    };
+    const int* operm = treeOut ? nullptr : dPerm.as<int>();
+    const int64_t obase = treeOut ? plan.ownBegin : 0;
+    const double scale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
+    const int nl = (int)plan.leaves.size();
+    const int e0 = tr ? mark(s) : -1;
+    launch_prepare(K, geo.N, x, ldx, treeIn ? 1 : 0, dPerm.as<int>(), sigT, dWT.as<double>(), dFT.as<double>(),
+                   dCT.as<double>(), s);
+    launch_near_hm(K, nl, plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(),
+                   dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
+                   dSigDiag.as<double>(), hw, dFT.as<double>(), operm, obase, ldo, mask, scale, out, nullptr, nullptr,
+                   nullptr, 0, nullptr, nearWpe, s, nullptr, win);
+    const int e1 = tr ? mark(s) : -1;
+    span(4, e0, e1);
+    launch_corr(K, geo.d, plan.ownBegin, plan.ownEnd, dPerm.as<int>(), dIperm.as<int>(), dCT.as<double>(),
+                dFT.as<double>(), cf.Wc.as<double>(), cf.Wm.as<double>(), P, mask, scale, treeOut, ldo, out, s);
+    const int e2 = tr ? mark(s) : -1;
+    if (tm) span(6, e1, e2);
+    launch_ho_p2m(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
+                  dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), dFT.as<double>(), T, dHoMult.as<double>(), s);
+    for (size_t l = 0; l + 1 < hoM2mPtr.size(); ++l)
+        launch_ho_m2m(np, K, hoM2mPtr[l + 1] - hoM2mPtr[l], dHoM2m.as<int>() + hoM2mPtr[l], dHoChild.as<int4>(), T,
+                      dHoMult.as<double>(), s);
+    const int e3 = tr ? mark(s) : -1;
+    if (tm) span(1, e2, e3);
+    launch_ho_m2l(np, K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
+                  dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
+                  dNry.as<double>(), T, hw, win, dHoMult.as<double>(), dHoLocal.as<double>(), s);
+    const int e4 = tr ? mark(s) : -1;
+    span(2, e3, e4);
+    for (size_t l = 0; l + 1 < hoL2lPtr.size(); ++l)
+        launch_ho_l2l(np, K, hoL2lPtr[l + 1] - hoL2lPtr[l], dHoL2l.as<int>() + hoL2lPtr[l], dParent.as<int>(),
+                      dSlot.as<int>(), T, dHoLocal.as<double>(), s);
+    launch_ho_l2p(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
+                  dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), T, dHoLocal.as<double>(), operm, obase, ldo,
+                  scale, out, call.minuend, call.minuendLd, s);
+    if (tr) {
+        const int e5 = mark(s);
+        if (tm) span(5, e4, e5);
+        span(7, e0, e5);
+        ++applies;
+    }
+}
+
 // The modes of a batched apply: every one needs its correction tables; the per-mode
 // stream (any apply that is not the harmonic one or a pass) needs their operators too.
 // Raised before anything is staged or launched.
@@ -1363,7 +1536,7 @@ void Operator::checkModes(int K, int nterm, const int* ids, const double* mixes,
             throw std::runtime_error("mapping on kernel id " + std::to_string(ids[t]) + " before cache(" + std::to_string(ids[t]) + ")");
         lean = lean || !modes[ids[t]].resident;
     }
-    if (!lean) return;
+    if (!lean || highOrder()) return;  // (a high-order apply checks its own form, applyBlockHigh)
     if (call.pass && useAtt && attReady && plan.nearPartTotal == 0) return;  // a pass: the mode-shared caches
     HarmWeights hw;
     bool harmonic = false;
@@ -1401,6 +1574,7 @@ void Operator::blockOpDev(int which, const double* x, int64_t ldx, double* out, 
                           hipStream_t s, double gval, const double* sigT, int phase, double* rootsSend,
                           const double* rootsRecv) {
     if (which < 0 || which > 2) throw std::invalid_argument("block operator: which must be 0, 1 or 2");
+    if (phase != 0) refuseHighOrder("the two-phase block operator");
     checkBlockLimit(phase != 0);
     if (!coeffSet) throw std::runtime_error("block operator before setCoeff");
     ensureDevice();
@@ -1431,7 +1605,7 @@ void Operator::blockOp(int which, const double* x, int64_t ldx, double* out, int
     const int64_t nOut = treeIo ? plan.ownEnd - plan.ownBegin : geo.N;
     if (!treeIo && plan.nranks != 1) throw std::logic_error("block matvec in original order on a sharded handle: use tree order");
     const double* xo = x + (treeIo ? plan.ownBegin : 0);  // x at the output positions
-    if (fuseSub && rhs_supported(nb) && !plan.dnDesc.empty()) {
+    if (fuseSub && rhs_supported(nb) && (highOrder() ? nb > 1 : !plan.dnDesc.empty())) {
         // the down pass, last writer of every owned point, stores x - (near + corr + far)
         call.minuend = xo;
         call.minuendLd = ldx;
@@ -2067,6 +2241,7 @@ void Operator::buildMrhs64(int id) {
 }
 
 void Operator::mrhs64Dev(int id, bool forward, const double* X, double* Y, hipStream_t s, int mask) {
+    refuseHighOrder("the 16-RHS fp64 operator");
     if (plan.nranks != 1) throw std::logic_error("16-right-hand-side operator on a sharded handle");
     if (id < 0 || id >= kernelSize) throw std::out_of_range("kernel id out of range");
     if (forward && id != 0) throw std::invalid_argument("the forward operator is mode 0's (main.cpp:125-136)");
@@ -2120,6 +2295,7 @@ void Operator::mrhs64Dev(int id, bool forward, const double* X, double* Y, hipSt
 }
 
 void Operator::forwardF32Dev(const float* X, float* Y, hipStream_t s, int mask) {
+    refuseHighOrder("the fp32 operator");
     if (plan.nranks != 1) throw std::logic_error("fp32 operator on a sharded handle");
     if (!f32Ready) buildF32();
     ensureDevice();
@@ -2168,6 +2344,7 @@ void Operator::forwardF32Dev(const float* X, float* Y, hipStream_t s, int mask) 
 // what it sends to peer p is p's halo inside its own range, so every rank's halo
 // ranges are exchanged once (one all-gather of the counts, one of the ranges).
 void Operator::commInit(std::unique_ptr<Collectives> c) {
+    refuseHighOrder("aniso_comm_init");
     if (!c) throw std::invalid_argument("null communicator");
     if (c->nranks != plan.nranks || c->rank != plan.rank)
         throw std::logic_error("communicator rank / size (" + std::to_string(c->rank) + " of " +
@@ -2499,6 +2676,7 @@ bool Operator::oneExchangeUsable(int which) {
 }
 
 void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s) {
+    refuseHighOrder("aniso_block_op_sharded_dev");
     if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
     if (ldx < geo.N || ldy < geo.N) throw std::invalid_argument("sharded block operator: leading dimension below N");
     blockOpShardedOwned(which, x, ldx, y + plan.ownBegin, ldy, s);

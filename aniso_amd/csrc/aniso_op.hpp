@@ -292,6 +292,9 @@ public:
     // launches of their own; ANISO_DET_PER_TARGET=1 keeps the round-2 form instead (one
     // wave per target, every sum in a fixed order, every block read from both ends)
     void setDeterministic(bool on) {
+        if (on && highOrder())
+            throw std::invalid_argument("deterministic applies: not on a high-order handle (np = " + std::to_string(np) +
+                                        "): its far field sums in a fixed order and is bitwise repeatable as it is");
         if (on && ks > kMaxRhs)
             throw std::invalid_argument("deterministic applies: not with more than " + std::to_string(kMaxRhs) +
                                         " blocks (ks = " + std::to_string(ks) + ")");
@@ -299,6 +302,11 @@ public:
         useClusters = !(on && detPerTarget);
     }
     bool deterministicOn() const { return detSums || !useClusters; }
+    // a high-order handle (np = 6 or 8): every mode runs on the mode-shared
+    // caches; whatever streams per-mode operators, shards or runs single stages is refused
+    bool highOrder() const { return np != kNP; }
+    // raise (ANISO_ERR_STATE) on a high-order handle, before anything is launched
+    void refuseHighOrder(const char* what) const;
     // the mode's own operators are resident (cache(id) since the last setCoeff)
     bool modeCached(int id) const { return id >= 0 && id < kernelSize && modes[id].resident; }
     // raise (ANISO_ERR_STATE) if the mode was made ready by cacheBlock only: `what`
@@ -323,7 +331,7 @@ public:
 
     // stats
     int64_t nearEntries() const { return plan.pairsNear; }
-    int64_t m2lEntries() const { return plan.pairsM2L * 256; }
+    int64_t m2lEntries() const { return plan.pairsM2L * np * np * np * np; }
     int maxNearSources() const { return maxNearS; }
 
 private:
@@ -379,6 +387,14 @@ private:
     using PhaseFn = std::function<void(ApplyCall&)>;
     void shardedExchange(int nb, double* x, int64_t ldx, bool one, hipStream_t s, const PhaseFn& phase1,
                          const PhaseFn& phase2);
+    // the far field of a high-order handle (high_order.hip): applyBlock's branch for np != 4
+    void applyBlockHigh(int K, const double* x, int64_t ldx, bool treeIn, const double* sigT, int nterm, const int* ids,
+                        const double* mixes, double* out, int64_t ldo, bool treeOut, hipStream_t s, int mask,
+                        const ApplyCall& call);
+    void uploadHighPlan();  // its tables and level lists (ensureDevice: they follow the tree alone)
+    DevBuf dHoTab, dHoChild, dHoM2m, dHoL2l, dHoMult, dHoLocal;
+    std::vector<int> hoM2mPtr, hoL2lPtr;  // per level: its range of dHoM2m (bottom-up) / dHoL2l (top-down)
+    int hoWorkK = 0;
     // mapping of a mode whose operators are not resident: one pass of the offset form
     void leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask);
     // the modes of a batched apply are usable by it: tables for the harmonic launches,

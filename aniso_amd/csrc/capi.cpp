@@ -836,6 +836,7 @@ int aniso_comm_init_rccl(aniso_handle h, const unsigned char* id) {
     return guarded([&] {
         CHECK_PTR(id);
         auto& op = get(h);
+        op.refuseHighOrder("aniso_comm_init");  // before a communicator is made
         op.commInit(aniso::make_rccl_collectives(id, op.plan.nranks, op.plan.rank));
     });
 }
@@ -845,6 +846,7 @@ int aniso_comm_init_callbacks(aniso_handle h, const aniso_collectives* c) {
     return guarded([&] {
         CHECK_PTR(c);
         auto& op = get(h);
+        op.refuseHighOrder("aniso_comm_init");  // before a communicator is made
         op.commInit(aniso::make_callback_collectives(*c, op.plan.nranks, op.plan.rank));
     });
 }
@@ -988,6 +990,7 @@ int aniso_comm_init_loopback(aniso_handle h) {
     ENTER(h);
     return guarded([&] {
         auto& op = get(h);
+        op.refuseHighOrder("aniso_comm_init");  // before a communicator is made
         op.commInit(aniso::make_loopback_collectives(op.plan.nranks, op.plan.rank));
     });
 }

@@ -77,6 +77,10 @@ struct Plan {
     // input: symmetric U storage in the near field (worth it for single right-hand
     // sides; block applies read every block directed)
     bool nearSymmetric = true;
+    // input: a high-order handle (np = 6, 8) reads the lists only -- M2L
+    // targets and mode-shared pairs, leaves and directed near lists.  The rank-16 schedules
+    // (up / down tiers, clusters, staged near tables, the exchange) are not built.
+    bool listsOnly = false;
     int nearMaxLeaf = 0;  // largest owned target leaf (points)
     // input: canonical M2L pairs kept per target (<= kMaxCanon; block handles use
     // fewer: k_m2l stages their transposed products in LDS)

@@ -249,9 +249,10 @@ std::vector<int64_t> shard_cuts(const Tree& t, int nranks) {
 void Plan::build(const Tree& t, int np, int rank_, int nranks_) {
     (void)np;
     if (nranks_ < 1 || rank_ < 0 || rank_ >= nranks_) throw std::invalid_argument("bad shard rank/nranks");
-    const bool symNear = nearSymmetric, symHs = nearSymHs, upIn = xUpPartialIn;
+    const bool symNear = nearSymmetric, symHs = nearSymHs, upIn = xUpPartialIn, lists = listsOnly;
     const int capCanon = maxCanon;
     *this = Plan();
+    listsOnly = lists;
     nearSymmetric = symNear;
     nearSymHs = symHs;
     xUpPartialIn = upIn;
@@ -273,7 +274,7 @@ void Plan::build(const Tree& t, int np, int rank_, int nranks_) {
         const int D = t.maxLevel;
         tierRootLevel.clear();
         tierBottomLevel.clear();
-        if (D >= 1) {
+        if (D >= 1 && !listsOnly) {
             const int bspan = 3;  // levels of the bottom tier (3: 4x the tasks at 1/4 the LDS; down 0.124 -> 0.090 ms, r01g)
             tierRootLevel.push_back(std::max(1, D - (bspan - 1)));
             tierBottomLevel.push_back(D);
@@ -284,7 +285,7 @@ void Plan::build(const Tree& t, int np, int rank_, int nranks_) {
             }
         }
     }
-    buildUpTasks(t);
+    if (!listsOnly) buildUpTasks(t);
     // ---- M2L over V then X (bbfmm.h:1051-1065), active non-empty targets.
     // V is a symmetric relation and K_{B<-A} = (-1)^m K_{A<-B}^T (tau is symmetric,
     // g_m(-d) = (-1)^m g_m(d)), so when both ends are targets here only the block
@@ -359,7 +360,7 @@ void Plan::build(const Tree& t, int np, int rank_, int nranks_) {
         m2lPtr.push_back((int64_t)m2lSrc.size());
     }
     m2lCanon = canon;
-    buildClusters(t);
+    if (!listsOnly) buildClusters(t);
     storedM2L = (int64_t)m2lSrc.size();
     m2lOutSlot.assign(canon, -1);
     m2lInPtr.push_back(0);
@@ -446,7 +447,7 @@ void Plan::build(const Tree& t, int np, int rank_, int nranks_) {
     nsPts.clear();
     nearLoc.clear();
     nsMax = 0;
-    if (nearMaxLeaf <= 16 && !leaves.empty()) {
+    if (nearMaxLeaf <= 16 && !leaves.empty() && !listsOnly) {
         nearLoc.resize(nearPts.size());
         std::vector<int> u;
         for (size_t g0 = 0; g0 < leaves.size(); g0 += 16) {
@@ -469,6 +470,7 @@ void Plan::build(const Tree& t, int np, int rank_, int nranks_) {
             nsMax = std::max<int>(nsMax, (int)u.size());
         }
     }
+    if (listsOnly) return;
     buildNearHs(t, leafIdx);
     buildDownTasks(t);
     buildNearUp(t);

@@ -386,6 +386,43 @@ void launch_add_rows(int64_t n, int nrhs, const double* a, int64_t lda, double* 
 void launch_sub_slice(int64_t n, int nrhs, const double* x, int64_t ldx, const double* a, int64_t lda, double* y,
                       int64_t ldy, hipStream_t s);
 
+// ---- high-order handles (high_order.hip): np = 6 or 8, rank R = np^2.
+// The order-dependent tables, apart from the rank-16 Params: the Chebyshev nodes,
+// T_l(c_i) at [i + l np], and the 1-D transfer S[b][c np + p] = the weight of parent node
+// p at child node c of half b (M2M / L2L apply S[y half] (x) S[x half] as two transforms).
+constexpr int kMaxNP = 8;
+struct HoTables {
+    double cheb[kMaxNP];
+    double tnode[kMaxNP * kMaxNP];
+    double S[2][kMaxNP * kMaxNP];
+};
+void ho_tables(int np, HoTables* t);  // host
+// E[pair][s][t] = e^-tau between the pair's Chebyshev nodes (R x R doubles per stored pair)
+void launch_ho_cache_att(int np, int64_t npairs, const int* pairTgt, const int* src, const double* ncx,
+                         const double* ncy, const double* nrx, const double* nry, const double* stcoef,
+                         const Params* P, const HoTables* T, double* E, hipStream_t s);
+// expansions [node][R][K]; leafInfo as Plan::leafInfo; fT from launch_prepare
+void launch_ho_p2m(int np, int K, int nl, const int4* leafInfo, const double* ncx, const double* ncy,
+                   const double* nrx, const double* nry, const double* pxT, const double* pyT, const double* fT,
+                   const HoTables* T, double* mult, hipStream_t s);
+// one level: child[n] = the four children of node n (< 0: empty, contributes nothing)
+void launch_ho_m2m(int np, int K, int nn, const int* nodes, const int4* child, const HoTables* T, double* mult,
+                   hipStream_t s);
+// the pair lists of the mode-shared plan (Plan::attPtr / attSrc / attBlk over m2lTgt);
+// win: the offset form (K = 8); local = om_i x the unscaled sums, as k_m2l_hm stores them
+void launch_ho_m2l(int np, int K, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk,
+                   const double* E, const double* ncx, const double* ncy, const double* nrx, const double* nry,
+                   const HoTables* T, const HarmWeights& hw, const HarmWindow* win, const double* mult,
+                   double* local, hipStream_t s);
+// one level, top-down: local[n] += L2L of its parent's (complete) local
+void launch_ho_l2l(int np, int K, int nn, const int* nodes, const int* parent, const int* slot, const HoTables* T,
+                   double* local, hipStream_t s);
+// out += scale * L2P (xsub: out = xsub - (out + scale * L2P)), output modes as k_down_tier
+void launch_ho_l2p(int np, int K, int nl, const int4* leafInfo, const double* ncx, const double* ncy,
+                   const double* nrx, const double* nry, const double* pxT, const double* pyT, const HoTables* T,
+                   const double* local, const int* operm, int64_t obase, int64_t ldo, double scale, double* out,
+                   const double* xsub, int64_t ldx, hipStream_t s);
+
 // ---- cache build and helpers (kernels.hip)
 void launch_cache_m2l(int64_t npairs, const int* pairTgt, const int* src, const double* ncx, const double* ncy,
                       const double* nrx, const double* nry, const double* stcoef, const Params* P, int mode,

@@ -340,6 +340,7 @@ void Operator::forwardDev(const double* u, double* out, hipStream_t s) {
 // printed at the start of every inner iteration plus the final one.
 int Operator::gmresHost(const double* q, double* xh, int m, int maxit, double tol, double* hist, int maxhist,
                         double* finalResid) {
+    refuseHighOrder("aniso_gmres");
     if (m < 1 || maxit < 0) throw std::invalid_argument("GMRES needs m >= 1 and maxit >= 0");
     needResident(0, "aniso_gmres");
     if (!modeCached(0)) throw std::runtime_error("GMRES before cache(0)");
@@ -788,6 +789,7 @@ static void rows_copy(int rows, int64_t len, const double* src, int64_t lds, dou
 // every rank at the same step.
 int Operator::blockSolveShardedDev(const double* rhs, int64_t ldr, double* x, int64_t ldx, int restart, double tol,
                                    int maxit, double* hist, int maxhist, double* relresOut, hipStream_t s) {
+    refuseHighOrder("aniso_block_solve_sharded_dev");
     if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
     ensureDevice();
     const int64_t N = geo.N, ob = plan.ownBegin, owned = plan.ownEnd - plan.ownBegin, L = (int64_t)ks * owned;
@@ -1100,6 +1102,7 @@ int Operator::solveMixed(int nrhs, const double* B, int64_t ldb, double* X, int6
 // entry's restart bound); neither touches the device
 void Operator::mixedCheckState(const char* what, const char* entry) const {
     const std::string w(what);
+    refuseHighOrder(entry);
     if (plan.nranks != 1) throw std::logic_error(w + " on a sharded handle");
     if (!coeffSet) throw std::runtime_error(w + " before setCoeff");
     needResident(0, entry);
