@@ -75,6 +75,9 @@ def lib():
             "aniso_mapping": [P, dp, I, dp],
             "aniso_mapping_dev": [P, P, I, P, P],
             "aniso_mapping_batched": [P, dp, I, I, dp],
+            "aniso_mapping_multi_dev": [P, I, I, P, I64, P, I64, P],
+            "aniso_forward_multi_dev": [P, I, P, I64, P, I64, P],
+            "aniso_mapping_multi": [P, dp, I, I, dp],
             "aniso_mapping_stages_dev": [P, P, I, I, P, P],
             "aniso_set_shard": [P, I, I],
             "aniso_get_shard": [P, lp, lp],
@@ -341,7 +344,43 @@ class Aniso:
         _check(lib().aniso_mapping_batched(self.address, _dp(Q), Q.shape[1], int(id_), _dp(out)))
         return out
 
+    def mapping_multi(self, Q, id_):
+        """K_id applied to the k columns of Q (N x k), also on a high-order or lean handle
+        (aniso_mapping_multi; mapping_multi_dev on host arrays)."""
+        Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
+        if Q.ndim != 2 or Q.shape[0] != self.N:
+            raise AnisoError(1, f"Q must be N x k with N = {self.N}")
+        out = np.zeros(Q.shape, order="F")
+        _check(lib().aniso_mapping_multi(self.address, _dp(Q), Q.shape[1], int(id_), _dp(out)))
+        return out
+
     # ---- device-pointer variants (torch tensors on the current HIP device)
+    def mapping_multi_dev(self, X, id_, Out, stream=None):
+        """Out[k] = K_id X[k]: X and Out are (nrhs, >= N) float64 CUDA tensors with unit column
+        stride (strided rows allowed; entries past N of a row are left alone).  One mode on
+        several vectors wherever the mode is ready: on a high-order handle 8 columns per read
+        of the mode-shared caches, on a lean np = 4 mode one mapping_dev pass per column."""
+        import torch
+
+        nrhs = int(X.shape[0]) if isinstance(X, torch.Tensor) and X.dim() == 2 else -1
+        px, po = _dev_rows(X, nrhs, self.N, "X"), _dev_rows(Out, nrhs, self.N, "Out")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _check(lib().aniso_mapping_multi_dev(self.address, int(id_), nrhs, px, max(X.stride(0), self.N), po,
+                                             max(Out.stride(0), self.N), ctypes.c_void_p(s)))
+        return Out
+
+    def forward_multi_dev(self, X, Out, stream=None):
+        """Out[k] = X[k] - K_0(sigma_s .* X[k]) (main.cpp forwardOperator per row); tensors as
+        mapping_multi_dev, X and Out must not overlap."""
+        import torch
+
+        nrhs = int(X.shape[0]) if isinstance(X, torch.Tensor) and X.dim() == 2 else -1
+        px, po = _dev_rows(X, nrhs, self.N, "X"), _dev_rows(Out, nrhs, self.N, "Out")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _check(lib().aniso_forward_multi_dev(self.address, nrhs, px, max(X.stride(0), self.N), po,
+                                             max(Out.stride(0), self.N), ctypes.c_void_p(s)))
+        return Out
+
     def mapping_dev(self, charge, id_, out, stream=None, mask=STAGE_ALL):
         """charge/out: contiguous float64 torch tensors of N entries on the GPU."""
         import torch

@@ -828,7 +828,7 @@ void Operator::mappingDev(const double* charge, int id, double* out, hipStream_t
 // over the M2L and the near field, with mode id's correction stencils and, for id = 0,
 // the sigma_t diagonal (dw).  The launches are the pass's; the stage mask is not
 // supported on this route.
-void Operator::leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask) {
+void Operator::leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask, const double* sigT) {
     constexpr int K = kMaxRhs;
     if (mask != kStageAll) refuseHighOrder("a per-stage apply");
     if (mask != kStageAll)
@@ -854,7 +854,7 @@ void Operator::leanMapping(const double* charge, int id, double* out, hipStream_
     call.hw.dw[row] = id == 0 ? 1.0 : 0.0;
     std::vector<double> sub((size_t)K * K, 0.0);  // the correction fold: mode id, input row 0 to output row `row`
     sub[(size_t)row * K] = 1.0;
-    applyBlock(K, dPassIn.as<double>(), N, false, nullptr, 1, &id, sub.data(), dPassOut.as<double>(), N, false, s,
+    applyBlock(K, dPassIn.as<double>(), N, false, sigT, 1, &id, sub.data(), dPassOut.as<double>(), N, false, s,
                kStageAll, call);
     HIP_CHECK(hipMemcpyAsync(out, orow, N * sizeof(double), hipMemcpyDeviceToDevice, s));
 }
@@ -1522,6 +1522,176 @@ void Operator::applyBlockHigh(int K, const double* x, int64_t ldx, bool treeIn, 
         if (tm) span(5, e4, e5);
         span(7, e0, e5);
         ++applies;
+    }
+}
+
+// ---- one mode on several vectors ----
+
+bool Operator::modeApplyCheck(const char* what, int id, int nrhs, const void* x, int64_t ldx, const void* out,
+                              int64_t ldo, bool minuend) const {
+    const std::string w(what);
+    if (nrhs < 0) throw std::invalid_argument(w + ": nrhs must be >= 0, got " + std::to_string(nrhs));
+    if (ldx < geo.N) throw std::invalid_argument(w + ": ldx = " + std::to_string(ldx) + " is below N = " + std::to_string(geo.N));
+    if (ldo < geo.N) throw std::invalid_argument(w + ": ldo = " + std::to_string(ldo) + " is below N = " + std::to_string(geo.N));
+    if (nrhs > 0 && !x) throw std::invalid_argument(w + ": x is NULL");
+    if (nrhs > 0 && !out) throw std::invalid_argument(w + ": out is NULL");
+    if (id < 0 || id >= kernelSize)
+        throw std::out_of_range(w + ": kernel id " + std::to_string(id) + " out of range [0, " + std::to_string(kernelSize) + ")");
+    if (nrhs == 0) return false;
+    if (minuend) {  // the near field stores `out` before the down pass reads x at the same points
+        const char* xb = static_cast<const char*>(x);
+        const char* ob = static_cast<const char*>(out);
+        const size_t xs = ((size_t)(nrhs - 1) * ldx + geo.N) * sizeof(double), os = ((size_t)(nrhs - 1) * ldo + geo.N) * sizeof(double);
+        if (xb < ob + os && ob < xb + xs) throw std::invalid_argument(w + ": x and out overlap");
+    }
+    if (plan.nranks > 1)
+        throw std::logic_error(w + " on a sharded handle: it writes every target (use an unsharded handle)");
+    if (!coeffSet)
+        throw std::runtime_error(w + " before aniso_set_coeff and aniso_cache(" + std::to_string(id) + ") or aniso_cache_block");
+    const ModeCache& mc = modes[id];
+    const bool shared = useAtt && attReady && plan.nearPartTotal == 0;  // the mode-shared caches serve it
+    if (!mc.tables || !(highOrder() ? attReady : (mc.resident || shared)))
+        throw std::runtime_error(w + " on kernel id " + std::to_string(id) + " before aniso_cache(" + std::to_string(id) +
+                                 ") or aniso_cache_block");
+    return true;
+}
+
+// One chunk on a high-order handle: applyBlockHigh's launch sequence with the mode
+// kernels in place of launch_near_hm and launch_ho_m2l.  launch_prepare forms the
+// (sigma-weighted) charges; the near field stores `out`, the corrections of mode id
+// (identity fold) add to it; P2M and M2M level by level, the mode M2L, L2L level by
+// level and L2P, the last writer (minuend: x - K_id(...)).  The expansions live in the
+// block path's dHoMult / dHoLocal.
+void Operator::modeApplyHigh(int id, int K, const double* x, int64_t ldx, const double* sigT, const double* minuend,
+                             int64_t minuendLd, double* out, int64_t ldo, hipStream_t s) {
+    const Params* P = dParams.as<Params>();
+    const HoTables* T = dHoTab.as<HoTables>();
+    const size_t R = (size_t)np * np;
+    ensureWork(K);
+    if (K > hoWorkK) {
+        dHoMult.alloc((size_t)tree.nn * R * K * sizeof(double));
+        dHoLocal.alloc((size_t)tree.nn * R * K * sizeof(double));
+        hoWorkK = K;
+    }
+    // nodes that are no M2L target keep zero locals (as applyBlockHigh)
+    HIP_CHECK(hipMemsetAsync(dHoLocal.p, 0, (size_t)tree.nn * R * K * sizeof(double), s));
+    std::vector<double> eye((size_t)K * K, 0.0);
+    for (int i = 0; i < K; ++i) eye[(size_t)i * K + i] = 1.0;
+    const CorrFold& cf = corrTable(K, 1, &id, eye.data());
+    const bool tr = timeStages != 0, tm = timeStages == 1;
+    auto span = [&](int stage, int a, int b) {
+        if (a >= 0 && b >= 0) spans.push_back({stage, a, b});
+    };
+    const int* operm = dPerm.as<int>();
+    const double scale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
+    const int nl = (int)plan.leaves.size();
+    const int e0 = tr ? mark(s) : -1;
+    launch_prepare(K, geo.N, x, ldx, 0, dPerm.as<int>(), sigT, dWT.as<double>(), dFT.as<double>(), dCT.as<double>(), s);
+    launch_near_mode(K, id, nl, plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(),
+                     dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
+                     dSigDiag.as<double>(), dFT.as<double>(), operm, 0, ldo, scale, out, s);
+    const int e1 = tr ? mark(s) : -1;
+    span(4, e0, e1);
+    launch_corr(K, geo.d, plan.ownBegin, plan.ownEnd, dPerm.as<int>(), dIperm.as<int>(), dCT.as<double>(),
+                dFT.as<double>(), cf.Wc.as<double>(), cf.Wm.as<double>(), P, kStageAll, scale, false, ldo, out, s);
+    const int e2 = tr ? mark(s) : -1;
+    if (tm) span(6, e1, e2);
+    launch_ho_p2m(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
+                  dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), dFT.as<double>(), T, dHoMult.as<double>(), s);
+    for (size_t l = 0; l + 1 < hoM2mPtr.size(); ++l)
+        launch_ho_m2m(np, K, hoM2mPtr[l + 1] - hoM2mPtr[l], dHoM2m.as<int>() + hoM2mPtr[l], dHoChild.as<int4>(), T,
+                      dHoMult.as<double>(), s);
+    const int e3 = tr ? mark(s) : -1;
+    if (tm) span(1, e2, e3);
+    launch_ho_m2l_mode(np, K, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
+                       dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
+                       dNry.as<double>(), T, dHoMult.as<double>(), dHoLocal.as<double>(), s);
+    const int e4 = tr ? mark(s) : -1;
+    span(2, e3, e4);
+    for (size_t l = 0; l + 1 < hoL2lPtr.size(); ++l)
+        launch_ho_l2l(np, K, hoL2lPtr[l + 1] - hoL2lPtr[l], dHoL2l.as<int>() + hoL2lPtr[l], dParent.as<int>(),
+                      dSlot.as<int>(), T, dHoLocal.as<double>(), s);
+    launch_ho_l2p(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
+                  dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), T, dHoLocal.as<double>(), operm, 0, ldo, scale,
+                  out, minuend, minuendLd, s);
+    if (tr) {
+        const int e5 = mark(s);
+        if (tm) span(5, e4, e5);
+        span(7, e0, e5);
+        ++applies;
+    }
+}
+
+void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, const double* sigT, bool minuend,
+                            double* out, int64_t ldo, hipStream_t s) {
+    if (!modeApplyCheck("mode apply", id, nrhs, x, ldx, out, ldo, minuend)) return;
+    checkDeviceErrors();
+    ensureDevice();
+    const int64_t N = geo.N;
+    if (highOrder()) {
+        for (int j0 = 0; j0 < nrhs; j0 += kMaxRhs) {
+            const int nb = std::min(kMaxRhs, nrhs - j0);
+            const int K = nb == 1 ? 2 : rhs_padded(nb);  // (the mode kernels start at 2 columns)
+            const double* xc = x + (size_t)j0 * ldx;
+            double* oc = out + (size_t)j0 * ldo;
+            if (K == nb) {
+                modeApplyHigh(id, K, xc, ldx, sigT, minuend ? xc : nullptr, ldx, oc, ldo, s);
+                continue;
+            }
+            // zero columns pad the chunk to the next compiled count, as applyBlock pads
+            dPadIn.alloc((size_t)K * N * sizeof(double));
+            dPadOut.alloc((size_t)K * N * sizeof(double));
+            HIP_CHECK(hipMemsetAsync(dPadIn.p, 0, (size_t)K * N * sizeof(double), s));
+            HIP_CHECK(hipMemcpy2DAsync(dPadIn.p, N * sizeof(double), xc, ldx * sizeof(double), N * sizeof(double), nb,
+                                       hipMemcpyDeviceToDevice, s));
+            modeApplyHigh(id, K, dPadIn.as<double>(), N, sigT, minuend ? dPadIn.as<double>() : nullptr, N,
+                          dPadOut.as<double>(), N, s);
+            HIP_CHECK(hipMemcpy2DAsync(oc, ldo * sizeof(double), dPadOut.p, N * sizeof(double), N * sizeof(double), nb,
+                                       hipMemcpyDeviceToDevice, s));
+        }
+        return;
+    }
+    // np = 4.  The forward form goes through a buffer: the applies store K_id(...) there
+    // and the subtraction writes `out`
+    double* dst = out;
+    int64_t ldd = ldo;
+    if (minuend) {
+        dBlk.alloc((size_t)nrhs * N * sizeof(double));
+        dst = dBlk.as<double>();
+        ldd = N;
+    }
+    if (modes[id].resident) {  // mappingBatchedHost's 8-column branch on device pointers
+        for (int j0 = 0; j0 < nrhs; j0 += kMaxRhs) {
+            const int nb = std::min(kMaxRhs, nrhs - j0);
+            std::vector<double> eye((size_t)nb * nb, 0.0);
+            for (int i = 0; i < nb; ++i) eye[(size_t)i * nb + i] = 1.0;
+            ApplyCall call;
+            applyBlock(nb, x + (size_t)j0 * ldx, ldx, false, sigT, 1, &id, eye.data(), dst + (size_t)j0 * ldd, ldd, false,
+                       s, kStageAll, call);
+        }
+    } else {  // a lean mode: one pass of the offset form per column
+        for (int j = 0; j < nrhs; ++j) leanMapping(x + (size_t)j * ldx, id, dst + (size_t)j * ldd, s, kStageAll, sigT);
+    }
+    if (minuend) launch_sub_slice(N, nrhs, x, ldx, dBlk.as<double>(), N, out, ldo, s);
+}
+
+// N x k column-major host arrays through modeApplyDev, 8 columns at a time
+void Operator::mappingMultiHost(const double* Q, int k, int id, double* Out) {
+    if (!modeApplyCheck("aniso_mapping_multi", id, k, Q, geo.N, Out, geo.N, false)) return;
+    ensureDevice();
+    const int64_t N = geo.N;
+    const int kb = std::min(k, kMaxRhs);
+    DevBuf dq, dout;
+    dq.alloc((size_t)kb * N * sizeof(double));
+    dout.alloc((size_t)kb * N * sizeof(double));
+    for (int j0 = 0; j0 < k; j0 += kb) {
+        const int nb = std::min(kb, k - j0);
+        HIP_CHECK(hipMemcpyAsync(dq.p, Q + (size_t)j0 * N, (size_t)nb * N * sizeof(double), hipMemcpyHostToDevice, own));
+        modeApplyDev(id, nb, dq.as<double>(), N, nullptr, false, dout.as<double>(), N, own);
+        HIP_CHECK(hipMemcpyAsync(Out + (size_t)j0 * N, dout.p, (size_t)nb * N * sizeof(double), hipMemcpyDeviceToHost,
+                                 own));
+        HIP_CHECK(hipStreamSynchronize(own));
+        checkDeviceErrors();
     }
 }
 

@@ -113,6 +113,23 @@ public:
     void cacheBytes(int64_t bytes[2]) const;
     void mappingHost(const double* charge, int id, double* out);
     void mappingBatchedHost(const double* Q, int k, int id, double* Out);  // N x k column-major
+    // One mode on nrhs vectors wherever the mode is ready: rows of N
+    // doubles in original order, strides ldx, ldo >= N, unsharded handles.
+    //     out[k] = K_id (sigT .* x[k])          (sigT: tree-order sigma_s, or nullptr)
+    //     out[k] = x[k] - K_id (sigT .* x[k])   (minuend; x and out must not overlap)
+    // A high-order handle runs chunks of 8 columns (a remainder zero-padded to 2, 4 or 8)
+    // through the mode kernels of mode_apply.hip on the mode-shared caches: the entry's
+    // factor is formed once per chunk.  np = 4: a resident mode runs applyBlock's identity
+    // mix in chunks of 8; a lean mode runs ONE leanMapping PER COLUMN -- correct, and a
+    // whole 8-row pass over the shared caches for every column (no rank-16 mode kernel).
+    // modeApplyCheck raises everything that can be refused before the device is touched
+    // (false: nrhs = 0, nothing to do).
+    bool modeApplyCheck(const char* what, int id, int nrhs, const void* x, int64_t ldx, const void* out, int64_t ldo,
+                        bool minuend) const;
+    void modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, const double* sigT, bool minuend, double* out,
+                      int64_t ldo, hipStream_t s);
+    void mappingMultiHost(const double* Q, int k, int id, double* Out);  // N x k column-major
+    const double* sigmaSTree() const { return dSigmaT.as<double>(); }    // sigma_s in tree order (device)
     void mappingDev(const double* charge, int id, double* out, hipStream_t s, int stageMask = 0x3f);
     void mappingTreeDev(const double* qTree, int id, double* outSlice, hipStream_t s);
     void forwardTreeDev(const double* xTree, double* ySlice, hipStream_t s);
@@ -396,7 +413,11 @@ private:
     std::vector<int> hoM2mPtr, hoL2lPtr;  // per level: its range of dHoM2m (bottom-up) / dHoL2l (top-down)
     int hoWorkK = 0;
     // mapping of a mode whose operators are not resident: one pass of the offset form
-    void leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask);
+    // (sigT: tree-order sigma_s multiplied into the charge by the pass's launch_prepare)
+    void leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask, const double* sigT = nullptr);
+    // modeApplyDev's chunk of K = 2, 4, 5 or 8 columns on a high-order handle
+    void modeApplyHigh(int id, int K, const double* x, int64_t ldx, const double* sigT, const double* minuend,
+                       int64_t minuendLd, double* out, int64_t ldo, hipStream_t s);
     // the modes of a batched apply are usable by it: tables for the harmonic launches,
     // resident operators for the per-mode stream (checked before anything is launched)
     void checkModes(int K, int nterm, const int* ids, const double* mixes, const ApplyCall& call) const;

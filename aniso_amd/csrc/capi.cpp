@@ -214,6 +214,31 @@ int aniso_mapping_batched(aniso_handle h, const double* Q, int k, int id, double
     });
 }
 
+int aniso_mapping_multi_dev(aniso_handle h, int id, int nrhs, const double* x, int64_t ldx, double* out, int64_t ldo,
+                            void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        auto& op = get(h);
+        if (!op.modeApplyCheck("aniso_mapping_multi_dev", id, nrhs, x, ldx, out, ldo, false)) return;
+        op.modeApplyDev(id, nrhs, x, ldx, nullptr, false, out, ldo, (hipStream_t)stream);
+    });
+}
+
+int aniso_forward_multi_dev(aniso_handle h, int nrhs, const double* x, int64_t ldx, double* out, int64_t ldo,
+                            void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        auto& op = get(h);
+        if (!op.modeApplyCheck("aniso_forward_multi_dev", 0, nrhs, x, ldx, out, ldo, true)) return;
+        op.modeApplyDev(0, nrhs, x, ldx, op.sigmaSTree(), true, out, ldo, (hipStream_t)stream);
+    });
+}
+
+int aniso_mapping_multi(aniso_handle h, const double* Q, int k, int id, double* Out) {
+    ENTER(h);
+    return guarded([&] { get(h).mappingMultiHost(Q, k, id, Out); });
+}
+
 int aniso_forward_dev(aniso_handle h, const double* u, double* out, void* stream) {
     ENTER(h);
     return guarded([&] {

@@ -422,6 +422,18 @@ void launch_ho_l2p(int np, int K, int nl, const int4* leafInfo, const double* nc
                    const double* nrx, const double* nry, const double* pxT, const double* pyT, const HoTables* T,
                    const double* local, const int* operm, int64_t obase, int64_t ldo, double scale, double* out,
                    const double* xsub, int64_t ldx, hipStream_t s);
+// ---- one mode on K columns of a high-order handle (mode_apply.hip): K in
+// {2, 4, 5, 8}, the entry's factor (E / r) T_id(c) formed once for all K columns.
+// launch_near_hm's unstaged kernel for mode id: out (stored) = scale * (near field + the
+// sigma_t diagonal when id = 0); fT from launch_prepare
+void launch_near_mode(int K, int id, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
+                      const int* nearPts, const int64_t* nearKOff, const double* E, const double* pxT,
+                      const double* pyT, const double* sigDiag, const double* fT, const int* operm, int64_t obase,
+                      int64_t ldo, double scale, double* out, hipStream_t s);
+// launch_ho_m2l for mode id: mult as launch_ho_p2m / _m2m leave it, local = the plain sums
+void launch_ho_m2l_mode(int np, int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
+                        const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
+                        const double* nry, const HoTables* T, const double* mult, double* local, hipStream_t s);
 
 // ---- cache build and helpers (kernels.hip)
 void launch_cache_m2l(int64_t npairs, const int* pairTgt, const int* src, const double* ncx, const double* ncy,

@@ -1,0 +1,297 @@
+// mode_apply.hip -- one mode applied to K vectors on the mode-shared E caches of a
+// high-order handle (np = 6, 8):
+//     out[k] = sum over sources of (E / r) T_id(c) x[k],   c = cos of the pair's angle.
+//
+// The block kernels (k_near_hm, k_ho_m2l) form K modes of one entry and mix K inputs
+// into them; their offset form serves a single mode of one vector as an 8-row pass that
+// runs both windows' recurrences and keeps one row.  Here the entry's factor
+// (E / r) T_id(c) -- the geometry, 1/r with two Newton steps and one recurrence up to
+// id -- is formed once and applied to the K columns with one FMA each.  There are no
+// harmonic weights: the staged multipole is the P2M's own and the stored local is the
+// plain sum, so P2M, M2M, L2L and L2P of high_order.hip run unchanged around the M2L.
+// Every sum runs in a fixed order and there are no atomics: repeats are bitwise equal.
+#include <hip/hip_runtime.h>
+
+#include <stdexcept>
+#include <string>
+
+#include "device_common.hpp"
+#include "hm_entry.hpp"
+
+namespace aniso {
+
+// (E / r) T_id(c) at (dx, dy^2) from the source (dx: source minus target, as hm_entry
+// takes it; T_id is odd in c for odd id).  id is wave-uniform: the three-term recurrence
+// runs from (T_0, T_1) in a uniform loop.  guard0 as in hm_entry: r = 0 adds E = 0.
+template <bool guard0>
+__device__ __forceinline__ double mode_factor(double e, double dx, double dy2, int id) {
+    double r2 = __builtin_fma(dx, dx, dy2);
+    if constexpr (guard0) r2 = __builtin_fmax(r2, 1e-300);
+    const double ri = rsqrt_nr<2>(r2);
+    const double c = dx * ri, c2 = c + c;
+    double t0 = 1.0, t1 = c;
+#pragma nounroll
+    for (int n = 1; n < id; ++n) {
+        const double t = __builtin_fma(c2, t1, -t0);
+        t0 = t1;
+        t1 = t;
+    }
+    return (e * ri) * (id == 0 ? 1.0 : t1);
+}
+
+// ----------------------------------------------------------------- M2L
+
+// k_ho_m2l for one mode and K columns: one workgroup per target node, thread (row t,
+// column phase ph) of the NPH = 256 / R phases, G columns in flight; a V pair stored once
+// by its smaller id is read transposed through the LDS tile (row stride R + 1); the
+// source's multipole and Chebyshev nodes are staged in LDS per pair; the phases' partial
+// rows are summed through LDS in phase order.
+template <int NP, int K>
+__global__ void __launch_bounds__(256) k_ho_m2l_mode(const int* __restrict__ tgt, const int64_t* __restrict__ ptr,
+                                                     const int* __restrict__ src, const int* __restrict__ blk,
+                                                     const double* __restrict__ E, const double* __restrict__ ncx,
+                                                     const double* __restrict__ ncy, const double* __restrict__ nrx,
+                                                     const double* __restrict__ nry, const HoTables* __restrict__ T,
+                                                     int id, const double* __restrict__ mult,
+                                                     double* __restrict__ local) {
+    constexpr int R = NP * NP, RK = R * K, NPH = 256 / R, NC = (R + NPH - 1) / NPH, LD = R + 1;
+    constexpr int G = NP == 8 ? 4 : 3;  // NC = 16 / 6
+    static_assert(NC % G == 0, "whole column groups");
+    constexpr int TILE = R * LD > NPH * RK ? R * LD : NPH * RK;
+    __shared__ double X[RK], SX[R], SY[R], TL[TILE];
+    const int tid = threadIdx.x, t = tid % R, ph = tid / R;
+    const bool active = ph < NPH;
+    const int n = tgt[blockIdx.x];
+    const double bx = ncx[n] + nrx[n] * T->cheb[t % NP];
+    const double by = ncy[n] + nry[n] * T->cheb[t / NP];
+    double acc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+    const int64_t p0 = ptr[blockIdx.x], p1 = ptr[blockIdx.x + 1];
+    for (int64_t e = p0; e < p1; ++e) {
+        const int B = src[e], b = blk[e];
+        const bool tr = b < 0;
+        const double* Eb = E + (size_t)(tr ? ~b : b) * (R * R);
+        __syncthreads();  // the previous pair's LDS reads are done
+        for (int i = tid; i < RK; i += 256) X[i] = mult[(size_t)B * RK + i];
+        if (tid < R) {
+            SX[tid] = ncx[B] + nrx[B] * T->cheb[tid % NP];
+            SY[tid] = ncy[B] + nry[B] * T->cheb[tid / NP];
+        }
+        if (tr)
+            for (int i = tid; i < R * R; i += 256) TL[(i / R) * LD + (i % R)] = Eb[i];
+        __syncthreads();
+        // G columns in flight per thread (their loads issued together)
+#pragma unroll 1
+        for (int g = 0; g < NC; g += G) {
+            double ev[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const int s = min(ph + NPH * (g + i), R - 1);  // clamped: a valid address, skipped below
+                ev[i] = tr ? TL[t * LD + s] : Eb[s * R + t];
+            }
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const int s = ph + NPH * (g + i);
+                if (active && s < R) {
+                    const double dy = SY[s] - by;
+                    const double f = mode_factor<false>(ev[i], SX[s] - bx, dy * dy, id);
+#pragma unroll
+                    for (int k = 0; k < K; ++k) acc[k] = __builtin_fma(f, X[s * K + k], acc[k]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) TL[(ph * R + t) * K + k] = acc[k];
+    }
+    __syncthreads();
+    for (int i = tid; i < RK; i += 256) {
+        double v = TL[i];
+#pragma unroll
+        for (int p = 1; p < NPH; ++p) v += TL[p * RK + i];
+        local[(size_t)n * RK + i] = v;
+    }
+}
+
+// ----------------------------------------------------------------- near field
+
+// k_near_hm for one mode and K columns: directed E blocks (column-major nT4 x S per
+// target leaf, rows padded to a multiple of 4), G lanes per target leaf (G = 16: leaves
+// <= 16 points, 4 leaves per wave; else 64), lane (row quad rq, column phase) computes
+// rows 4rq .. 4rq+3 for its columns, U = 2 columns in flight; the row loop serves leaves over
+// 256 points.  out (stored, not added) = scale * (sum over sources + the sigma_t
+// diagonal, present for id = 0 only).
+template <int K, int G>
+__global__ void __launch_bounds__(256) k_near_mode(int nl, const int4* __restrict__ leafInfo,
+                                                   const int64_t* __restrict__ nearPtsPtr,
+                                                   const int* __restrict__ nearPts, const int64_t* __restrict__ nearKOff,
+                                                   const double* __restrict__ E, const double* __restrict__ pxT,
+                                                   const double* __restrict__ pyT, const double* __restrict__ sigDiag,
+                                                   int id, const double* __restrict__ fT,
+                                                   const int* __restrict__ operm, int64_t obase, int64_t ldo,
+                                                   double scale, double* __restrict__ out) {
+    static_assert(G == 16 || G == 64, "leaf group of 16 or 64 lanes");
+    // (2 columns in flight, as k_near_hm's offset form: 112 .. 198 VGPRs for K = 2 .. 8; with 4
+    // the 16 entries' 1/r chains take K = 8 to 256 VGPRs, one wave per SIMD)
+    constexpr int KS = kStride<K>, U = 2;
+    const int gl = threadIdx.x & (G - 1);
+    const int li = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G);
+    const bool active = li < nl;
+    int4 info = make_int4(0, 0, 0, 0);
+    int64_t pb = 0, koff = 0;
+    if (active) {
+        info = leafInfo[li];
+        pb = nearPtsPtr[li];
+        koff = nearKOff[li];
+    }
+    const int nT = info.z, S = info.w;
+    const int64_t tb = info.y;
+    const int nq = (nT + 3) >> 2;  // row quads
+    const int cstr = 2 * nq;       // column stride in 16-B units
+    int lpc = 4;                   // lanes per column (G = 16: leaves <= 16 points, 4 quads)
+    if constexpr (G == 64) {
+        lpc = 1;
+        while (lpc < nq && lpc < kWave) lpc <<= 1;
+    }
+    const int cps = G / lpc, cph = gl / lpc;
+    for (int rc = 0; rc < nq || rc == 0; rc += G) {  // > 64 row quads: leaves over 256 points
+        const int rq = rc + (gl & (lpc - 1));
+        const bool rowOk = active && rq < nq;
+        double tx[4], ty[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int t = min(4 * rq + j, max(nT - 1, 0));  // padded rows: E is zero there
+            tx[j] = rowOk ? pxT[tb + t] : 0.0;
+            ty[j] = rowOk ? pyT[tb + t] : 0.0;
+        }
+        double a[4][K];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int k = 0; k < K; ++k) a[j][k] = 0.0;
+        if (rowOk) {
+            const dbl2* kc = reinterpret_cast<const dbl2*>(E + koff) + 2 * rq;
+            for (int c0 = cph; c0 < S; c0 += U * cps) {
+                int ix[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) ix[u] = nearPts[pb + min(c0 + u * cps, S - 1)];
+                dbl2 kk[U][2];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int sc = c0 + u * cps;
+                    const dbl2* p = kc + (size_t)min(sc, S - 1) * cstr;
+                    const bool ok = sc < S;
+                    kk[u][0] = ok ? __builtin_nontemporal_load(p) : dbl2{0.0, 0.0};
+                    kk[u][1] = ok ? __builtin_nontemporal_load(p + 1) : dbl2{0.0, 0.0};
+                }
+                double sx[U], sy[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    sx[u] = pxT[ix[u]];
+                    sy[u] = pyT[ix[u]];
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    double x[K];
+                    load_charges<K>(fT + (size_t)ix[u] * KS, x);
+                    const double e4[4] = {kk[u][0].x, kk[u][0].y, kk[u][1].x, kk[u][1].y};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const double dy = sy[u] - ty[j];
+                        const double f = mode_factor<true>(e4[j], sx[u] - tx[j], dy * dy, id);
+#pragma unroll
+                        for (int k = 0; k < K; ++k) a[j][k] = __builtin_fma(f, x[k], a[j][k]);
+                    }
+                }
+            }
+        }
+        // sum over the column phases
+        if constexpr (G == 16) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    double v = a[j][k];
+                    v += dpp_f64<0x124>(v);  // row_ror:4
+                    v += dpp_f64<0x128>(v);  // row_ror:8
+                    a[j][k] = v;
+                }
+        } else {
+            for (int off = lpc; off < kWave; off <<= 1)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int k = 0; k < K; ++k) a[j][k] += __shfl_xor(a[j][k], off);
+        }
+        if (rowOk) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int t = 4 * rq + j;
+                const bool mine = (G == 16) ? (cph == j) : (cph == 0);
+                if (!mine || t >= nT) continue;
+                const int64_t kp = tb + t;
+                double x[K];
+                load_charges<K>(fT + (size_t)kp * KS, x);
+                const double sd = id == 0 ? sigDiag[kp] : 0.0;
+                const int64_t oi = out_index(operm, obase, kp);
+#pragma unroll
+                for (int k = 0; k < K; ++k) out[(size_t)k * ldo + oi] = scale * __builtin_fma(sd, x[k], a[j][k]);
+            }
+        }
+        if constexpr (G == 16) break;
+    }
+}
+
+// ----------------------------------------------------------------- launchers
+
+#define ANISO_MODE_DISPATCH_K(k, CALL)                                                                \
+    switch (k) {                                                                                      \
+        case 2: { constexpr int KK = 2; CALL; } break;                                                \
+        case 4: { constexpr int KK = 4; CALL; } break;                                                \
+        case 5: { constexpr int KK = 5; CALL; } break;                                                \
+        case 8: { constexpr int KK = 8; CALL; } break;                                                \
+        default:                                                                                      \
+            throw std::invalid_argument("mode apply: unsupported column count " + std::to_string(k)); \
+    }
+
+void launch_near_mode(int K, int id, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
+                      const int* nearPts, const int64_t* nearKOff, const double* E, const double* pxT,
+                      const double* pyT, const double* sigDiag, const double* fT, const int* operm, int64_t obase,
+                      int64_t ldo, double scale, double* out, hipStream_t s) {
+    if (nl <= 0) return;
+    if (id < 0) throw std::invalid_argument("mode apply: negative mode");
+    if (maxLeaf <= 16) {
+        ANISO_MODE_DISPATCH_K(K, (k_near_mode<KK, 16><<<blocks_for((int64_t)nl * 16, 256), 256, 0, s>>>(
+                                     nl, leafInfo, nearPtsPtr, nearPts, nearKOff, E, pxT, pyT, sigDiag, id, fT, operm,
+                                     obase, ldo, scale, out)));
+    } else {
+        ANISO_MODE_DISPATCH_K(K, (k_near_mode<KK, 64><<<blocks_for((int64_t)nl * 64, 256), 256, 0, s>>>(
+                                     nl, leafInfo, nearPtsPtr, nearPts, nearKOff, E, pxT, pyT, sigDiag, id, fT, operm,
+                                     obase, ldo, scale, out)));
+    }
+    HIP_LAUNCH_CHECK();
+}
+
+void launch_ho_m2l_mode(int np, int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
+                        const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
+                        const double* nry, const HoTables* T, const double* mult, double* local, hipStream_t s) {
+    if (ntgt <= 0) return;
+    if (id < 0) throw std::invalid_argument("mode apply: negative mode");
+    if (np == 6) {
+        ANISO_MODE_DISPATCH_K(K, (k_ho_m2l_mode<6, KK><<<ntgt, 256, 0, s>>>(tgt, ptr, src, blk, E, ncx, ncy, nrx, nry, T,
+                                                                           id, mult, local)));
+    } else if (np == 8) {
+        ANISO_MODE_DISPATCH_K(K, (k_ho_m2l_mode<8, KK><<<ntgt, 256, 0, s>>>(tgt, ptr, src, blk, E, ncx, ncy, nrx, nry, T,
+                                                                           id, mult, local)));
+    } else {
+        throw std::invalid_argument("mode apply: np must be 6 or 8");
+    }
+    HIP_LAUNCH_CHECK();
+}
+
+#undef ANISO_MODE_DISPATCH_K
+
+}  // namespace aniso
