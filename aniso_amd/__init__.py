@@ -78,6 +78,9 @@ def lib():
             "aniso_mapping_multi_dev": [P, I, I, P, I64, P, I64, P],
             "aniso_forward_multi_dev": [P, I, P, I64, P, I64, P],
             "aniso_mapping_multi": [P, dp, I, I, dp],
+            "aniso_forward_solve_multi_dev": [P, I, P, I64, I, P, I64, I, D, I, ip, dp, dp, I, P],
+            "aniso_forward_solve_multi": [P, dp, I, I, dp, I, D, I, ip, dp],
+            "aniso_forward_solve_calls": [P, ip, I, ip],
             "aniso_mapping_stages_dev": [P, P, I, I, P, P],
             "aniso_set_shard": [P, I, I],
             "aniso_get_shard": [P, lp, lp],
@@ -380,6 +383,60 @@ class Aniso:
         _check(lib().aniso_forward_multi_dev(self.address, nrhs, px, max(X.stride(0), self.N), po,
                                              max(Out.stride(0), self.N), ctypes.c_void_p(s)))
         return Out
+
+    def forward_solve_multi_dev(self, Q, X, restart=80, tol=1e-12, maxit=5, rhs_is_source=True, stream=None):
+        """main.cpp:121-141 for several sources (aniso_forward_solve_multi_dev): solves
+        u_k - K_0(sigma_s .* u_k) = b_k, b_k = K_0 Q[k] (rhs_is_source) or Q[k], every column a
+        restarted GMRES(restart) of its own, 8 columns per operator pass, on any handle
+        forward_multi_dev accepts.  Q and X are (nrhs, >= N) float64 CUDA tensors as
+        mapping_multi_dev takes them; X holds the guess on entry and the solution on return.
+        Returns (iters, relres, hist): the steps per column (negative: not converged), the
+        last explicit relative residuals, and hist[k, :abs(iters[k])] the estimates after
+        each step of column k (zeros behind them)."""
+        import torch
+
+        nrhs = int(Q.shape[0]) if isinstance(Q, torch.Tensor) and Q.dim() == 2 else -1
+        pq, px = _dev_rows(Q, nrhs, self.N, "Q"), _dev_rows(X, nrhs, self.N, "X")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        maxhist = max(1, min(int(restart) * int(maxit), 100000)) if restart > 0 and maxit > 0 else 1
+        iters = np.zeros(nrhs, dtype=np.int32)
+        relres = np.zeros(nrhs)
+        hist = np.zeros((nrhs, maxhist))
+        _check(lib().aniso_forward_solve_multi_dev(
+            self.address, nrhs, pq, max(Q.stride(0), self.N), int(bool(rhs_is_source)), px, max(X.stride(0), self.N),
+            int(restart), float(tol), int(maxit), iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(relres),
+            _dp(hist), maxhist, ctypes.c_void_p(s)))
+        return iters, relres, hist
+
+    def forward_solve_multi(self, Q, restart=80, tol=1e-12, maxit=5, rhs_is_source=True, x0=None):
+        """The same on numpy arrays (aniso_forward_solve_multi): Q is N x k, one source or
+        right-hand side per column; x0 (N x k) is the initial guess, zero if None.  Returns
+        (X (N x k), iters, relres)."""
+        Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
+        if Q.ndim != 2 or Q.shape[0] != self.N:
+            raise AnisoError(1, f"Q must be N x k with N = {self.N}")
+        if x0 is None:
+            X = np.zeros(Q.shape, order="F")
+        else:
+            X = np.array(x0, dtype=np.float64, order="F")
+            if X.shape != Q.shape:
+                raise AnisoError(1, f"x0 must have Q's shape {Q.shape}")
+        k = Q.shape[1]
+        iters = np.zeros(k, dtype=np.int32)
+        relres = np.zeros(k)
+        _check(lib().aniso_forward_solve_multi(self.address, _dp(Q), k, int(bool(rhs_is_source)), _dp(X), int(restart),
+                                               float(tol), int(maxit),
+                                               iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(relres)))
+        return X, iters, relres
+
+    def forward_solve_calls(self):
+        """The column count of every operator call of the last forward_solve_multi(_dev)."""
+        n = ctypes.c_int()
+        _check(lib().aniso_forward_solve_calls(self.address, None, 0, ctypes.byref(n)))
+        counts = np.zeros(max(n.value, 1), dtype=np.int32)
+        _check(lib().aniso_forward_solve_calls(self.address, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                               n.value, ctypes.byref(n)))
+        return counts[: n.value]
 
     def mapping_dev(self, charge, id_, out, stream=None, mask=STAGE_ALL):
         """charge/out: contiguous float64 torch tensors of N entries on the GPU."""

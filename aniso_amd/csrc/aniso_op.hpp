@@ -227,6 +227,24 @@ public:
                            hipStream_t s);
     int blockSolveHost(const double* rhs, double* x, int restart, double tol, int maxit, double* hist, int maxhist,
                        double* relres);
+    // the multi-source forward solve (main.cpp:121-141 for nrhs sources):
+    // u_k - K_0(sigma_s u_k) = b_k with b_k = K_0 q_k (rhsIsSource) or q_k, every column a
+    // restarted GMRES of its own (blockSolveDev's semantics per column) over modeApplyDev,
+    // in groups of 8 columns that share one operator call per step on the rows still
+    // active.  q / x: device rows of N doubles in original order at strides ldq, ldx >= N;
+    // x: guess in, solution out.  iters / relres (nrhs entries) and hist (row k at k *
+    // maxhist) are host arrays.  Every unsharded handle whose mode 0 is ready.  Returns the
+    // steps of all columns.  forwardSolveMultiCheck raises everything that can be refused
+    // before the device is touched (false: nrhs = 0, nothing to do).
+    bool forwardSolveMultiCheck(const char* what, int nrhs, const void* q, int64_t ldq, const void* x, int64_t ldx,
+                                const int* iters, int restart, double tol, int maxit) const;
+    int forwardSolveMultiDev(int nrhs, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx,
+                             int restart, double tol, int maxit, int* iters, double* relres, double* hist, int maxhist,
+                             hipStream_t s);
+    int forwardSolveMultiHost(const double* Q, int k, bool rhsIsSource, double* X, int restart, double tol, int maxit,
+                              int* iters, double* relres);  // N x k column-major
+    // the column count of every operator call of the last forward solve, in order
+    const std::vector<int>& forwardSolveCalls() const { return solveCalls; }
     // the same solve on a sharded handle with a communicator, every rank together
     // (DESIGN.md §3.17): rhs / x are this rank's owned slices in tree order, ks rows of
     // `owned` doubles at strides ldr / ldx (device).  Every branch is taken from
@@ -472,6 +490,12 @@ private:
     int mixedGroupRun(const double* B, int64_t ldb, double* X, int64_t ldx, int nrows, int m, double tol,
                       double innerTol, int maxOuter, int maxCycles, int* outer, int* longest, double* rel,
                       hipStream_t s);
+    // one group of ng <= 8 columns of the forward solve on the caller's work buffers
+    int forwardSolveGroup(int ng, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx, int m,
+                          double tol, int maxit, int* iters, double* relres, double* hist, int maxhist, double* V,
+                          double* B, double* In, double* W, double* st, double* part, double* dNb, double* hstat,
+                          double* stat, hipEvent_t ev, hipStream_t s);
+    std::vector<int> solveCalls;
     void arnoldiParts(int rows);  // dKryPart for sweeps of `rows` rows
     bool topTraceOn = false;
     int hmRing = 0;  // the cluster M2L's LDS ring depth (ANISO_HM_RING; 0: the one-block-in-flight form)

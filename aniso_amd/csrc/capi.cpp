@@ -239,6 +239,35 @@ int aniso_mapping_multi(aniso_handle h, const double* Q, int k, int id, double* 
     return guarded([&] { get(h).mappingMultiHost(Q, k, id, Out); });
 }
 
+int aniso_forward_solve_multi_dev(aniso_handle h, int nrhs, const double* q, int64_t ldq, int rhs_is_source, double* x,
+                                  int64_t ldx, int restart, double tol, int maxit, int* iters, double* relres,
+                                  double* hist, int maxhist, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        get(h).forwardSolveMultiDev(nrhs, q, ldq, rhs_is_source != 0, x, ldx, restart, tol, maxit, iters, relres,
+                                    maxhist > 0 ? hist : nullptr, maxhist, (hipStream_t)stream);
+    });
+}
+
+int aniso_forward_solve_multi(aniso_handle h, const double* Q, int k, int rhs_is_source, double* X, int restart,
+                              double tol, int maxit, int* iters, double* relres) {
+    ENTER(h);
+    return guarded([&] {
+        get(h).forwardSolveMultiHost(Q, k, rhs_is_source != 0, X, restart, tol, maxit, iters, relres);
+    });
+}
+
+int aniso_forward_solve_calls(aniso_handle h, int* counts, int cap, int* n) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(n);
+        const auto& c = get(h).forwardSolveCalls();
+        *n = (int)c.size();
+        if (counts)
+            for (int i = 0; i < cap && i < (int)c.size(); ++i) counts[i] = c[i];
+    });
+}
+
 int aniso_forward_dev(aniso_handle h, const double* u, double* out, void* stream) {
     ENTER(h);
     return guarded([&] {

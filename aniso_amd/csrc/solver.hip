@@ -15,6 +15,7 @@
 #include "aniso_op.hpp"
 #include "arnoldi.hpp"
 #include "arnoldi16.hpp"
+#include "arnoldi_cols.hpp"
 #include "device_common.hpp"
 #include "kernels.hpp"
 
@@ -1274,6 +1275,315 @@ int Operator::mixedGroupRun(const double* B, int64_t ldb, double* X, int64_t ldx
     if (outerOut) *outerOut = outer;
     if (longest) *longest = longestCycle;
     return inner;
+}
+
+// ---- the multi-source forward solve (main.cpp:121-141 for several
+// sources): u_k - K_0(sigma_s u_k) = b_k, b_k = K_0 q_k or q_k, on every unsharded handle
+// whose mode 0 is ready -- np = 6, 8 and np = 4 lean or resident -- through modeApplyDev.
+// Each column is blockSolveDev's restarted GMRES (DCGS2 Arnoldi, arnoldi.hpp) with a
+// basis, a state block and a convergence of its own; the columns of a group of
+// arn::kMaxCols run in lockstep and share one operator call per step, on exactly the
+// rows still active.
+
+// everything that can be refused before the device is touched (false: nothing to do)
+bool Operator::forwardSolveMultiCheck(const char* what, int nrhs, const void* q, int64_t ldq, const void* x,
+                                      int64_t ldx, const int* iters, int restart, double tol, int maxit) const {
+    const std::string w(what);
+    const int64_t N = geo.N;
+    if (nrhs < 0) throw std::invalid_argument(w + ": nrhs must be >= 0, got " + std::to_string(nrhs));
+    if (ldq < N) throw std::invalid_argument(w + ": ldq = " + std::to_string(ldq) + " is below N = " + std::to_string(N));
+    if (ldx < N) throw std::invalid_argument(w + ": ldx = " + std::to_string(ldx) + " is below N = " + std::to_string(N));
+    if (restart < 1 || restart > 400)
+        throw std::invalid_argument(w + ": restart must be in [1, 400], got " + std::to_string(restart));
+    if (!(tol > 0.0)) throw std::invalid_argument(w + ": tol must be > 0");
+    if (maxit < 0) throw std::invalid_argument(w + ": maxit must be >= 0, got " + std::to_string(maxit));
+    if (nrhs > 0 && !q) throw std::invalid_argument(w + ": q is NULL");
+    if (nrhs > 0 && !x) throw std::invalid_argument(w + ": x is NULL");
+    if (nrhs > 0 && !iters) throw std::invalid_argument(w + ": iters is NULL");
+    if (nrhs == 0) return false;
+    const char* qb = static_cast<const char*>(q);
+    const char* xb = static_cast<const char*>(x);
+    const size_t qs = ((size_t)(nrhs - 1) * ldq + N) * sizeof(double), xs = ((size_t)(nrhs - 1) * ldx + N) * sizeof(double);
+    if (qb < xb + xs && xb < qb + qs) throw std::invalid_argument(w + ": q and x overlap");
+    return modeApplyCheck(what, 0, nrhs, q, ldq, x, ldx, false);  // the handle's state, as aniso_forward_multi_dev
+}
+
+int Operator::forwardSolveMultiDev(int nrhs, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx,
+                                   int restart, double tol, int maxit, int* iters, double* relres, double* hist,
+                                   int maxhist, hipStream_t s) {
+    if (!forwardSolveMultiCheck("aniso_forward_solve_multi_dev", nrhs, q, ldq, x, ldx, iters, restart, tol, maxit))
+        return 0;
+    ensureDevice();
+    checkDeviceErrors();
+    constexpr int G = arn::kMaxCols;
+    const int64_t N = geo.N;
+    const int m = restart, gmax = std::min(nrhs, G);
+    const arn::Layout lay(m);
+    const int64_t sts = lay.total, pc = (int64_t)(m + 2) * arn::kParts, vc = (int64_t)(m + 1) * N;
+    // every buffer of one group, allocated before anything is launched
+    DevBuf bV, bB, bIn, bW, bSt, bPart, bNb;
+    const size_t basis = (size_t)vc * gmax * sizeof(double);
+    const size_t rest = (size_t)(3 * N + sts + pc + 1) * gmax * sizeof(double);
+    try {
+        bV.alloc(basis);
+        bB.alloc((size_t)gmax * N * sizeof(double));
+        bIn.alloc((size_t)gmax * N * sizeof(double));
+        bW.alloc((size_t)gmax * N * sizeof(double));
+        bSt.alloc((size_t)gmax * sts * sizeof(double));
+        bPart.alloc((size_t)gmax * pc * sizeof(double));
+        bNb.alloc((size_t)gmax * sizeof(double));
+    } catch (const std::exception& e) {
+        throw std::runtime_error("forward solve: the Krylov bases of (restart + 1) x " + std::to_string(gmax) + " x N = " +
+                                 std::to_string(m + 1) + " x " + std::to_string(gmax) + " x " + std::to_string(N) +
+                                 " doubles (" + std::to_string(basis) + " bytes) and " + std::to_string(rest) +
+                                 " bytes of work buffers could not be allocated: " + e.what());
+    }
+    // per column {estimate, r', steps, -}, then |b|^2 and |x|^2 per column, in mapped host
+    // memory: the kernels store there and the host waits for an event behind them
+    struct HostStat {
+        double* p = nullptr;
+        hipEvent_t ev = nullptr;
+        ~HostStat() {
+            if (p) (void)hipHostFree(p);
+            if (ev) (void)hipEventDestroy(ev);
+        }
+    } hs;
+    HIP_CHECK(hipHostMalloc((void**)&hs.p, 6 * G * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_CHECK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
+    double* stat = nullptr;
+    HIP_CHECK(hipHostGetDevicePointer((void**)&stat, hs.p, 0));
+    arn_small_kernel_attrs();
+    solveCalls.clear();
+    int steps = 0;
+    try {
+        for (int r0 = 0; r0 < nrhs; r0 += G) {
+            const int ng = std::min(G, nrhs - r0);
+            steps += forwardSolveGroup(ng, q + (size_t)r0 * ldq, ldq, rhsIsSource, x + (size_t)r0 * ldx, ldx, m, tol,
+                                       maxit, iters + r0, relres ? relres + r0 : nullptr,
+                                       hist ? hist + (size_t)r0 * maxhist : nullptr, hist ? maxhist : 0, bV.as<double>(),
+                                       bB.as<double>(), bIn.as<double>(), bW.as<double>(), bSt.as<double>(),
+                                       bPart.as<double>(), bNb.as<double>(), hs.p, stat, hs.ev, s);
+        }
+    } catch (...) {
+        (void)hipStreamSynchronize(s);  // no kernel still writes the buffers freed here
+        throw;
+    }
+    return steps;
+}
+
+// one group of ng <= arn::kMaxCols columns on the buffers of forwardSolveMultiDev
+int Operator::forwardSolveGroup(int ng, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx, int m,
+                                double tol, int maxit, int* iters, double* relres, double* hist, int maxhist, double* V,
+                                double* B, double* In, double* W, double* st, double* part, double* dNb, double* hstat,
+                                double* stat, hipEvent_t ev, hipStream_t s) {
+    constexpr int G = arn::kMaxCols;
+    const int64_t N = geo.N;
+    const arn::Layout lay(m);
+    const int64_t sts = lay.total, pc = (int64_t)(m + 2) * arn::kParts, vc = (int64_t)(m + 1) * N;
+    const arn::ColArgs ca{sts, pc, arn::kParts, 4};
+    const double* sigS = sigmaSTree();
+    const unsigned nb = nblk(N);
+    struct Col {
+        int total = 0, used = 0, nh = 0;
+        bool done = false, conv = false, frozen = false, xzero = false;
+        double normb = 0.0, rel = 0.0, r = 0.0;
+    } col[G];
+    auto wait = [&] {
+        HIP_CHECK(hipEventRecord(ev, s));
+        HIP_CHECK(hipEventSynchronize(ev));
+    };
+    auto slot = [&](int c) {
+        arn::ColSlot sl{};
+        sl.V = V + (size_t)c * vc;
+        sl.b = B + (size_t)c * N;
+        sl.part = part + (size_t)c * pc;
+        sl.st = st + (size_t)c * sts;
+        sl.x = x + (size_t)c * ldx;
+        sl.w = sl.x;
+        return sl;
+    };
+    // f(c0, len) over the maximal runs of consecutive columns in `cols` (ascending): the
+    // small kernels address a launch's columns by a stride
+    auto runs = [&](const std::vector<int>& cols, auto&& f) {
+        for (size_t i = 0; i < cols.size();) {
+            size_t k = i + 1;
+            while (k < cols.size() && cols[k] == cols[k - 1] + 1) ++k;
+            f(cols[i], (int)(k - i));
+            i = k;
+        }
+    };
+    // A on the rows `src` of table t (nrows of them), W's compact rows out: one operator call
+    auto op = [&](const arn::ColTable& t, int nrows, int row, int64_t ldv) {
+        arn::k_arn_gather_cols<<<dim3(nb, nrows), arn::kThreads, 0, s>>>(N, row, ldv, t, In);
+        HIP_LAUNCH_CHECK();
+        modeApplyDev(0, nrows, In, N, sigS, true, W, N, s);
+        solveCalls.push_back(nrows);
+    };
+    // the right-hand sides
+    if (rhsIsSource) modeApplyDev(0, ng, q, ldq, nullptr, false, B, N, s);
+    else
+        HIP_CHECK(hipMemcpy2DAsync(B, N * sizeof(double), q, ldq * sizeof(double), N * sizeof(double), ng,
+                                   hipMemcpyDeviceToDevice, s));
+    {  // |b|^2 and |x|^2 per column
+        arn::ColTable tb{}, tx{};
+        for (int c = 0; c < ng; ++c) {
+            tb.c[c] = slot(c);
+            tb.c[c].V = B + (size_t)c * N;
+            tb.c[c].w = tb.c[c].V;
+            tx.c[c] = slot(c);
+            tx.c[c].V = tx.c[c].x;
+        }
+        arn::launch_project_cols(N, 1, N, tb, ng, s);
+        arn::k_arn_sums_cols<<<ng, arn::kThreads, 0, s>>>(tb, stat + 4 * G);
+        arn::launch_project_cols(N, 1, N, tx, ng, s);
+        arn::k_arn_sums_cols<<<ng, arn::kThreads, 0, s>>>(tx, stat + 5 * G);
+        HIP_LAUNCH_CHECK();
+        wait();
+    }
+    double normbs[G] = {};
+    for (int c = 0; c < ng; ++c) {
+        Col& k = col[c];
+        k.normb = std::sqrt(hstat[4 * G + c]);
+        k.xzero = hstat[5 * G + c] == 0.0;  // A 0 = 0: no operator row for its first residual
+        normbs[c] = k.normb > 0.0 ? k.normb : 1.0;
+        if (!(k.normb > 0.0)) {  // b = 0: x = 0
+            HIP_CHECK(hipMemsetAsync(x + (size_t)c * ldx, 0, N * sizeof(double), s));
+            k.done = k.conv = true;
+        }
+    }
+    HIP_CHECK(hipMemcpyAsync(dNb, normbs, ng * sizeof(double), hipMemcpyHostToDevice, s));
+    // r = b - A x into V[0] of the columns `cols`, and their cycle's start
+    auto residual = [&](const std::vector<int>& cols) {
+        if (cols.empty()) return;
+        arn::ColTable t{}, tg{};
+        int nop = 0;
+        for (size_t a = 0; a < cols.size(); ++a) {
+            const int c = cols[a];
+            t.c[a] = slot(c);
+            if (!col[c].xzero) {
+                tg.c[nop] = t.c[a];
+                tg.c[nop].V = t.c[a].x;
+                t.c[a].w = W + (size_t)nop * N;
+                ++nop;
+            }  // else w = x = 0: r = b
+            hstat[4 * c + 2] = -1.0;
+        }
+        if (nop > 0) op(tg, nop, 0, 0);
+        arn::k_arn_resid_cols<<<dim3(nb, (unsigned)cols.size()), arn::kThreads, 0, s>>>(N, t);
+        HIP_LAUNCH_CHECK();
+        for (size_t a = 0; a < cols.size(); ++a) t.c[a].w = t.c[a].V;
+        arn::launch_project_cols(N, 1, N, t, (int)cols.size(), s);
+        runs(cols, [&](int c0, int len) {
+            arn::k_arn_begin<<<len, arn::kThreads, 0, s>>>(m, st + (size_t)c0 * sts, part + (size_t)c0 * pc, arn::kParts,
+                                                           1.0, stat + 4 * c0, ca, dNb + c0);
+        });
+        HIP_LAUNCH_CHECK();
+        wait();
+        for (int c : cols) {
+            if (hstat[4 * c + 2] != 0.0) throw std::runtime_error("forward solve: a cycle's start left no status");
+            col[c].rel = hstat[4 * c];
+            col[c].r = hstat[4 * c + 1];
+            col[c].conv = col[c].rel <= tol;
+        }
+    };
+    std::vector<int> act, live;
+    for (int c = 0; c < ng; ++c)
+        if (!col[c].done) act.push_back(c);
+    residual(act);
+    for (int cyc = 0; cyc < maxit; ++cyc) {
+        act.clear();
+        for (int c = 0; c < ng; ++c)
+            if (!col[c].done && !col[c].conv && col[c].r != 0.0) act.push_back(c);
+        if (act.empty()) break;
+        for (int c : act) {
+            col[c].used = 0;
+            col[c].frozen = false;
+        }
+        for (int j = 0; j < m; ++j) {
+            live.clear();
+            for (int c : act)
+                if (!col[c].frozen) live.push_back(c);
+            if (live.empty()) break;
+            const int nl = (int)live.size();
+            arn::ColTable t{};
+            for (int a = 0; a < nl; ++a) {
+                t.c[a] = slot(live[a]);
+                t.c[a].w = W + (size_t)a * N;
+                hstat[4 * live[a] + 2] = -1.0;
+            }
+            op(t, nl, j, N);
+            arn::launch_project_cols(N, j + 1, N, t, nl, s);
+            runs(live, [&](int c0, int len) {
+                arn::k_arn_coef<<<len, arn::kThreads, arn::coef_lds(j), s>>>(m, j, st + (size_t)c0 * sts,
+                                                                              part + (size_t)c0 * pc, arn::kParts, ca);
+            });
+            HIP_LAUNCH_CHECK();
+            arn::launch_update_cols(N, j + 1, N, m, t, nl, s);
+            runs(live, [&](int c0, int len) {
+                arn::k_arn_column<<<len, arn::kThreads, arn::column_lds(j), s>>>(
+                    m, j, st + (size_t)c0 * sts, part + (size_t)c0 * pc, arn::kParts, stat + 4 * c0, ca);
+            });
+            HIP_LAUNCH_CHECK();
+            wait();
+            for (int c : live) {
+                Col& k = col[c];
+                if (hstat[4 * c + 2] != (double)(j + 1))
+                    throw std::runtime_error("forward solve: Arnoldi step " + std::to_string(j) + " left no status");
+                const double rel = hstat[4 * c], rnext = hstat[4 * c + 1];
+                ++k.total;
+                k.used = j + 1;
+                if (hist && k.nh < maxhist) hist[(size_t)c * maxhist + k.nh++] = rel;
+                k.frozen = rel <= tol || rnext == 0.0;  // converged (estimate) or lucky breakdown
+            }
+        }
+        // x += P T R^-1 g, every column with its own row count
+        arn::ColTable tu{};
+        int nu = 0, maxUsed = 0;
+        for (int c : act)
+            if (col[c].used > 0) {
+                arn::k_arn_solve<<<1, arn::kThreads, arn::solve_lds(col[c].used), s>>>(m, col[c].used,
+                                                                                        st + (size_t)c * sts);
+                tu.c[nu] = slot(c);
+                tu.c[nu].used = col[c].used;
+                maxUsed = std::max(maxUsed, col[c].used);
+                col[c].xzero = false;
+                ++nu;
+            }
+        HIP_LAUNCH_CHECK();
+        if (nu > 0) {
+            arn::k_arn_axpy_cols<<<dim3(nb, nu), arn::kThreads, (size_t)maxUsed * sizeof(double), s>>>(N, N, m, tu);
+            HIP_LAUNCH_CHECK();
+        }
+        residual(act);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    checkDeviceErrors();
+    int steps = 0;
+    for (int c = 0; c < ng; ++c) {
+        const Col& k = col[c];
+        iters[c] = k.conv ? k.total : -std::max(k.total, 1);
+        if (relres) relres[c] = k.rel;
+        steps += k.total;
+    }
+    return steps;
+}
+
+// N x k column-major host arrays: one staging copy each way
+int Operator::forwardSolveMultiHost(const double* Q, int k, bool rhsIsSource, double* X, int restart, double tol,
+                                    int maxit, int* iters, double* relres) {
+    if (!forwardSolveMultiCheck("aniso_forward_solve_multi", k, Q, geo.N, X, geo.N, iters, restart, tol, maxit)) return 0;
+    ensureDevice();
+    const size_t bytes = (size_t)k * geo.N * sizeof(double);
+    DevBuf dq, dx;
+    dq.alloc(bytes);
+    dx.alloc(bytes);
+    HIP_CHECK(hipMemcpyAsync(dq.p, Q, bytes, hipMemcpyHostToDevice, own));
+    HIP_CHECK(hipMemcpyAsync(dx.p, X, bytes, hipMemcpyHostToDevice, own));
+    const int steps = forwardSolveMultiDev(k, dq.as<double>(), geo.N, rhsIsSource, dx.as<double>(), geo.N, restart, tol,
+                                           maxit, iters, relres, nullptr, 0, own);
+    HIP_CHECK(hipMemcpyAsync(X, dx.p, bytes, hipMemcpyDeviceToHost, own));
+    HIP_CHECK(hipStreamSynchronize(own));
+    return steps;
 }
 
 // the same on host pointers (the MEX shim's 'solve' op): one staging copy each way
