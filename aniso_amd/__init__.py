@@ -80,6 +80,10 @@ def lib():
             "aniso_mapping_multi": [P, dp, I, I, dp],
             "aniso_forward_solve_multi_dev": [P, I, P, I64, I, P, I64, I, D, I, ip, dp, dp, I, P],
             "aniso_forward_solve_multi": [P, dp, I, I, dp, I, D, I, ip, dp],
+            "aniso_block_op_multi_dev": [P, I, I, P, I64, P, I64, P],
+            "aniso_block_op_multi": [P, I, dp, I, dp],
+            "aniso_block_solve_multi_dev": [P, I, P, I64, I, P, I64, I, D, I, ip, dp, dp, I, P],
+            "aniso_block_solve_multi": [P, dp, I, I, dp, I, D, I, ip, dp],
             "aniso_forward_solve_calls": [P, ip, I, ip],
             "aniso_mapping_stages_dev": [P, P, I, I, P, P],
             "aniso_set_shard": [P, I, I],
@@ -430,7 +434,9 @@ class Aniso:
         return X, iters, relres
 
     def forward_solve_calls(self):
-        """The column count of every operator call of the last forward_solve_multi(_dev)."""
+        """The column count of every operator call of the last forward_solve_multi(_dev), or the
+        source count of every one of the last block_solve_multi(_dev), each group's
+        forward(charge) call first."""
         n = ctypes.c_int()
         _check(lib().aniso_forward_solve_calls(self.address, None, 0, ctypes.byref(n)))
         counts = np.zeros(max(n.value, 1), dtype=np.int32)
@@ -641,6 +647,91 @@ class Aniso:
         out = np.zeros(self.ks * self.N)
         _check(lib().aniso_block_op(self.address, int(which), _dp(u), _dp(out)))
         return out.reshape(self.ks, self.N)
+
+    # ---- the block operator and its solve for several sources
+    def _src_rows(self, t, name):
+        """(nsrc, pointer) of a (nsrc * ks, >= N) float64 CUDA tensor: row s * ks + b is block
+        b of source s."""
+        import torch
+
+        rows = int(t.shape[0]) if isinstance(t, torch.Tensor) and t.dim() == 2 else -1
+        if rows >= 0 and rows % self.ks:
+            raise AnisoError(1, f"{name} must have nsrc * ks rows with ks = {self.ks}, got {rows}")
+        return rows // self.ks if rows >= 0 else -1, _dev_rows(t, rows, self.N, name)
+
+    def block_op_multi_dev(self, which, X, Out, stream=None):
+        """aniso.m's forward (0) / mforward (1) / x - mforward(x) (2) for several sources in one
+        medium (aniso_block_op_multi_dev).  X and Out are (nsrc * ks, >= N) float64 CUDA tensors
+        with unit column stride (strided rows allowed; entries past N of a row are left alone),
+        row s * ks + b = block b of source s; they must not overlap.  np = 6, 8 with ks <= 8:
+        4 sources per read of the M2L blocks; np = 4 or ks > 8: one block_op_dev per source."""
+        import torch
+
+        nsrc, px = self._src_rows(X, "X")
+        _, po = self._src_rows(Out, "Out")
+        if nsrc >= 0 and Out.shape[0] != X.shape[0]:
+            raise AnisoError(1, f"Out must have X's {X.shape[0]} rows")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _check(lib().aniso_block_op_multi_dev(self.address, int(which), nsrc, px, max(X.stride(0), self.N), po,
+                                              max(Out.stride(0), self.N), ctypes.c_void_p(s)))
+        return Out
+
+    def block_op_multi(self, which, U):
+        """The same on numpy arrays (aniso_block_op_multi): U is (ks * N) x nsrc, one source per
+        column with its blocks stacked as block_op takes them; returns an array of U's shape."""
+        U = np.asfortranarray(np.asarray(U, dtype=np.float64))
+        if U.ndim != 2 or U.shape[0] != self.ks * self.N:
+            raise AnisoError(1, f"U must be (ks * N) x nsrc with ks * N = {self.ks * self.N}")
+        out = np.zeros(U.shape, order="F")
+        _check(lib().aniso_block_op_multi(self.address, int(which), _dp(U), U.shape[1], _dp(out)))
+        return out
+
+    def block_solve_multi_dev(self, Q, X, restart=80, tol=1e-11, maxit=5, rhs_is_charge=True, stream=None):
+        """aniso.m:159-173 for several charges in one medium (aniso_block_solve_multi_dev):
+        b_s = forward(Q_s) (rhs_is_charge) or Q_s, then block_solve's restarted GMRES of
+        x - mforward(x) per source, 4 sources per operator pass.  Q and X are tensors as
+        block_op_multi_dev takes them; X holds the guesses on entry and the solutions on return.
+        Returns (iters, relres, hist): the steps per source (negative: not converged), the last
+        explicit relative residuals, and hist[s, :abs(iters[s])] the estimates after each step
+        of source s (zeros behind them)."""
+        import torch
+
+        nsrc, pq = self._src_rows(Q, "Q")
+        _, px = self._src_rows(X, "X")
+        if nsrc >= 0 and X.shape[0] != Q.shape[0]:
+            raise AnisoError(1, f"X must have Q's {Q.shape[0]} rows")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        maxhist = max(1, min(int(restart) * int(maxit), 100000)) if restart > 0 and maxit > 0 else 1
+        n = max(nsrc, 0)
+        iters = np.zeros(n, dtype=np.int32)
+        relres = np.zeros(n)
+        hist = np.zeros((n, maxhist))
+        _check(lib().aniso_block_solve_multi_dev(
+            self.address, nsrc, pq, max(Q.stride(0), self.N), int(bool(rhs_is_charge)), px, max(X.stride(0), self.N),
+            int(restart), float(tol), int(maxit), iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(relres),
+            _dp(hist), maxhist, ctypes.c_void_p(s)))
+        return iters, relres, hist
+
+    def block_solve_multi(self, Q, restart=80, tol=1e-11, maxit=5, rhs_is_charge=True, x0=None):
+        """The same on numpy arrays (aniso_block_solve_multi): Q is (ks * N) x nsrc, one charge
+        or right-hand side per column; x0 (Q's shape) holds the initial guesses, zero if None.
+        Returns (X of Q's shape, iters, relres)."""
+        Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
+        if Q.ndim != 2 or Q.shape[0] != self.ks * self.N:
+            raise AnisoError(1, f"Q must be (ks * N) x nsrc with ks * N = {self.ks * self.N}")
+        if x0 is None:
+            X = np.zeros(Q.shape, order="F")
+        else:
+            X = np.array(x0, dtype=np.float64, order="F")
+            if X.shape != Q.shape:
+                raise AnisoError(1, f"x0 must have Q's shape {Q.shape}")
+        k = Q.shape[1]
+        iters = np.zeros(k, dtype=np.int32)
+        relres = np.zeros(k)
+        _check(lib().aniso_block_solve_multi(self.address, _dp(Q), k, int(bool(rhs_is_charge)), _dp(X), int(restart),
+                                             float(tol), int(maxit),
+                                             iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(relres)))
+        return X, iters, relres
 
     # ---- direct evaluation at chosen targets (DESIGN.md "Accuracy of the method")
     def mapping_direct(self, charge, id_, targets):

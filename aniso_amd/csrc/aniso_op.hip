@@ -1941,6 +1941,175 @@ void Operator::blockOpHost(int which, const double* u, const double* sigmaS, dou
     checkDeviceErrors();
 }
 
+// ---- the block operator for several sources ----
+
+bool Operator::blockOpMultiCheck(const char* what, int which, int nsrc, const void* x, int64_t ldx, const void* out,
+                                 int64_t ldo) const {
+    const std::string w(what);
+    const int64_t N = geo.N;
+    if (nsrc < 0) throw std::invalid_argument(w + ": nsrc must be >= 0, got " + std::to_string(nsrc));
+    if (which < 0 || which > 2) throw std::invalid_argument(w + ": which must be 0, 1 or 2, got " + std::to_string(which));
+    if (ldx < N) throw std::invalid_argument(w + ": the input stride " + std::to_string(ldx) + " is below N = " + std::to_string(N));
+    if (ldo < N) throw std::invalid_argument(w + ": the output stride " + std::to_string(ldo) + " is below N = " + std::to_string(N));
+    if (nsrc > 0 && !x) throw std::invalid_argument(w + ": the input is NULL");
+    if (nsrc > 0 && !out) throw std::invalid_argument(w + ": the output is NULL");
+    if (nsrc == 0) return false;
+    {  // a source's near field stores its output rows before the next source's input rows are read
+        const char* xb = static_cast<const char*>(x);
+        const char* ob = static_cast<const char*>(out);
+        const size_t rows = (size_t)nsrc * ks - 1;
+        const size_t xs = (rows * ldx + N) * sizeof(double), os = (rows * ldo + N) * sizeof(double);
+        if (xb < ob + os && ob < xb + xs) throw std::invalid_argument(w + ": the input and output rows overlap");
+    }
+    if (plan.nranks > 1)
+        throw std::logic_error(w + " on a sharded handle: it writes every target (use an unsharded handle)");
+    if (!coeffSet) throw std::runtime_error(w + " before aniso_set_coeff and aniso_cache_block");
+    const bool shared = useAtt && attReady && plan.nearPartTotal == 0;  // the mode-shared caches serve a lean mode
+    for (int m = 0; m < 2 * ks - 1; ++m) {
+        const ModeCache& mc = modes[m];
+        if (!mc.tables || !(highOrder() ? attReady : (mc.resident || shared)))
+            throw std::runtime_error(w + " before mode " + std::to_string(m) + " of 0 .. " + std::to_string(2 * ks - 2) +
+                                     " is ready: call aniso_cache_block (or aniso_cache for every mode)");
+    }
+    return true;
+}
+
+// the chunk's buffers for S sources: S multipole and S local buffers beside dHoMult / dHoLocal,
+// and the rows of a block count that is not compiled padded with zero blocks
+void Operator::blockMultiReserve(int S) {
+    const int K = ks == 1 ? 2 : rhs_padded(ks);
+    const size_t exp = (size_t)S * tree.nn * np * np * K * sizeof(double);
+    ensureWork(K);
+    if (dMsMult.bytes < exp) dMsMult.alloc(exp);
+    if (dMsLocal.bytes < exp) dMsLocal.alloc(exp);
+    if (K != ks) {
+        const size_t pad = (size_t)S * K * geo.N * sizeof(double);
+        if (dMsIn.bytes < pad) dMsIn.alloc(pad);
+        if (dMsOut.bytes < pad) dMsOut.alloc(pad);
+    }
+}
+
+// One chunk on a high-order handle: applyBlockHigh's launch sequence with launch_prepare, the
+// near field, the corrections, P2M and M2M per source (each into its own multipole buffer),
+// ONE M2L launch for the chunk, then L2L and L2P per source, the last writer of its rows
+// (which = 2: x - mforward(x) through the L2P's minuend).  An absent source (nreal < S) is a
+// zero multipole buffer whose locals nobody reads.
+void Operator::blockMultiChunk(int which, int S, int nreal, const double* x, int64_t ldx, double* out, int64_t ldo,
+                               hipStream_t s) {
+    const int nb = ks, nm = 2 * ks - 1, K = nb == 1 ? 2 : rhs_padded(nb);
+    const int64_t N = geo.N;
+    std::vector<double> mix = blockMixes(nb, g, which != 0);
+    if (K != nb) mix = padMixes(nb, K, nm, mix.data());
+    const std::vector<int> ids = modeIds(nm);
+    HarmWeights hw;
+    if (!harmonicWeights(K, nm, ids.data(), mix.data(), hw))
+        throw std::logic_error("multi-source block operator: the mode-shared caches are not ready");
+    const double* sigT = which != 0 ? dSigmaT.as<double>() : nullptr;
+    const Params* P = dParams.as<Params>();
+    const HoTables* T = dHoTab.as<HoTables>();
+    blockMultiReserve(S);
+    const size_t exp = (size_t)tree.nn * np * np * K;  // doubles of one expansion buffer
+    const CorrFold& cf = corrTable(K, nm, ids.data(), mix.data());
+    const bool padded = K != nb;
+    auto xin = [&](int j) { return padded ? dMsIn.as<double>() + (size_t)j * K * N : x + (size_t)j * nb * ldx; };
+    auto xout = [&](int j) { return padded ? dMsOut.as<double>() + (size_t)j * K * N : out + (size_t)j * nb * ldo; };
+    const int64_t ldi = padded ? N : ldx, ldw = padded ? N : ldo;  // the strides of xin / xout
+    const bool tr = timeStages != 0, tm = timeStages == 1;
+    auto span = [&](int stage, int a, int b) {
+        if (a >= 0 && b >= 0) spans.push_back({stage, a, b});
+    };
+    const int* operm = dPerm.as<int>();
+    const double scale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
+    const int nl = (int)plan.leaves.size();
+    const int e0 = tr ? mark(s) : -1;
+    if (padded) {
+        HIP_CHECK(hipMemsetAsync(dMsIn.p, 0, (size_t)nreal * K * N * sizeof(double), s));
+        for (int j = 0; j < nreal; ++j)
+            HIP_CHECK(hipMemcpy2DAsync(dMsIn.as<double>() + (size_t)j * K * N, N * sizeof(double), x + (size_t)j * nb * ldx,
+                                       ldx * sizeof(double), N * sizeof(double), nb, hipMemcpyDeviceToDevice, s));
+    }
+    // nodes that are no M2L target (the root, empty nodes) keep zero locals
+    HIP_CHECK(hipMemsetAsync(dMsLocal.p, 0, (size_t)S * exp * sizeof(double), s));
+    if (nreal < S)
+        HIP_CHECK(hipMemsetAsync(dMsMult.as<double>() + (size_t)nreal * exp, 0, (size_t)(S - nreal) * exp * sizeof(double), s));
+    for (int j = 0; j < nreal; ++j) {
+        double* mj = dMsMult.as<double>() + (size_t)j * exp;
+        const int a0 = tr ? mark(s) : -1;
+        launch_prepare(K, N, xin(j), ldi, 0, dPerm.as<int>(), sigT, dWT.as<double>(), dFT.as<double>(), dCT.as<double>(), s);
+        launch_near_hm(K, nl, plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(),
+                       dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
+                       dSigDiag.as<double>(), hw, dFT.as<double>(), operm, 0, ldw, kStageAll, scale, xout(j), nullptr,
+                       nullptr, nullptr, 0, nullptr, nearWpe, s, nullptr, nullptr);
+        const int a1 = tr ? mark(s) : -1;
+        span(4, a0, a1);
+        launch_corr(K, geo.d, plan.ownBegin, plan.ownEnd, dPerm.as<int>(), dIperm.as<int>(), dCT.as<double>(),
+                    dFT.as<double>(), cf.Wc.as<double>(), cf.Wm.as<double>(), P, kStageAll, scale, false, ldw, xout(j), s);
+        const int a2 = tr ? mark(s) : -1;
+        if (tm) span(6, a1, a2);
+        launch_ho_p2m(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
+                      dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), dFT.as<double>(), T, mj, s);
+        for (size_t l = 0; l + 1 < hoM2mPtr.size(); ++l)
+            launch_ho_m2m(np, K, hoM2mPtr[l + 1] - hoM2mPtr[l], dHoM2m.as<int>() + hoM2mPtr[l], dHoChild.as<int4>(), T, mj,
+                          s);
+        if (tm) span(1, a2, mark(s));
+    }
+    const int e3 = tr ? mark(s) : -1;
+    launch_ho_m2l_src(np, K, S, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
+                      dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
+                      dNry.as<double>(), T, hw, dMsMult.as<double>(), (int64_t)exp, dMsLocal.as<double>(), (int64_t)exp, s);
+    const int e4 = tr ? mark(s) : -1;
+    span(2, e3, e4);
+    for (int j = 0; j < nreal; ++j) {
+        double* lj = dMsLocal.as<double>() + (size_t)j * exp;
+        for (size_t l = 0; l + 1 < hoL2lPtr.size(); ++l)
+            launch_ho_l2l(np, K, hoL2lPtr[l + 1] - hoL2lPtr[l], dHoL2l.as<int>() + hoL2lPtr[l], dParent.as<int>(),
+                          dSlot.as<int>(), T, lj, s);
+        launch_ho_l2p(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
+                      dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), T, lj, operm, 0, ldw, scale, xout(j),
+                      which == 2 ? xin(j) : nullptr, ldi, s);
+        if (padded)
+            HIP_CHECK(hipMemcpy2DAsync(out + (size_t)j * nb * ldo, ldo * sizeof(double), xout(j), N * sizeof(double),
+                                       N * sizeof(double), nb, hipMemcpyDeviceToDevice, s));
+    }
+    if (tr) {
+        const int e5 = mark(s);
+        if (tm) span(5, e4, e5);
+        span(7, e0, e5);
+        ++applies;
+    }
+}
+
+void Operator::blockOpMultiDev(int which, int nsrc, const double* x, int64_t ldx, double* out, int64_t ldo,
+                               hipStream_t s) {
+    if (!blockOpMultiCheck("multi-source block operator", which, nsrc, x, ldx, out, ldo)) return;
+    checkDeviceErrors();
+    ensureDevice();
+    if (!highOrder() || ks > kMaxRhs) {  // nothing shared: the existing operator per source
+        for (int j = 0; j < nsrc; ++j)
+            blockOpDev(which, x + (size_t)j * ks * ldx, ldx, out + (size_t)j * ks * ldo, ldo, false, s);
+        return;
+    }
+    for (int j0 = 0; j0 < nsrc; j0 += 4) {
+        const int n = std::min(4, nsrc - j0);
+        blockMultiChunk(which, n == 3 ? 4 : n, n, x + (size_t)j0 * ks * ldx, ldx, out + (size_t)j0 * ks * ldo, ldo, s);
+    }
+}
+
+// (ks N) x nsrc column-major host arrays: one staging copy each way
+void Operator::blockOpMultiHost(int which, const double* U, int nsrc, double* Out) {
+    if (!blockOpMultiCheck("aniso_block_op_multi", which, nsrc, U, geo.N, Out, geo.N)) return;
+    ensureDevice();
+    const size_t bytes = (size_t)nsrc * ks * geo.N * sizeof(double);
+    DevBuf du, dout;
+    du.alloc(bytes);
+    dout.alloc(bytes);
+    HIP_CHECK(hipMemcpyAsync(du.p, U, bytes, hipMemcpyHostToDevice, own));
+    blockOpMultiDev(which, nsrc, du.as<double>(), geo.N, dout.as<double>(), geo.N, own);
+    HIP_CHECK(hipMemcpyAsync(Out, dout.p, bytes, hipMemcpyDeviceToHost, own));
+    HIP_CHECK(hipStreamSynchronize(own));
+    checkDeviceErrors();
+}
+
 // ---- direct evaluation at chosen targets (direct.hip) ----
 //
 // The direct sum over all N sources gives the near field a one-leaf tree would compute;

@@ -245,6 +245,37 @@ public:
                               int* iters, double* relres);  // N x k column-major
     // the column count of every operator call of the last forward solve, in order
     const std::vector<int>& forwardSolveCalls() const { return solveCalls; }
+    // --- the block operator and its solve for several sources (aniso.m:121-173
+    // for nsrc charges in one medium).  x / out: nsrc * ks device rows of N doubles in original
+    // order at strides ldx, ldo >= N, row s * ks + b = block b of source s; `which` as blockOpDev's.
+    // x and out must not overlap.  Unsharded handles with every mode 0 .. 2 ks - 2 ready.
+    // np = 6, 8 and ks <= 8: the sources run in chunks of 4 (a remainder of 3 zero-padded to 4, of
+    // 2 and 1 on the 2- and 1-source instances) through ONE M2L launch per chunk that reads every
+    // stored E block once for all its sources (block_multi.hip); the near field, the corrections
+    // and the up and down passes run per source on blockOpDev's launches.  np = 4 (cached or lean)
+    // or ks > 8: ONE blockOpDev PER SOURCE -- correct, nothing shared.  A source's output bits do
+    // not depend on how many sources the call has, which ones, or its position among them.
+    // blockOpMultiCheck raises everything that can be refused before the device is touched
+    // (false: nsrc = 0, nothing to do).
+    bool blockOpMultiCheck(const char* what, int which, int nsrc, const void* x, int64_t ldx, const void* out,
+                           int64_t ldo) const;
+    void blockOpMultiDev(int which, int nsrc, const double* x, int64_t ldx, double* out, int64_t ldo, hipStream_t s);
+    void blockOpMultiHost(int which, const double* U, int nsrc, double* Out);  // (ks N) x nsrc column-major
+    // aniso.m:159-173 per source: b_s = forward(q_s) (rhsIsCharge, aniso.m:160) or q_s, then
+    // blockSolveDev's restarted GMRES of x - mforward(x) on the source's ks * N vector.  Groups of
+    // 4 sources run in lockstep (forwardSolveMultiDev's scheme at row length ks * N) and share one
+    // blockOpMultiDev(2, ...) per step on exactly the sources still active.  q / x as
+    // blockOpMultiDev's rows; x: guess in, solution out (untouched if the work buffers cannot be
+    // allocated); iters / relres (nsrc) and hist (row s at s * maxhist) are host arrays.  Every
+    // buffer is allocated before the first launch and freed on return.  Returns the steps of all
+    // sources; the source count of every operator call is left in forwardSolveCalls().
+    bool blockSolveMultiCheck(const char* what, int nsrc, const void* q, int64_t ldq, const void* x, int64_t ldx,
+                              const int* iters, int restart, double tol, int maxit) const;
+    int blockSolveMultiDev(int nsrc, const double* q, int64_t ldq, bool rhsIsCharge, double* x, int64_t ldx,
+                           int restart, double tol, int maxit, int* iters, double* relres, double* hist, int maxhist,
+                           hipStream_t s);
+    int blockSolveMultiHost(const double* Q, int nsrc, bool rhsIsCharge, double* X, int restart, double tol, int maxit,
+                            int* iters, double* relres);  // (ks N) x nsrc column-major
     // the same solve on a sharded handle with a communicator, every rank together
     // (DESIGN.md §3.17): rhs / x are this rank's owned slices in tree order, ks rows of
     // `owned` doubles at strides ldr / ldx (device).  Every branch is taken from
@@ -430,6 +461,13 @@ private:
     DevBuf dHoTab, dHoChild, dHoM2m, dHoL2l, dHoMult, dHoLocal;
     std::vector<int> hoM2mPtr, hoL2lPtr;  // per level: its range of dHoM2m (bottom-up) / dHoL2l (top-down)
     int hoWorkK = 0;
+    // blockOpMultiDev's chunk of S in {1, 2, 4} sources (nreal of them present, the rest zero)
+    // on a high-order handle: its S multipole and S local buffers, and the chunk's rows padded
+    // to the compiled block count (grown, never shrunk: a hipFree synchronises the device)
+    void blockMultiChunk(int which, int S, int nreal, const double* x, int64_t ldx, double* out, int64_t ldo,
+                         hipStream_t s);
+    void blockMultiReserve(int S);
+    DevBuf dMsMult, dMsLocal, dMsIn, dMsOut;
     // mapping of a mode whose operators are not resident: one pass of the offset form
     // (sigT: tree-order sigma_s multiplied into the charge by the pass's launch_prepare)
     void leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask, const double* sigT = nullptr);
@@ -490,6 +528,19 @@ private:
     int mixedGroupRun(const double* B, int64_t ldb, double* X, int64_t ldx, int nrows, int m, double tol,
                       double innerTol, int maxOuter, int maxCycles, int* outer, int* longest, double* rel,
                       hipStream_t s);
+    // One group of ng <= arn::kMaxCols independent columns of row length L in lockstep, the loop
+    // the forward solve and the multi-source block solve share: B holds the right-hand sides
+    // (compact rows of L), x the guesses / solutions (rows at stride ldx), A(nrows, In, W) is one
+    // operator call on nrows compact rows.  `what` names the solve in its error messages.
+    struct ColsSolve {
+        int64_t L;
+        const char* what;
+        std::function<void(int, const double*, double*)> A;
+    };
+    int colsSolveGroup(const ColsSolve& cs, int ng, double* x, int64_t ldx, int m, double tol, int maxit, int* iters,
+                       double* relres, double* hist, int maxhist, double* V, double* B, double* In, double* W,
+                       double* st, double* part, double* dNb, double* hstat, double* stat, hipEvent_t ev,
+                       hipStream_t s);
     // one group of ng <= 8 columns of the forward solve on the caller's work buffers
     int forwardSolveGroup(int ng, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx, int m,
                           double tol, int maxit, int* iters, double* relres, double* hist, int maxhist, double* V,

@@ -257,6 +257,39 @@ int aniso_forward_solve_multi(aniso_handle h, const double* Q, int k, int rhs_is
     });
 }
 
+int aniso_block_op_multi_dev(aniso_handle h, int which, int nsrc, const double* x, int64_t ldx, double* out,
+                             int64_t ldo, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        auto& op = get(h);
+        if (!op.blockOpMultiCheck("aniso_block_op_multi_dev", which, nsrc, x, ldx, out, ldo)) return;
+        op.blockOpMultiDev(which, nsrc, x, ldx, out, ldo, (hipStream_t)stream);
+    });
+}
+
+int aniso_block_op_multi(aniso_handle h, int which, const double* U, int nsrc, double* Out) {
+    ENTER(h);
+    return guarded([&] { get(h).blockOpMultiHost(which, U, nsrc, Out); });
+}
+
+int aniso_block_solve_multi_dev(aniso_handle h, int nsrc, const double* q, int64_t ldq, int rhs_is_charge, double* x,
+                                int64_t ldx, int restart, double tol, int maxit, int* iters, double* relres,
+                                double* hist, int maxhist, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        get(h).blockSolveMultiDev(nsrc, q, ldq, rhs_is_charge != 0, x, ldx, restart, tol, maxit, iters, relres,
+                                  maxhist > 0 ? hist : nullptr, maxhist, (hipStream_t)stream);
+    });
+}
+
+int aniso_block_solve_multi(aniso_handle h, const double* Q, int nsrc, int rhs_is_charge, double* X, int restart,
+                            double tol, int maxit, int* iters, double* relres) {
+    ENTER(h);
+    return guarded([&] {
+        get(h).blockSolveMultiHost(Q, nsrc, rhs_is_charge != 0, X, restart, tol, maxit, iters, relres);
+    });
+}
+
 int aniso_forward_solve_calls(aniso_handle h, int* counts, int cap, int* n) {
     ENTER(h);
     return guarded([&] {

@@ -127,4 +127,33 @@ __device__ __forceinline__ void hm_rows_win(const double (&e)[J], const double (
         for (int j = 0; j < J; ++j) o[j][i] = __builtin_fma(step(j), v[j], o[j][i]);
 }
 
+// One entry for S sources and the whole operator (i0 = b0 = 0, at most kMaxRhs blocks;
+// DESIGN.md §3.18.3).  What does not depend on the source -- r^2, 1/r, c, T_0 .. T_{K-1}
+// and E / r -- is formed once; per source s
+//     V_s = (E / r) sum_b T_b(c) xw[s][b],   o[s][i] += T_i(c) V_s.
+// A source's chain is hm_rows_win's at i0 = b0 = 0 with one row, operation by operation,
+// and reads nothing of another source: its bits depend neither on S nor on its slot.
+template <int K, int S, int NR = 2>
+__device__ __forceinline__ void hm_rows_src(double e, double dx, double dy2, const double (&xw)[S][K],
+                                            double (&o)[S][K]) {
+    static_assert(K >= 2, "at least T_0 and T_1");
+    const double r2 = __builtin_fma(dx, dx, dy2);
+    const double ri = rsqrt_nr<NR>(r2);
+    const double c = dx * ri, c2 = c + c, er = e * ri;
+    double T[K];
+    T[0] = 1.0;
+    T[1] = c;
+#pragma unroll
+    for (int i = 2; i < K; ++i) T[i] = __builtin_fma(c2, T[i - 1], -T[i - 2]);
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        double v = __builtin_fma(T[1], xw[s][1], T[0] * xw[s][0]);
+#pragma unroll
+        for (int b = 2; b < K; ++b) v = __builtin_fma(T[b], xw[s][b], v);
+        v *= er;  // (E / r) V
+#pragma unroll
+        for (int i = 0; i < K; ++i) o[s][i] = __builtin_fma(T[i], v, o[s][i]);
+    }
+}
+
 }  // namespace aniso

@@ -434,6 +434,14 @@ void launch_near_mode(int K, int id, int nl, int maxLeaf, const int4* leafInfo, 
 void launch_ho_m2l_mode(int np, int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
                         const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
                         const double* nry, const HoTables* T, const double* mult, double* local, hipStream_t s);
+// ---- the block operator for S sources per read of the E blocks (block_multi.hip, DESIGN.md
+// §3.18.3): launch_ho_m2l (whole operator, no window) on S in {1, 2, 4} multipole buffers
+// mult + j * mstride into S local buffers local + j * lstride, each [node][R][K].  A
+// source's bits do not depend on S or on its slot.
+void launch_ho_m2l_src(int np, int K, int S, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
+                       const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
+                       const double* nry, const HoTables* T, const HarmWeights& hw, const double* mult,
+                       int64_t mstride, double* local, int64_t lstride, hipStream_t s);
 
 // ---- cache build and helpers (kernels.hip)
 void launch_cache_m2l(int64_t npairs, const int* pairTgt, const int* src, const double* ncx, const double* ncy,

@@ -1371,17 +1371,36 @@ int Operator::forwardSolveMultiDev(int nrhs, const double* q, int64_t ldq, bool 
     return steps;
 }
 
-// one group of ng <= arn::kMaxCols columns on the buffers of forwardSolveMultiDev
+// one group of ng <= arn::kMaxCols columns on the buffers of forwardSolveMultiDev: the
+// right-hand sides, then the shared loop over mode 0's x - K_0(sigma_s x)
 int Operator::forwardSolveGroup(int ng, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx, int m,
                                 double tol, int maxit, int* iters, double* relres, double* hist, int maxhist, double* V,
                                 double* B, double* In, double* W, double* st, double* part, double* dNb, double* hstat,
                                 double* stat, hipEvent_t ev, hipStream_t s) {
-    constexpr int G = arn::kMaxCols;
     const int64_t N = geo.N;
+    const double* sigS = sigmaSTree();
+    if (rhsIsSource) modeApplyDev(0, ng, q, ldq, nullptr, false, B, N, s);
+    else
+        HIP_CHECK(hipMemcpy2DAsync(B, N * sizeof(double), q, ldq * sizeof(double), N * sizeof(double), ng,
+                                   hipMemcpyDeviceToDevice, s));
+    const ColsSolve cs{N, "forward solve",
+                       [&](int nrows, const double* in, double* w) { modeApplyDev(0, nrows, in, N, sigS, true, w, N, s); }};
+    return colsSolveGroup(cs, ng, x, ldx, m, tol, maxit, iters, relres, hist, maxhist, V, B, In, W, st, part, dNb, hstat,
+                          stat, ev, s);
+}
+
+// The lockstep loop of one group (ColsSolve): every column a restarted GMRES of its own on
+// vectors of cs.L doubles; B holds the right-hand sides.
+int Operator::colsSolveGroup(const ColsSolve& cs, int ng, double* x, int64_t ldx, int m, double tol, int maxit,
+                             int* iters, double* relres, double* hist, int maxhist, double* V, double* B, double* In,
+                             double* W, double* st, double* part, double* dNb, double* hstat, double* stat,
+                             hipEvent_t ev, hipStream_t s) {
+    constexpr int G = arn::kMaxCols;
+    const int64_t N = cs.L;  // the row length
+    const std::string what(cs.what);
     const arn::Layout lay(m);
     const int64_t sts = lay.total, pc = (int64_t)(m + 2) * arn::kParts, vc = (int64_t)(m + 1) * N;
     const arn::ColArgs ca{sts, pc, arn::kParts, 4};
-    const double* sigS = sigmaSTree();
     const unsigned nb = nblk(N);
     struct Col {
         int total = 0, used = 0, nh = 0;
@@ -1416,14 +1435,9 @@ int Operator::forwardSolveGroup(int ng, const double* q, int64_t ldq, bool rhsIs
     auto op = [&](const arn::ColTable& t, int nrows, int row, int64_t ldv) {
         arn::k_arn_gather_cols<<<dim3(nb, nrows), arn::kThreads, 0, s>>>(N, row, ldv, t, In);
         HIP_LAUNCH_CHECK();
-        modeApplyDev(0, nrows, In, N, sigS, true, W, N, s);
+        cs.A(nrows, In, W);
         solveCalls.push_back(nrows);
     };
-    // the right-hand sides
-    if (rhsIsSource) modeApplyDev(0, ng, q, ldq, nullptr, false, B, N, s);
-    else
-        HIP_CHECK(hipMemcpy2DAsync(B, N * sizeof(double), q, ldq * sizeof(double), N * sizeof(double), ng,
-                                   hipMemcpyDeviceToDevice, s));
     {  // |b|^2 and |x|^2 per column
         arn::ColTable tb{}, tx{};
         for (int c = 0; c < ng; ++c) {
@@ -1480,7 +1494,7 @@ int Operator::forwardSolveGroup(int ng, const double* q, int64_t ldq, bool rhsIs
         HIP_LAUNCH_CHECK();
         wait();
         for (int c : cols) {
-            if (hstat[4 * c + 2] != 0.0) throw std::runtime_error("forward solve: a cycle's start left no status");
+            if (hstat[4 * c + 2] != 0.0) throw std::runtime_error(what + ": a cycle's start left no status");
             col[c].rel = hstat[4 * c];
             col[c].r = hstat[4 * c + 1];
             col[c].conv = col[c].rel <= tol;
@@ -1528,7 +1542,7 @@ int Operator::forwardSolveGroup(int ng, const double* q, int64_t ldq, bool rhsIs
             for (int c : live) {
                 Col& k = col[c];
                 if (hstat[4 * c + 2] != (double)(j + 1))
-                    throw std::runtime_error("forward solve: Arnoldi step " + std::to_string(j) + " left no status");
+                    throw std::runtime_error(what + ": Arnoldi step " + std::to_string(j) + " left no status");
                 const double rel = hstat[4 * c], rnext = hstat[4 * c + 1];
                 ++k.total;
                 k.used = j + 1;
@@ -1581,6 +1595,122 @@ int Operator::forwardSolveMultiHost(const double* Q, int k, bool rhsIsSource, do
     HIP_CHECK(hipMemcpyAsync(dx.p, X, bytes, hipMemcpyHostToDevice, own));
     const int steps = forwardSolveMultiDev(k, dq.as<double>(), geo.N, rhsIsSource, dx.as<double>(), geo.N, restart, tol,
                                            maxit, iters, relres, nullptr, 0, own);
+    HIP_CHECK(hipMemcpyAsync(X, dx.p, bytes, hipMemcpyDeviceToHost, own));
+    HIP_CHECK(hipStreamSynchronize(own));
+    return steps;
+}
+
+// ---- the block solve for several sources (aniso.m:159-173 per source):
+// forwardSolveMultiDev's scheme on vectors of ks * N doubles, groups of kBlockGroup sources
+// sharing one blockOpMultiDev(2, ...) per step on the sources still active.
+
+constexpr int kBlockGroup = 4;  // sources per group: one chunk of blockOpMultiDev
+
+bool Operator::blockSolveMultiCheck(const char* what, int nsrc, const void* q, int64_t ldq, const void* x, int64_t ldx,
+                                    const int* iters, int restart, double tol, int maxit) const {
+    const std::string w(what);
+    if (restart < 1 || restart > 400)
+        throw std::invalid_argument(w + ": restart must be in [1, 400], got " + std::to_string(restart));
+    if (!(tol > 0.0)) throw std::invalid_argument(w + ": tol must be > 0");
+    if (maxit < 0) throw std::invalid_argument(w + ": maxit must be >= 0, got " + std::to_string(maxit));
+    if (nsrc > 0 && !iters) throw std::invalid_argument(w + ": iters is NULL");
+    return blockOpMultiCheck(what, 2, nsrc, q, ldq, x, ldx);  // the rows, their overlap and the handle's state
+}
+
+int Operator::blockSolveMultiDev(int nsrc, const double* q, int64_t ldq, bool rhsIsCharge, double* x, int64_t ldx,
+                                 int restart, double tol, int maxit, int* iters, double* relres, double* hist,
+                                 int maxhist, hipStream_t s) {
+    if (!blockSolveMultiCheck("aniso_block_solve_multi_dev", nsrc, q, ldq, x, ldx, iters, restart, tol, maxit)) return 0;
+    ensureDevice();
+    checkDeviceErrors();
+    constexpr int G = arn::kMaxCols;
+    static_assert(kBlockGroup <= G, "a group fits the column tables");
+    const int64_t N = geo.N, L = (int64_t)ks * N;
+    const int m = restart, gmax = std::min(nsrc, kBlockGroup);
+    const arn::Layout lay(m);
+    const int64_t sts = lay.total, pc = (int64_t)(m + 2) * arn::kParts, vc = (int64_t)(m + 1) * L;
+    // every buffer of one group, allocated before anything is launched
+    DevBuf bV, bB, bIn, bW, bX, bSt, bPart, bNb;
+    const size_t basis = (size_t)vc * gmax * sizeof(double);
+    const size_t rest = (size_t)(4 * L + sts + pc + 1) * gmax * sizeof(double);
+    try {
+        bV.alloc(basis);
+        bB.alloc((size_t)gmax * L * sizeof(double));
+        bIn.alloc((size_t)gmax * L * sizeof(double));
+        bW.alloc((size_t)gmax * L * sizeof(double));
+        bX.alloc((size_t)gmax * L * sizeof(double));
+        bSt.alloc((size_t)gmax * sts * sizeof(double));
+        bPart.alloc((size_t)gmax * pc * sizeof(double));
+        bNb.alloc((size_t)gmax * sizeof(double));
+        if (highOrder() && ks <= kMaxRhs) blockMultiReserve(gmax == 3 ? 4 : gmax);
+    } catch (const std::exception& e) {
+        throw std::runtime_error("multi-source block solve: the Krylov bases of (restart + 1) x " + std::to_string(gmax) +
+                                 " x ks x N = " + std::to_string(m + 1) + " x " + std::to_string(gmax) + " x " +
+                                 std::to_string(ks) + " x " + std::to_string(N) + " doubles (" + std::to_string(basis) +
+                                 " bytes) and " + std::to_string(rest) +
+                                 " bytes of work rows could not be allocated: " + e.what());
+    }
+    struct HostStat {
+        double* p = nullptr;
+        hipEvent_t ev = nullptr;
+        ~HostStat() {
+            if (p) (void)hipHostFree(p);
+            if (ev) (void)hipEventDestroy(ev);
+        }
+    } hs;
+    HIP_CHECK(hipHostMalloc((void**)&hs.p, 6 * G * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_CHECK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
+    double* stat = nullptr;
+    HIP_CHECK(hipHostGetDevicePointer((void**)&stat, hs.p, 0));
+    arn_small_kernel_attrs();
+    solveCalls.clear();
+    const ColsSolve cs{L, "multi-source block solve", [&](int nrows, const double* in, double* w) {
+                           blockOpMultiDev(2, nrows, in, N, w, N, s);
+                       }};
+    int steps = 0;
+    try {
+        for (int r0 = 0; r0 < nsrc; r0 += kBlockGroup) {
+            const int ng = std::min(kBlockGroup, nsrc - r0);
+            const double* qg = q + (size_t)r0 * ks * ldq;
+            double* xg = x + (size_t)r0 * ks * ldx;
+            // the group's guesses as compact vectors, its right-hand sides (aniso.m:160)
+            HIP_CHECK(hipMemcpy2DAsync(bX.p, N * sizeof(double), xg, ldx * sizeof(double), N * sizeof(double),
+                                       (size_t)ng * ks, hipMemcpyDeviceToDevice, s));
+            if (rhsIsCharge) {
+                blockOpMultiDev(0, ng, qg, ldq, bB.as<double>(), N, s);
+                solveCalls.push_back(ng);
+            } else {
+                HIP_CHECK(hipMemcpy2DAsync(bB.p, N * sizeof(double), qg, ldq * sizeof(double), N * sizeof(double),
+                                           (size_t)ng * ks, hipMemcpyDeviceToDevice, s));
+            }
+            steps += colsSolveGroup(cs, ng, bX.as<double>(), L, m, tol, maxit, iters + r0, relres ? relres + r0 : nullptr,
+                                    hist ? hist + (size_t)r0 * maxhist : nullptr, hist ? maxhist : 0, bV.as<double>(),
+                                    bB.as<double>(), bIn.as<double>(), bW.as<double>(), bSt.as<double>(),
+                                    bPart.as<double>(), bNb.as<double>(), hs.p, stat, hs.ev, s);
+            HIP_CHECK(hipMemcpy2DAsync(xg, ldx * sizeof(double), bX.p, N * sizeof(double), N * sizeof(double),
+                                       (size_t)ng * ks, hipMemcpyDeviceToDevice, s));
+        }
+        HIP_CHECK(hipStreamSynchronize(s));  // the buffers are freed on return
+    } catch (...) {
+        (void)hipStreamSynchronize(s);  // no kernel still writes the buffers freed here
+        throw;
+    }
+    return steps;
+}
+
+// (ks N) x nsrc column-major host arrays: one staging copy each way
+int Operator::blockSolveMultiHost(const double* Q, int nsrc, bool rhsIsCharge, double* X, int restart, double tol,
+                                  int maxit, int* iters, double* relres) {
+    if (!blockSolveMultiCheck("aniso_block_solve_multi", nsrc, Q, geo.N, X, geo.N, iters, restart, tol, maxit)) return 0;
+    ensureDevice();
+    const size_t bytes = (size_t)nsrc * ks * geo.N * sizeof(double);
+    DevBuf dq, dx;
+    dq.alloc(bytes);
+    dx.alloc(bytes);
+    HIP_CHECK(hipMemcpyAsync(dq.p, Q, bytes, hipMemcpyHostToDevice, own));
+    HIP_CHECK(hipMemcpyAsync(dx.p, X, bytes, hipMemcpyHostToDevice, own));
+    const int steps = blockSolveMultiDev(nsrc, dq.as<double>(), geo.N, rhsIsCharge, dx.as<double>(), geo.N, restart, tol,
+                                         maxit, iters, relres, nullptr, 0, own);
     HIP_CHECK(hipMemcpyAsync(X, dx.p, bytes, hipMemcpyDeviceToHost, own));
     HIP_CHECK(hipStreamSynchronize(own));
     return steps;

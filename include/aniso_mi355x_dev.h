@@ -138,9 +138,11 @@ int aniso_arnoldi16_step(aniso_handle h, int64_t n16, int m, int j, float *V, in
 int aniso_arnoldi16_solution(aniso_handle h, int64_t n16, int m, int used, const float *V, int64_t ldv,
                              double *state, double *x, void *stream);
 /* ---- the multi-source forward solve ---- */
-/* the operator calls of the handle's last aniso_forward_solve_multi(_dev): *n = their
- * number, counts (cap >= 0 entries, may be NULL) = the column count of each, in order
- * (tools/forward_solve_time.py).  Host only. */
+/* the operator calls of the handle's last aniso_forward_solve_multi(_dev) or
+ * aniso_block_solve_multi(_dev): *n = their number, counts (cap >= 0 entries, may be NULL) =
+ * the column (source) count of each, in order (the block solve's list starts with each
+ * group's forward(charge) call)
+ * (tools/forward_solve_time.py, tools/block_multi_time.py).  Host only. */
 int aniso_forward_solve_calls(aniso_handle h, int *counts, int cap, int *n);
 
 #ifdef __cplusplus

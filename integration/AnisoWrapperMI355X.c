@@ -19,6 +19,9 @@
  * and aniso.m:159-173's solve, gmres(A, rhs, 400, 1e-11, 400), as one call with the
  * Krylov basis resident on the GPU:
  *   [u, relres, iters] = AnisoWrapperMI355X('solve', h, rhs, 400, 1e-11, 400);
+ * and the same solve for several charges in one medium, one stacked charge per column of Q
+ * (the right-hand sides forward(Q(:, s)) are formed in the call):
+ *   [U, relres, iters] = AnisoWrapperMI355X('solveMulti', h, Q, 80, 1e-11, 5);
  *
  * MATLAB is absent from this image and from the GPU box: tests/test_integration.py
  * compiles this file for syntax against a declaration-only mex.h (tests/mex_stub).
@@ -153,6 +156,33 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                                (int)mxGetScalar(prhs[5]), NULL, 0, &iters, &relres));
         if (nlhs > 1) plhs[1] = mxCreateDoubleScalar(relres);
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar((double)iters);
+    } else if (!strcmp(op, "solveMulti")) {
+        /* aniso.m's solve (aniso.m:159-173) for several charges in one medium:
+         *   [U, relres, iters] = ('solveMulti', h, Q, restart, tol, maxit)
+         * Q is (ks * N) x nsrc, one stacked charge per column; column s of U solves
+         * x - mforward(x) = forward(Q(:, s)) (aniso.m:160).  On a high-order handle the
+         * sources share the reads of the M2L blocks, 4 per pass (aniso_block_solve_multi) */
+        aniso_handle h;
+        int64_t len, total, nsrc, s;
+        mxArray *scratch, *relres, *steps;
+        int* iters;
+        need(nrhs, 6, op);
+        h = handle_of(prhs[1]);
+        len = num_blocks(h) * num_nodes(h);
+        total = (int64_t)mxGetNumberOfElements(prhs[2]);
+        if (!mxIsDouble(prhs[2]) || mxIsComplex(prhs[2]) || total % len != 0 || total / len > 0x7fffffff)
+            mexErrMsgIdAndTxt("mexplus:arguments:error", "Q must be a real double matrix of %lld rows", (long long)len);
+        nsrc = total / len;
+        plhs[0] = mxCreateDoubleMatrix((size_t)len, (size_t)nsrc, mxREAL); /* zeros: MATLAB's default x0 */
+        relres = mxCreateDoubleMatrix((size_t)nsrc, 1, mxREAL);
+        steps = mxCreateDoubleMatrix((size_t)nsrc, 1, mxREAL);
+        scratch = mxCreateNumericMatrix((size_t)nsrc, 1, mxINT64_CLASS, mxREAL); /* room for nsrc ints; MATLAB frees it */
+        iters = (int*)mxGetData(scratch);
+        CALL(aniso_block_solve_multi(h, mxGetPr(prhs[2]), (int)nsrc, 1, mxGetPr(plhs[0]), (int)mxGetScalar(prhs[3]),
+                                     mxGetScalar(prhs[4]), (int)mxGetScalar(prhs[5]), iters, mxGetPr(relres)));
+        for (s = 0; s < nsrc; ++s) mxGetPr(steps)[s] = (double)iters[s];
+        if (nlhs > 1) plhs[1] = relres;
+        if (nlhs > 2) plhs[2] = steps;
     } else {
         mexErrMsgIdAndTxt("mexplus:dispatch:argumentError", "Unknown operation %s", op);
     }
