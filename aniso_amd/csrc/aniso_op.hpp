@@ -26,6 +26,10 @@ int64_t arn_state_doubles(int m);  // the Arnoldi state block of restart length 
 // the 16-column Arnoldi's state blocks and sweep partials at restart m (arnoldi16.hpp), in doubles
 void arn16_work_doubles(int m, int64_t* state, int64_t* part);
 
+struct StatusBlock;  // gmres_driver.hpp: what the solves of solver.hip share
+struct GmresSystem;
+struct ColsWork;
+
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
@@ -537,15 +541,11 @@ private:
         const char* what;
         std::function<void(int, const double*, double*)> A;
     };
-    int colsSolveGroup(const ColsSolve& cs, int ng, double* x, int64_t ldx, int m, double tol, int maxit, int* iters,
-                       double* relres, double* hist, int maxhist, double* V, double* B, double* In, double* W,
-                       double* st, double* part, double* dNb, double* hstat, double* stat, hipEvent_t ev,
-                       hipStream_t s);
-    // one group of ng <= 8 columns of the forward solve on the caller's work buffers
-    int forwardSolveGroup(int ng, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx, int m,
-                          double tol, int maxit, int* iters, double* relres, double* hist, int maxhist, double* V,
-                          double* B, double* In, double* W, double* st, double* part, double* dNb, double* hstat,
-                          double* stat, hipEvent_t ev, hipStream_t s);
+    int colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* x, int64_t ldx, int m, double tol, int maxit,
+                       int* iters, double* relres, double* hist, int maxhist, hipStream_t s);
+    // the restarted GMRES of one system: the loop blockSolveDev and blockSolveShardedDev share
+    int gmresRestarted(const GmresSystem& g, StatusBlock& hs, double tol, int maxit, double* hist, int maxhist,
+                       double* relres, hipStream_t s);
     std::vector<int> solveCalls;
     void arnoldiParts(int rows);  // dKryPart for sweeps of `rows` rows
     bool topTraceOn = false;

@@ -17,16 +17,10 @@
 #include "arnoldi16.hpp"
 #include "arnoldi_cols.hpp"
 #include "device_common.hpp"
+#include "gmres_driver.hpp"
 #include "kernels.hpp"
 
 namespace aniso {
-
-[[noreturn]] void throw_hip(hipError_t e, const char* file, int line);
-#define HIP_CHECK(x)                                               \
-    do {                                                           \
-        hipError_t e__ = (x);                                      \
-        if (e__ != hipSuccess) throw_hip(e__, __FILE__, __LINE__); \
-    } while (0)
 
 constexpr int kRedBlocks = 512;
 
@@ -441,15 +435,6 @@ done:
     return ret;
 }
 
-// aniso.m:159-173: u = gmres(A, rhs, restart, tol, maxit) with A(x) = x - mforward(x)
-// (aniso.m:155) on the nb = ks stacked blocks.  MATLAB's restarted GMRES semantics:
-// x0 = the given guess, at most maxit cycles of at most `restart` steps, converged
-// when ||rhs - A x|| / ||rhs|| <= tol (the estimate inside a cycle, confirmed by the
-// explicit residual at its end).  The vectors are permuted once into tree order and
-// every Krylov vector ((restart + 1) x ks x N doubles) stays in HBM; orthogonalisation
-// is CGS2 on the device.  rhs / x: device, original order, block b at b * N.
-// Returns the total step count (negative if not converged); hist gets the relative
-// residual estimate after every step.
 // The CGS2 sweeps as library primitives for a caller's own Krylov loop (the sharded
 // GMRES of aniso_amd.solve.gmres_dist reduces their outputs over the ranks between
 // the calls): out[k] = V_k . w; and w -= V c followed by out[k] = V_k . w, out[nv] =
@@ -590,6 +575,84 @@ void Operator::arnoldiSolution(int64_t n, int m, int used, const double* V, int6
     HIP_LAUNCH_CHECK();
 }
 
+// The restarted GMRES of one system (GmresSystem, gmres_driver.hpp), the loop of the block
+// solve and of its sharded form: MATLAB's semantics as described at blockSolveDev, g.x
+// updated in place.  Returns the total step count (negative if not converged); hist gets
+// the relative residual estimate after every step, *relresOut the final one.  hs: the
+// status words {relres, r', steps, -} that startCycle and step store.  Every decision is
+// taken from those words, which the sharded solve's kernels compute from all-reduced sums:
+// no rank takes a branch of its own.
+int Operator::gmresRestarted(const GmresSystem& g, StatusBlock& hs, double tol, int maxit, double* hist, int maxhist,
+                             double* relresOut, hipStream_t s) {
+    const int64_t L = g.L;
+    const int m = g.m;
+    double* const V = g.V;
+    *relresOut = 0.0;
+    if (g.normb == 0.0) {  // b = 0: x = 0
+        if (L > 0) HIP_CHECK(hipMemsetAsync(g.x, 0, L * sizeof(double), s));
+        return 0;
+    }
+    bool xZero = g.xZero;
+    // r = b - A x into V[0], then the cycle's start; returns |r| / |b|
+    auto residual = [&] {
+        for (int tries = 0;; ++tries) {
+            if (xZero) {
+                if (L > 0) HIP_CHECK(hipMemcpyAsync(V, g.b, L * sizeof(double), hipMemcpyDeviceToDevice, s));
+            } else {
+                g.matvec(g.x);
+                if (L > 0) k_sub<<<nblk(L), 256, 0, s>>>(L, g.b, g.w, V);
+            }
+            g.startCycle();
+            hs.sync(s);
+            // a residual whose matvec ran on an invalid fused launch is redone, once
+            if (!g.spoiled() || tries > 0) return hs.p[0];
+        }
+    };
+    int nh = 0, total = 0;
+    double relres = residual();
+    bool conv = relres <= tol;
+    LookAhead la;
+    for (int cyc = 0; cyc < maxit && !conv; ++cyc) {
+        if (hs.p[1] == 0.0) break;  // |r| = 0 in floating point
+        int used = 0;
+        bool ahead = false;  // the matvec of V[j] is already enqueued
+        la.clear();
+        for (int j = 0; j < m; ++j) {
+            if (!ahead) g.matvec(V + (size_t)j * L);
+            g.step(j);
+            hs.post(s);
+            // the next step's matvec before the host reads the status, unless this step is
+            // predicted to converge (LookAhead); sharded, every rank holds the same
+            // estimates: all ranks enqueue it, or none
+            ahead = j + 1 < m && !la.near(tol);
+            if (ahead) g.matvec(V + (size_t)(j + 1) * L);
+            hs.wait();
+            if (g.spoiled()) {
+                // this step's matvec (or the look-ahead one) ran on an invalid fused launch:
+                // the cycle ends before this step (columns 0 .. j - 1 are valid) and restarts
+                // from its update on the tier launches
+                ahead = false;
+                break;
+            }
+            const double rel = hs.p[0], rnext = hs.p[1];
+            if (hs.p[2] != (double)(j + 1))  // the column kernel of this step did not run
+                throw std::runtime_error("block solve: Arnoldi step " + std::to_string(j) + " left no status");
+            ++total;
+            used = j + 1;
+            relres = rel;
+            la.push(rel);
+            if (hist && nh < maxhist) hist[nh++] = rel;
+            if (rel <= tol || rnext == 0.0) break;  // converged (estimate) or lucky breakdown
+        }
+        arnoldiSolution(L, m, used, V, L, g.st, g.x, s);  // x += P T R^-1 g
+        xZero = xZero && used == 0;
+        relres = residual();
+        conv = relres <= tol;
+    }
+    *relresOut = relres;
+    return conv ? total : -std::max(total, 1);
+}
+
 // aniso.m:159-173: u = gmres(A, rhs, restart, tol, maxit) with A(x) = x - mforward(x)
 // (aniso.m:155) on the nb = ks stacked blocks.  MATLAB's restarted GMRES semantics:
 // x0 = the given guess, at most maxit cycles of at most `restart` steps, converged
@@ -633,116 +696,35 @@ int Operator::blockSolveDev(const double* rhs, double* x, int restart, double to
     }
     // the status word {relres, r', steps} in mapped host memory: the column kernel
     // stores it there and the host waits for an event behind it, not a stream drain
-    struct HostStat {
-        double* p = nullptr;
-        hipEvent_t ev = nullptr;
-        ~HostStat() {
-            if (p) (void)hipHostFree(p);
-            if (ev) (void)hipEventDestroy(ev);
-        }
-    } hs;
-    HIP_CHECK(hipHostMalloc((void**)&hs.p, 4 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_CHECK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
-    double* stat = nullptr;
-    HIP_CHECK(hipHostGetDevicePointer((void**)&stat, hs.p, 0));
-    auto post = [&] { HIP_CHECK(hipEventRecord(hs.ev, s)); };
+    StatusBlock hs;
+    hs.alloc(4);
+    double* stat = hs.dev;
     auto sumsq = [&](const double* v) {  // |v|^2 on the host (once per solve)
-        arn::launch_project(L, 1, v, L, v, dKryPart.as<double>(), s);
-        arn::k_arn_rows<<<1, arn::kThreads, sizeof(double), s>>>(dKryPart.as<double>(), arn::kParts, 1, stat);
-        post();
-        HIP_CHECK(hipEventSynchronize(hs.ev));
+        arnoldiProject(L, 0, v, L, v, stat, s);
+        hs.sync(s);
         return hs.p[0];
     };
     // a fused-launch time-out (recoverTopTimeout) re-runs the apply it spoiled on the
     // tier launches, and the rest of the solve keeps them
-    struct Restore {
-        bool& f;
-        bool v;
-        ~Restore() { f = v; }
-    } restore{forceUnfused, forceUnfused}, own{ownTimeline, ownTimeline};
-    ownTimeline = true;  // the look-ahead matvec may be enqueued after a spoiled one: recovered below
-    const double normb = std::sqrt(sumsq(b));
+    ScopedFlag restore(forceUnfused), own(ownTimeline);
+    ownTimeline = true;  // the look-ahead matvec may be enqueued after a spoiled one: recovered in the driver
+    GmresSystem g{L, m, 0.0, false, b, xt, w, V, st};
+    g.normb = std::sqrt(sumsq(b));
     // A 0 = 0: a zero initial guess needs no matvec for its residual
-    bool xZero = normb > 0.0 && sumsq(xt) == 0.0;
-    // r = b - A x into V[0], then the cycle's start; returns |r| / |b|
-    auto residual = [&] {
-        for (int tries = 0;; ++tries) {
-            if (xZero) {
-                HIP_CHECK(hipMemcpyAsync(V, b, L * sizeof(double), hipMemcpyDeviceToDevice, s));
-            } else {
-                blockOpDev(2, xt, N, w, N, true, s);
-                k_sub<<<nblk(L), 256, 0, s>>>(L, b, w, V);
-            }
-            arnoldiBegin(L, m, V, L, st, nullptr, normb, stat, s);
-            post();
-            HIP_CHECK(hipEventSynchronize(hs.ev));
-            if (!recoverTopTimeout(s) || tries > 0) return hs.p[0];
-        }
-    };
-    int nh = 0, total = 0;
+    g.xZero = g.normb > 0.0 && sumsq(xt) == 0.0;
+    g.matvec = [&](const double* v) { blockOpDev(2, v, N, w, N, true, s); };
+    g.startCycle = [&] { arnoldiBegin(L, m, V, L, st, nullptr, g.normb, stat, s); };
+    g.step = [&](int j) { arnoldiStep(L, m, j, V, L, w, st, stat, s); };
+    g.spoiled = [&] { return recoverTopTimeout(s); };
     double relres = 0.0;
-    bool conv = false;
-    if (normb == 0.0) {
-        HIP_CHECK(hipMemsetAsync(xt, 0, L * sizeof(double), s));
-        conv = true;
-    } else {
-        relres = residual();
-        conv = relres <= tol;
-        std::vector<double> hrel;
-        for (int cyc = 0; cyc < maxit && !conv; ++cyc) {
-            if (hs.p[1] == 0.0) break;  // |r| = 0 in floating point
-            int used = 0;
-            bool ahead = false;  // the matvec of V[j] is already enqueued
-            hrel.clear();
-            for (int j = 0; j < m; ++j) {
-                double* vj = V + (size_t)j * L;
-                if (!ahead) blockOpDev(2, vj, N, w, N, true, s);
-                arnoldiStep(L, m, j, V, L, w, st, stat, s);
-                post();
-                // the next step's matvec goes in before the host reads the status: the GPU
-                // runs it while the host decides (wasted once per cycle, at the step that
-                // converges) -- except where the residual estimate is predicted to reach tol
-                // at this step (geometric extrapolation of the last two estimates, 10x margin)
-                bool near = false;
-                if (hrel.size() >= 2) {
-                    const double q = std::min(1.0, hrel.back() / hrel[hrel.size() - 2]);
-                    near = hrel.back() * q <= 10.0 * tol;
-                } else if (!hrel.empty()) {
-                    near = hrel.back() <= 10.0 * tol;
-                }
-                ahead = j + 1 < m && !near;
-                if (ahead) blockOpDev(2, V + (size_t)(j + 1) * L, N, w, N, true, s);
-                HIP_CHECK(hipEventSynchronize(hs.ev));
-                if (recoverTopTimeout(s)) {
-                    // this step's matvec (or the look-ahead one) ran on an invalid fused launch:
-                    // the cycle ends before this step (columns 0 .. j - 1 are valid) and restarts
-                    // from its update on the tier launches
-                    ahead = false;
-                    break;
-                }
-                const double rel = hs.p[0], rnext = hs.p[1];
-                if (hs.p[2] != (double)(j + 1))  // the column kernel of this step did not run
-                    throw std::runtime_error("block solve: Arnoldi step " + std::to_string(j) + " left no status");
-                ++total;
-                used = j + 1;
-                relres = rel;
-                hrel.push_back(rel);
-                if (hist && nh < maxhist) hist[nh++] = rel;
-                if (rel <= tol || rnext == 0.0) break;  // converged (estimate) or lucky breakdown
-            }
-            arnoldiSolution(L, m, used, V, L, st, xt, s);  // x += P T R^-1 g
-            xZero = xZero && used == 0;
-            relres = residual();
-            conv = relres <= tol;
-        }
-    }
+    const int its = gmresRestarted(g, hs, tol, maxit, hist, maxhist, &relres, s);
     for (int k = 0; k < ks; ++k)
         k_unpermute<<<nblk(N), 256, 0, s>>>(N, perm, xt + (size_t)k * N, x + (size_t)k * N);
     HIP_CHECK(hipStreamSynchronize(s));
     ownTimeline = false;
     checkDeviceErrors();  // every apply was checked at its recovery point: a flag here is new
     if (relresOut) *relresOut = relres;
-    return conv ? total : -std::max(total, 1);
+    return its;
 }
 
 // ---- the block solve across ranks: the small device pieces beside the
@@ -771,8 +753,8 @@ static void rows_copy(int rows, int64_t len, const double* src, int64_t lds, dou
     HIP_LAUNCH_CHECK();
 }
 
-// blockSolveDev's loop on this rank's compact owned vectors (L = ks x owned, contiguous
-// rows), every rank of the communicator together.  The matvec is the one-call sharded
+// blockSolveDev's loop (gmresRestarted) on this rank's compact owned vectors (L = ks x
+// owned, contiguous rows), every rank of the communicator together.  The matvec is the one-call sharded
 // operator: V[j] goes into the own-range columns of the handle's (ks, N) input with one
 // strided copy, and the operator writes its owned output straight into w.  A step is
 //   project -> k_arn_rows -> all-reduce (j + 1) -> k_arn_coef(P = 1) -> update ->
@@ -802,15 +784,7 @@ int Operator::blockSolveShardedDev(const double* rhs, int64_t ldr, double* x, in
     }
     double* red = dShRed.as<double>();
     DevBuf bB, bX, bW, bV, bSt;
-    struct HostStat {
-        double* p = nullptr;
-        hipEvent_t ev = nullptr;
-        ~HostStat() {
-            if (p) (void)hipHostFree(p);
-            if (ev) (void)hipEventDestroy(ev);
-        }
-    } hs;
-    double* stat = nullptr;
+    StatusBlock hs;
     unsigned* errDev = nullptr;
     // ---- everything that can fail on this rank alone
     std::exception_ptr refused;
@@ -831,9 +805,7 @@ int Operator::blockSolveShardedDev(const double* rhs, int64_t ldr, double* x, in
             HIP_CHECK(hipMemsetAsync(dShIn.p, 0, dShIn.bytes, s));  // outside the own range: the exchange's halo
         }
         arnoldiParts(m + 2);
-        HIP_CHECK(hipHostMalloc((void**)&hs.p, 4 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_CHECK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
-        HIP_CHECK(hipHostGetDevicePointer((void**)&stat, hs.p, 0));
+        hs.alloc(4);
         HIP_CHECK(hipHostGetDevicePointer((void**)&errDev, topErr, 0));
     } catch (...) {
         refused = std::current_exception();
@@ -849,12 +821,8 @@ int Operator::blockSolveShardedDev(const double* rhs, int64_t ldr, double* x, in
     if (!refused) {
         rows_copy(ks, owned, rhs, ldr, b, owned, s);
         rows_copy(ks, owned, x, ldx, xt, owned, s);
-        double* part = dKryPart.as<double>();
-        arn::launch_project(L, 1, b, L, b, part, s);
-        arn::k_arn_rows<<<1, arn::kThreads, sizeof(double), s>>>(part, arn::kParts, 1, red + 1);
-        arn::launch_project(L, 1, xt, L, xt, part, s);
-        arn::k_arn_rows<<<1, arn::kThreads, sizeof(double), s>>>(part, arn::kParts, 1, red + 2);
-        HIP_LAUNCH_CHECK();
+        arnoldiProject(L, 0, b, L, b, red + 1, s);
+        arnoldiProject(L, 0, xt, L, xt, red + 2, s);
     }
     comm->allreduce(red, 3, s);
     double opening[3] = {0.0, 0.0, 0.0};
@@ -864,115 +832,52 @@ int Operator::blockSolveShardedDev(const double* rhs, int64_t ldr, double* x, in
     if (opening[0] != 0.0)
         throw std::invalid_argument("sharded block solve: another rank refused the call (its own error says why); "
                                     "no rank started and nothing was changed");
-    struct Restore {
-        bool& f;
-        bool v;
-        ~Restore() { f = v; }
-    } ownTl{ownTimeline, ownTimeline};
+    ScopedFlag ownTl(ownTimeline);
     ownTimeline = true;  // the applies' entry checks leave the failure flag to the all-reduces below
-    auto post = [&] { HIP_CHECK(hipEventRecord(hs.ev, s)); };
-    auto failed = [&]() {
+    double* const stat = hs.dev;
+    GmresSystem g{L, m, std::sqrt(opening[1]), false, b, xt, w, V, st};
+    g.xZero = g.normb > 0.0 && opening[2] == 0.0;  // A 0 = 0: no matvec for the first residual
+    // w = A v: v (compact) into the own-range columns of the (ks, N) input, the owned output into w
+    g.matvec = [&](const double* v) {
+        rows_copy(ks, owned, v, owned, xin + ob, N, s);
+        blockOpShardedOwned(2, xin, N, w, owned, s);
+    };
+    // the failure flag behind n reduced sums, all-reduced with them; then the flag's sum
+    // beside the status words that `then` stores
+    auto reduceFlagged = [&](int n, auto&& then) {
+        k_flag_put<<<1, 64, 0, s>>>(errDev, 0.0, red + n);
+        HIP_LAUNCH_CHECK();
+        comm->allreduce(red, (size_t)n + 1, s);
+        then();
+        k_words<<<1, 64, 0, s>>>(red + n, 1, stat + 3);
+        HIP_LAUNCH_CHECK();
+    };
+    g.startCycle = [&] {  // |r|^2 summed over the ranks
+        arnoldiProject(L, 0, V, L, V, red, s);
+        reduceFlagged(1, [&] { arnoldiBegin(L, m, V, L, st, red, g.normb, stat, s); });
+    };
+    g.step = [&](int j) {  // the library's sweeps (aniso_arnoldi_*), their sums reduced over the ranks
+        arnoldiProject(L, j, V, L, w, red, s);
+        comm->allreduce(red, (size_t)j + 1, s);
+        arnoldiCoef(m, j, st, red, s);
+        arnoldiUpdate(L, m, j, V, L, w, st, red, s);
+        reduceFlagged(j + 2, [&] { arnoldiColumn(m, j, st, red, stat, s); });
+    };
+    // the all-reduced failure flag beside the status words: never recovered, see above
+    g.spoiled = [&]() -> bool {
+        if (hs.p[3] == 0.0) return false;
         HIP_CHECK(hipStreamSynchronize(s));  // (a look-ahead matvec may be in flight; every rank enqueued it)
         *(volatile unsigned*)topErr = 0;
         throw std::runtime_error("sharded block solve: a rank reported a device-side failure (a hand-off time-out of "
                                  "its fused top-of-tree launch); every rank left the solve at the same step and x "
                                  "is unchanged");
     };
-    // w = A v: v (compact) into the own-range columns of the (ks, N) input, the owned output into w
-    auto matvec = [&](const double* v) {
-        rows_copy(ks, owned, v, owned, xin + ob, N, s);
-        blockOpShardedOwned(2, xin, N, w, owned, s);
-    };
-    const double normb = std::sqrt(opening[1]);
-    bool xZero = normb > 0.0 && opening[2] == 0.0;  // A 0 = 0: no matvec for the first residual
-    // r = b - A x into V[0], |r|^2 summed over the ranks, the cycle's start; returns |r| / |b|
-    auto residual = [&] {
-        if (xZero) {
-            if (L > 0) HIP_CHECK(hipMemcpyAsync(V, b, L * sizeof(double), hipMemcpyDeviceToDevice, s));
-        } else {
-            matvec(xt);
-            if (L > 0) k_sub<<<nblk(L), 256, 0, s>>>(L, b, w, V);
-        }
-        double* part = dKryPart.as<double>();
-        arn::launch_project(L, 1, V, L, V, part, s);
-        arn::k_arn_rows<<<1, arn::kThreads, sizeof(double), s>>>(part, arn::kParts, 1, red);
-        k_flag_put<<<1, 64, 0, s>>>(errDev, 0.0, red + 1);
-        HIP_LAUNCH_CHECK();
-        comm->allreduce(red, 2, s);
-        arn::k_arn_begin<<<1, arn::kThreads, 0, s>>>(m, st, red, 1, normb, stat);
-        k_words<<<1, 64, 0, s>>>(red + 1, 1, stat + 3);
-        HIP_LAUNCH_CHECK();
-        post();
-        HIP_CHECK(hipEventSynchronize(hs.ev));
-        if (hs.p[3] != 0.0) failed();
-        return hs.p[0];
-    };
-    int nh = 0, total = 0;
     double relres = 0.0;
-    bool conv = false;
-    if (normb == 0.0) {
-        if (L > 0) HIP_CHECK(hipMemsetAsync(xt, 0, L * sizeof(double), s));
-        conv = true;
-    } else {
-        relres = residual();
-        conv = relres <= tol;
-        std::vector<double> hrel;
-        for (int cyc = 0; cyc < maxit && !conv; ++cyc) {
-            if (hs.p[1] == 0.0) break;  // |r| = 0 in floating point
-            int used = 0;
-            bool ahead = false;  // the matvec of V[j] is already enqueued
-            hrel.clear();
-            for (int j = 0; j < m; ++j) {
-                if (!ahead) matvec(V + (size_t)j * L);
-                double* part = dKryPart.as<double>();
-                arn::launch_project(L, j + 1, V, L, w, part, s);
-                arn::k_arn_rows<<<1, arn::kThreads, (size_t)(j + 1) * sizeof(double), s>>>(part, arn::kParts, j + 1, red);
-                HIP_LAUNCH_CHECK();
-                comm->allreduce(red, (size_t)j + 1, s);
-                arn::k_arn_coef<<<1, arn::kThreads, arn::coef_lds(j), s>>>(m, j, st, red, 1);
-                HIP_LAUNCH_CHECK();
-                arn::launch_update(L, j + 1, V, L, w, st, m, part, s);
-                arn::k_arn_rows<<<1, arn::kThreads, (size_t)(j + 2) * sizeof(double), s>>>(part, arn::kParts, j + 2, red);
-                k_flag_put<<<1, 64, 0, s>>>(errDev, 0.0, red + j + 2);
-                HIP_LAUNCH_CHECK();
-                comm->allreduce(red, (size_t)j + 3, s);
-                arn::k_arn_column<<<1, arn::kThreads, arn::column_lds(j), s>>>(m, j, st, red, 1, stat);
-                k_words<<<1, 64, 0, s>>>(red + j + 2, 1, stat + 3);
-                HIP_LAUNCH_CHECK();
-                post();
-                // the look-ahead matvec and its prediction as blockSolveDev's, from the
-                // estimates every rank holds alike: all ranks enqueue it, or none
-                bool near = false;
-                if (hrel.size() >= 2) {
-                    const double q = std::min(1.0, hrel.back() / hrel[hrel.size() - 2]);
-                    near = hrel.back() * q <= 10.0 * tol;
-                } else if (!hrel.empty()) {
-                    near = hrel.back() <= 10.0 * tol;
-                }
-                ahead = j + 1 < m && !near;
-                if (ahead) matvec(V + (size_t)(j + 1) * L);
-                HIP_CHECK(hipEventSynchronize(hs.ev));
-                if (hs.p[3] != 0.0) failed();
-                const double rel = hs.p[0], rnext = hs.p[1];
-                if (hs.p[2] != (double)(j + 1))  // the column kernel of this step did not run
-                    throw std::runtime_error("block solve: Arnoldi step " + std::to_string(j) + " left no status");
-                ++total;
-                used = j + 1;
-                relres = rel;
-                hrel.push_back(rel);
-                if (hist && nh < maxhist) hist[nh++] = rel;
-                if (rel <= tol || rnext == 0.0) break;  // converged (estimate) or lucky breakdown
-            }
-            arnoldiSolution(L, m, used, V, L, st, xt, s);  // x += P T R^-1 g
-            xZero = xZero && used == 0;
-            relres = residual();
-            conv = relres <= tol;
-        }
-    }
+    const int its = gmresRestarted(g, hs, tol, maxit, hist, maxhist, &relres, s);
     rows_copy(ks, owned, xt, owned, x, ldx, s);
     HIP_CHECK(hipStreamSynchronize(s));
     if (relresOut) *relresOut = relres;
-    return conv ? total : -std::max(total, 1);
+    return its;
 }
 
 // ---- the 16-column Arnoldi of arnoldi16.hpp as functions on a caller's buffers: the
@@ -1180,22 +1085,15 @@ int Operator::mixedGroupRun(const double* B, int64_t ldb, double* X, int64_t ldx
     double *D = s16D.as<double>(), *st = s16St.as<double>(), *part = s16Part.as<double>(), *r0d = s16R0.as<double>();
     float *Df = s16Df.as<float>(), *W32 = s16W32.as<float>(), *V = s16V.as<float>();
     const int* perm = dPerm.as<int>();
-    struct {
-        double* p;
-        hipEvent_t ev;
-    } hs{s16Stat, s16Ev};
-    double* stat = nullptr;
-    HIP_CHECK(hipHostGetDevicePointer((void**)&stat, hs.p, 0));
+    StatusBlock hs;
+    hs.view(s16Stat, s16Ev);
+    double* stat = hs.dev;
     double* sums = stat + 4 * KC;
     const double* hsums = hs.p + 4 * KC;
-    auto wait = [&] {
-        HIP_CHECK(hipEventRecord(hs.ev, s));
-        HIP_CHECK(hipEventSynchronize(hs.ev));
-    };
     auto colsums = [&] {  // the one-row partials in `part` -> hsums[c]
         k16_rows<<<KC, arn::kThreads, 0, s>>>(part, sums);
         HIP_LAUNCH_CHECK();
-        wait();
+        hs.sync(s);
     };
     const unsigned g16 = nblk(n16);
     k16_gather<<<g16, 256, 0, s>>>(N, perm, B, ldb, nrows, Bt);
@@ -1231,25 +1129,22 @@ int Operator::mixedGroupRun(const double* B, int64_t ldb, double* X, int64_t ldx
                 forwardF32Dev(Df, W32, s);
             }
             arnoldi16Begin(n16, m, R, its > 0 ? W32 : nullptr, r0d, V, st, part, stat, s);
-            wait();
+            hs.sync(s);
             bool done = true;
             for (int c = 0; c < KC; ++c) done = done && hs.p[4 * c] <= innerTol;
             if (done) break;
             int used = 0;
             bool ahead = false;
-            std::vector<double> hrel;
+            LookAhead la;
             for (int j = 0; j < m; ++j) {
                 float* vj = V + (size_t)j * n16;
                 if (!ahead) forwardF32Dev(vj, W32, s);
                 arnoldi16Step(n16, m, j, V, n16, W32, st, part, stat, s);
-                HIP_CHECK(hipEventRecord(hs.ev, s));
-                // the next step's matvec before the host reads the estimates (as blockSolveDev)
-                bool near = false;
-                if (hrel.size() >= 2) near = hrel.back() * std::min(1.0, hrel.back() / hrel[hrel.size() - 2]) <= 10.0 * innerTol;
-                else if (!hrel.empty()) near = hrel.back() <= 10.0 * innerTol;
-                ahead = j + 1 < m && !near;
+                hs.post(s);
+                // the next step's matvec before the host reads the estimates (as gmresRestarted)
+                ahead = j + 1 < m && !la.near(innerTol);
                 if (ahead) forwardF32Dev(V + (size_t)(j + 1) * n16, W32, s);
-                HIP_CHECK(hipEventSynchronize(hs.ev));
+                hs.wait();
                 double worst = 0.0;
                 for (int c = 0; c < KC; ++c) {
                     if (hs.p[4 * c + 2] != (double)(j + 1))
@@ -1258,7 +1153,7 @@ int Operator::mixedGroupRun(const double* B, int64_t ldb, double* X, int64_t ldx
                 }
                 ++its;
                 used = j + 1;
-                hrel.push_back(worst);
+                la.push(worst);
                 if (worst <= innerTol) break;
             }
             longestCycle = std::max(longestCycle, used);
@@ -1285,6 +1180,14 @@ int Operator::mixedGroupRun(const double* B, int64_t ldb, double* X, int64_t ldx
 // arn::kMaxCols run in lockstep and share one operator call per step, on exactly the
 // rows still active.
 
+// the GMRES parameters of the lockstep multi-column solves (w: the entry's name)
+static void checkColsSolveParams(const std::string& w, int restart, double tol, int maxit) {
+    if (restart < 1 || restart > 400)
+        throw std::invalid_argument(w + ": restart must be in [1, 400], got " + std::to_string(restart));
+    if (!(tol > 0.0)) throw std::invalid_argument(w + ": tol must be > 0");
+    if (maxit < 0) throw std::invalid_argument(w + ": maxit must be >= 0, got " + std::to_string(maxit));
+}
+
 // everything that can be refused before the device is touched (false: nothing to do)
 bool Operator::forwardSolveMultiCheck(const char* what, int nrhs, const void* q, int64_t ldq, const void* x,
                                       int64_t ldx, const int* iters, int restart, double tol, int maxit) const {
@@ -1293,10 +1196,7 @@ bool Operator::forwardSolveMultiCheck(const char* what, int nrhs, const void* q,
     if (nrhs < 0) throw std::invalid_argument(w + ": nrhs must be >= 0, got " + std::to_string(nrhs));
     if (ldq < N) throw std::invalid_argument(w + ": ldq = " + std::to_string(ldq) + " is below N = " + std::to_string(N));
     if (ldx < N) throw std::invalid_argument(w + ": ldx = " + std::to_string(ldx) + " is below N = " + std::to_string(N));
-    if (restart < 1 || restart > 400)
-        throw std::invalid_argument(w + ": restart must be in [1, 400], got " + std::to_string(restart));
-    if (!(tol > 0.0)) throw std::invalid_argument(w + ": tol must be > 0");
-    if (maxit < 0) throw std::invalid_argument(w + ": maxit must be >= 0, got " + std::to_string(maxit));
+    checkColsSolveParams(w, restart, tol, maxit);
     if (nrhs > 0 && !q) throw std::invalid_argument(w + ": q is NULL");
     if (nrhs > 0 && !x) throw std::invalid_argument(w + ": x is NULL");
     if (nrhs > 0 && !iters) throw std::invalid_argument(w + ": iters is NULL");
@@ -1318,51 +1218,31 @@ int Operator::forwardSolveMultiDev(int nrhs, const double* q, int64_t ldq, bool 
     constexpr int G = arn::kMaxCols;
     const int64_t N = geo.N;
     const int m = restart, gmax = std::min(nrhs, G);
-    const arn::Layout lay(m);
-    const int64_t sts = lay.total, pc = (int64_t)(m + 2) * arn::kParts, vc = (int64_t)(m + 1) * N;
-    // every buffer of one group, allocated before anything is launched
-    DevBuf bV, bB, bIn, bW, bSt, bPart, bNb;
-    const size_t basis = (size_t)vc * gmax * sizeof(double);
-    const size_t rest = (size_t)(3 * N + sts + pc + 1) * gmax * sizeof(double);
-    try {
-        bV.alloc(basis);
-        bB.alloc((size_t)gmax * N * sizeof(double));
-        bIn.alloc((size_t)gmax * N * sizeof(double));
-        bW.alloc((size_t)gmax * N * sizeof(double));
-        bSt.alloc((size_t)gmax * sts * sizeof(double));
-        bPart.alloc((size_t)gmax * pc * sizeof(double));
-        bNb.alloc((size_t)gmax * sizeof(double));
-    } catch (const std::exception& e) {
-        throw std::runtime_error("forward solve: the Krylov bases of (restart + 1) x " + std::to_string(gmax) + " x N = " +
-                                 std::to_string(m + 1) + " x " + std::to_string(gmax) + " x " + std::to_string(N) +
-                                 " doubles (" + std::to_string(basis) + " bytes) and " + std::to_string(rest) +
-                                 " bytes of work buffers could not be allocated: " + e.what());
-    }
-    // per column {estimate, r', steps, -}, then |b|^2 and |x|^2 per column, in mapped host
-    // memory: the kernels store there and the host waits for an event behind them
-    struct HostStat {
-        double* p = nullptr;
-        hipEvent_t ev = nullptr;
-        ~HostStat() {
-            if (p) (void)hipHostFree(p);
-            if (ev) (void)hipEventDestroy(ev);
-        }
-    } hs;
-    HIP_CHECK(hipHostMalloc((void**)&hs.p, 6 * G * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_CHECK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
-    double* stat = nullptr;
-    HIP_CHECK(hipHostGetDevicePointer((void**)&stat, hs.p, 0));
+    const std::string g = std::to_string(gmax);
+    ColsWork cw;
+    cw.alloc(N, gmax, m, false,
+             "forward solve: the Krylov bases of (restart + 1) x " + g + " x N = " + std::to_string(m + 1) + " x " + g +
+                 " x " + std::to_string(N),
+             "work buffers");
     arn_small_kernel_attrs();
     solveCalls.clear();
+    const double* sigS = sigmaSTree();
+    // the shared loop over mode 0's x - K_0(sigma_s x)
+    const ColsSolve cs{N, "forward solve",
+                       [&](int nrows, const double* in, double* w) { modeApplyDev(0, nrows, in, N, sigS, true, w, N, s); }};
     int steps = 0;
     try {
         for (int r0 = 0; r0 < nrhs; r0 += G) {
             const int ng = std::min(G, nrhs - r0);
-            steps += forwardSolveGroup(ng, q + (size_t)r0 * ldq, ldq, rhsIsSource, x + (size_t)r0 * ldx, ldx, m, tol,
-                                       maxit, iters + r0, relres ? relres + r0 : nullptr,
-                                       hist ? hist + (size_t)r0 * maxhist : nullptr, hist ? maxhist : 0, bV.as<double>(),
-                                       bB.as<double>(), bIn.as<double>(), bW.as<double>(), bSt.as<double>(),
-                                       bPart.as<double>(), bNb.as<double>(), hs.p, stat, hs.ev, s);
+            const double* qg = q + (size_t)r0 * ldq;
+            // the group's right-hand sides
+            if (rhsIsSource) modeApplyDev(0, ng, qg, ldq, nullptr, false, cw.B.as<double>(), N, s);
+            else
+                HIP_CHECK(hipMemcpy2DAsync(cw.B.p, N * sizeof(double), qg, ldq * sizeof(double), N * sizeof(double), ng,
+                                           hipMemcpyDeviceToDevice, s));
+            steps += colsSolveGroup(cs, cw, ng, x + (size_t)r0 * ldx, ldx, m, tol, maxit, iters + r0,
+                                    relres ? relres + r0 : nullptr, hist ? hist + (size_t)r0 * maxhist : nullptr,
+                                    hist ? maxhist : 0, s);
         }
     } catch (...) {
         (void)hipStreamSynchronize(s);  // no kernel still writes the buffers freed here
@@ -1371,30 +1251,33 @@ int Operator::forwardSolveMultiDev(int nrhs, const double* q, int64_t ldq, bool 
     return steps;
 }
 
-// one group of ng <= arn::kMaxCols columns on the buffers of forwardSolveMultiDev: the
-// right-hand sides, then the shared loop over mode 0's x - K_0(sigma_s x)
-int Operator::forwardSolveGroup(int ng, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx, int m,
-                                double tol, int maxit, int* iters, double* relres, double* hist, int maxhist, double* V,
-                                double* B, double* In, double* W, double* st, double* part, double* dNb, double* hstat,
-                                double* stat, hipEvent_t ev, hipStream_t s) {
-    const int64_t N = geo.N;
-    const double* sigS = sigmaSTree();
-    if (rhsIsSource) modeApplyDev(0, ng, q, ldq, nullptr, false, B, N, s);
-    else
-        HIP_CHECK(hipMemcpy2DAsync(B, N * sizeof(double), q, ldq * sizeof(double), N * sizeof(double), ng,
-                                   hipMemcpyDeviceToDevice, s));
-    const ColsSolve cs{N, "forward solve",
-                       [&](int nrows, const double* in, double* w) { modeApplyDev(0, nrows, in, N, sigS, true, w, N, s); }};
-    return colsSolveGroup(cs, ng, x, ldx, m, tol, maxit, iters, relres, hist, maxhist, V, B, In, W, st, part, dNb, hstat,
-                          stat, ev, s);
+// one group's buffers at row length L (ColsWork, gmres_driver.hpp)
+void ColsWork::alloc(int64_t L, int gmax, int m, bool ownX, const std::string& head, const char* tail,
+                     const std::function<void()>& more) {
+    const int64_t sts = arn::Layout(m).total, pc = (int64_t)(m + 2) * arn::kParts;
+    const size_t row = (size_t)gmax * L * sizeof(double), basis = (size_t)(m + 1) * row;
+    const size_t rest = (size_t)((ownX ? 4 : 3) * L + sts + pc + 1) * gmax * sizeof(double);
+    try {
+        V.alloc(basis);
+        B.alloc(row);
+        In.alloc(row);
+        W.alloc(row);
+        if (ownX) X.alloc(row);
+        st.alloc((size_t)gmax * sts * sizeof(double));
+        part.alloc((size_t)gmax * pc * sizeof(double));
+        dNb.alloc((size_t)gmax * sizeof(double));
+        if (more) more();
+    } catch (const std::exception& e) {
+        throw std::runtime_error(head + " doubles (" + std::to_string(basis) + " bytes) and " + std::to_string(rest) +
+                                 " bytes of " + tail + " could not be allocated: " + e.what());
+    }
+    hs.alloc(6 * arn::kMaxCols);
 }
 
-// The lockstep loop of one group (ColsSolve): every column a restarted GMRES of its own on
-// vectors of cs.L doubles; B holds the right-hand sides.
-int Operator::colsSolveGroup(const ColsSolve& cs, int ng, double* x, int64_t ldx, int m, double tol, int maxit,
-                             int* iters, double* relres, double* hist, int maxhist, double* V, double* B, double* In,
-                             double* W, double* st, double* part, double* dNb, double* hstat, double* stat,
-                             hipEvent_t ev, hipStream_t s) {
+// The lockstep loop of one group (ColsSolve) on the buffers cw: every column a restarted
+// GMRES of its own on vectors of cs.L doubles; cw.B holds the right-hand sides.
+int Operator::colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* x, int64_t ldx, int m, double tol,
+                             int maxit, int* iters, double* relres, double* hist, int maxhist, hipStream_t s) {
     constexpr int G = arn::kMaxCols;
     const int64_t N = cs.L;  // the row length
     const std::string what(cs.what);
@@ -1402,15 +1285,14 @@ int Operator::colsSolveGroup(const ColsSolve& cs, int ng, double* x, int64_t ldx
     const int64_t sts = lay.total, pc = (int64_t)(m + 2) * arn::kParts, vc = (int64_t)(m + 1) * N;
     const arn::ColArgs ca{sts, pc, arn::kParts, 4};
     const unsigned nb = nblk(N);
+    double *V = cw.V.as<double>(), *B = cw.B.as<double>(), *In = cw.In.as<double>(), *W = cw.W.as<double>();
+    double *st = cw.st.as<double>(), *part = cw.part.as<double>(), *dNb = cw.dNb.as<double>();
+    double *hstat = cw.hs.p, *stat = cw.hs.dev;
     struct Col {
         int total = 0, used = 0, nh = 0;
         bool done = false, conv = false, frozen = false, xzero = false;
         double normb = 0.0, rel = 0.0, r = 0.0;
     } col[G];
-    auto wait = [&] {
-        HIP_CHECK(hipEventRecord(ev, s));
-        HIP_CHECK(hipEventSynchronize(ev));
-    };
     auto slot = [&](int c) {
         arn::ColSlot sl{};
         sl.V = V + (size_t)c * vc;
@@ -1452,7 +1334,7 @@ int Operator::colsSolveGroup(const ColsSolve& cs, int ng, double* x, int64_t ldx
         arn::launch_project_cols(N, 1, N, tx, ng, s);
         arn::k_arn_sums_cols<<<ng, arn::kThreads, 0, s>>>(tx, stat + 5 * G);
         HIP_LAUNCH_CHECK();
-        wait();
+        cw.hs.sync(s);
     }
     double normbs[G] = {};
     for (int c = 0; c < ng; ++c) {
@@ -1492,7 +1374,7 @@ int Operator::colsSolveGroup(const ColsSolve& cs, int ng, double* x, int64_t ldx
                                                            1.0, stat + 4 * c0, ca, dNb + c0);
         });
         HIP_LAUNCH_CHECK();
-        wait();
+        cw.hs.sync(s);
         for (int c : cols) {
             if (hstat[4 * c + 2] != 0.0) throw std::runtime_error(what + ": a cycle's start left no status");
             col[c].rel = hstat[4 * c];
@@ -1538,7 +1420,7 @@ int Operator::colsSolveGroup(const ColsSolve& cs, int ng, double* x, int64_t ldx
                     m, j, st + (size_t)c0 * sts, part + (size_t)c0 * pc, arn::kParts, stat + 4 * c0, ca);
             });
             HIP_LAUNCH_CHECK();
-            wait();
+            cw.hs.sync(s);
             for (int c : live) {
                 Col& k = col[c];
                 if (hstat[4 * c + 2] != (double)(j + 1))
@@ -1608,12 +1490,8 @@ constexpr int kBlockGroup = 4;  // sources per group: one chunk of blockOpMultiD
 
 bool Operator::blockSolveMultiCheck(const char* what, int nsrc, const void* q, int64_t ldq, const void* x, int64_t ldx,
                                     const int* iters, int restart, double tol, int maxit) const {
-    const std::string w(what);
-    if (restart < 1 || restart > 400)
-        throw std::invalid_argument(w + ": restart must be in [1, 400], got " + std::to_string(restart));
-    if (!(tol > 0.0)) throw std::invalid_argument(w + ": tol must be > 0");
-    if (maxit < 0) throw std::invalid_argument(w + ": maxit must be >= 0, got " + std::to_string(maxit));
-    if (nsrc > 0 && !iters) throw std::invalid_argument(w + ": iters is NULL");
+    checkColsSolveParams(what, restart, tol, maxit);
+    if (nsrc > 0 && !iters) throw std::invalid_argument(std::string(what) + ": iters is NULL");
     return blockOpMultiCheck(what, 2, nsrc, q, ldq, x, ldx);  // the rows, their overlap and the handle's state
 }
 
@@ -1627,41 +1505,15 @@ int Operator::blockSolveMultiDev(int nsrc, const double* q, int64_t ldq, bool rh
     static_assert(kBlockGroup <= G, "a group fits the column tables");
     const int64_t N = geo.N, L = (int64_t)ks * N;
     const int m = restart, gmax = std::min(nsrc, kBlockGroup);
-    const arn::Layout lay(m);
-    const int64_t sts = lay.total, pc = (int64_t)(m + 2) * arn::kParts, vc = (int64_t)(m + 1) * L;
-    // every buffer of one group, allocated before anything is launched
-    DevBuf bV, bB, bIn, bW, bX, bSt, bPart, bNb;
-    const size_t basis = (size_t)vc * gmax * sizeof(double);
-    const size_t rest = (size_t)(4 * L + sts + pc + 1) * gmax * sizeof(double);
-    try {
-        bV.alloc(basis);
-        bB.alloc((size_t)gmax * L * sizeof(double));
-        bIn.alloc((size_t)gmax * L * sizeof(double));
-        bW.alloc((size_t)gmax * L * sizeof(double));
-        bX.alloc((size_t)gmax * L * sizeof(double));
-        bSt.alloc((size_t)gmax * sts * sizeof(double));
-        bPart.alloc((size_t)gmax * pc * sizeof(double));
-        bNb.alloc((size_t)gmax * sizeof(double));
-        if (highOrder() && ks <= kMaxRhs) blockMultiReserve(gmax == 3 ? 4 : gmax);
-    } catch (const std::exception& e) {
-        throw std::runtime_error("multi-source block solve: the Krylov bases of (restart + 1) x " + std::to_string(gmax) +
-                                 " x ks x N = " + std::to_string(m + 1) + " x " + std::to_string(gmax) + " x " +
-                                 std::to_string(ks) + " x " + std::to_string(N) + " doubles (" + std::to_string(basis) +
-                                 " bytes) and " + std::to_string(rest) +
-                                 " bytes of work rows could not be allocated: " + e.what());
-    }
-    struct HostStat {
-        double* p = nullptr;
-        hipEvent_t ev = nullptr;
-        ~HostStat() {
-            if (p) (void)hipHostFree(p);
-            if (ev) (void)hipEventDestroy(ev);
-        }
-    } hs;
-    HIP_CHECK(hipHostMalloc((void**)&hs.p, 6 * G * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_CHECK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
-    double* stat = nullptr;
-    HIP_CHECK(hipHostGetDevicePointer((void**)&stat, hs.p, 0));
+    const std::string g = std::to_string(gmax);
+    ColsWork cw;  // X: the group's guesses as compact vectors
+    cw.alloc(L, gmax, m, true,
+             "multi-source block solve: the Krylov bases of (restart + 1) x " + g + " x ks x N = " +
+                 std::to_string(m + 1) + " x " + g + " x " + std::to_string(ks) + " x " + std::to_string(N),
+             "work rows", [&] {
+                 if (highOrder() && ks <= kMaxRhs) blockMultiReserve(gmax == 3 ? 4 : gmax);
+             });
+    DevBuf &bB = cw.B, &bX = cw.X;
     arn_small_kernel_attrs();
     solveCalls.clear();
     const ColsSolve cs{L, "multi-source block solve", [&](int nrows, const double* in, double* w) {
@@ -1683,10 +1535,9 @@ int Operator::blockSolveMultiDev(int nsrc, const double* q, int64_t ldq, bool rh
                 HIP_CHECK(hipMemcpy2DAsync(bB.p, N * sizeof(double), qg, ldq * sizeof(double), N * sizeof(double),
                                            (size_t)ng * ks, hipMemcpyDeviceToDevice, s));
             }
-            steps += colsSolveGroup(cs, ng, bX.as<double>(), L, m, tol, maxit, iters + r0, relres ? relres + r0 : nullptr,
-                                    hist ? hist + (size_t)r0 * maxhist : nullptr, hist ? maxhist : 0, bV.as<double>(),
-                                    bB.as<double>(), bIn.as<double>(), bW.as<double>(), bSt.as<double>(),
-                                    bPart.as<double>(), bNb.as<double>(), hs.p, stat, hs.ev, s);
+            steps += colsSolveGroup(cs, cw, ng, bX.as<double>(), L, m, tol, maxit, iters + r0,
+                                    relres ? relres + r0 : nullptr, hist ? hist + (size_t)r0 * maxhist : nullptr,
+                                    hist ? maxhist : 0, s);
             HIP_CHECK(hipMemcpy2DAsync(xg, ldx * sizeof(double), bX.p, N * sizeof(double), N * sizeof(double),
                                        (size_t)ng * ks, hipMemcpyDeviceToDevice, s));
         }
