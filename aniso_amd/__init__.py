@@ -85,6 +85,7 @@ def lib():
             "aniso_block_solve_multi_dev": [P, I, P, I64, I, P, I64, I, D, I, ip, dp, dp, I, P],
             "aniso_block_solve_multi": [P, dp, I, I, dp, I, D, I, ip, dp],
             "aniso_forward_solve_calls": [P, ip, I, ip],
+            "aniso_mode_apply_calls": [P, ip, I, ip],
             "aniso_mapping_stages_dev": [P, P, I, I, P, P],
             "aniso_set_shard": [P, I, I],
             "aniso_get_shard": [P, lp, lp],
@@ -365,8 +366,8 @@ class Aniso:
     def mapping_multi_dev(self, X, id_, Out, stream=None):
         """Out[k] = K_id X[k]: X and Out are (nrhs, >= N) float64 CUDA tensors with unit column
         stride (strided rows allowed; entries past N of a row are left alone).  One mode on
-        several vectors wherever the mode is ready: on a high-order handle 8 columns per read
-        of the mode-shared caches, on a lean np = 4 mode one mapping_dev pass per column."""
+        several vectors wherever the mode is ready: on a high-order handle and on a lean
+        np = 4 mode 8 columns per read of the mode-shared caches."""
         import torch
 
         nrhs = int(X.shape[0]) if isinstance(X, torch.Tensor) and X.dim() == 2 else -1
@@ -442,6 +443,19 @@ class Aniso:
         counts = np.zeros(max(n.value, 1), dtype=np.int32)
         _check(lib().aniso_forward_solve_calls(self.address, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
                                                n.value, ctypes.byref(n)))
+        return counts[: n.value]
+
+    def mode_apply_calls(self):
+        """The compiled column count K of every operator pass of the last mapping_multi(_dev) /
+        forward_multi_dev call (after a forward_solve_multi(_dev): of its last operator call).
+        The mode kernels (np = 6, 8, or a lean np = 4 mode) run chunks of up to 8 columns padded
+        to 2, 4, 5 or 8: 11 columns give [8, 4].  A resident np = 4 mode gives one entry per
+        chunk of the block apply's batched branch (1, 2, 4, 5 or 8)."""
+        n = ctypes.c_int()
+        _check(lib().aniso_mode_apply_calls(self.address, None, 0, ctypes.byref(n)))
+        counts = np.zeros(max(n.value, 1), dtype=np.int32)
+        _check(lib().aniso_mode_apply_calls(self.address, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                            n.value, ctypes.byref(n)))
         return counts[: n.value]
 
     def mapping_dev(self, charge, id_, out, stream=None, mask=STAGE_ALL):

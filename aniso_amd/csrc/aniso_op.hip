@@ -1622,33 +1622,118 @@ void Operator::modeApplyHigh(int id, int K, const double* x, int64_t ldx, const 
     }
 }
 
+// One chunk on a lean mode of an np = 4 handle: one pass of the offset form as leanMapping
+// ends up running it, un-fused, with the mode kernels in place of the offset near field and
+// M2L.  launch_prepare forms the (sigma-weighted) charges; the near field stores `out`, the
+// corrections of mode id (identity fold) add to it; the rank-16 up tiers on the K plain
+// columns, the mode M2L (plain sums into dLocal) and the down tiers, the last writer
+// (minuend: x - K_id(...), original order).  One stream, every sum in a fixed order.
+void Operator::modeApplyLean16(int id, int K, const double* x, int64_t ldx, const double* sigT, const double* minuend,
+                               int64_t minuendLd, double* out, int64_t ldo, hipStream_t s) {
+    ensureWork(K);
+    if (up_tier_lds(plan.upMaxTask, K) > 160 * 1024 ||
+        down_tier_lds(plan.dnMaxTask, plan.dnMaxLeaves, plan.dnMaxNear, plan.dnMaxChain, K) > 160 * 1024)
+        throw std::logic_error("up/down pass task exceeds one workgroup's LDS at " + std::to_string(K) + " right-hand sides");
+    const Params* P = dParams.as<Params>();
+    std::vector<double> eye((size_t)K * K, 0.0);
+    for (int i = 0; i < K; ++i) eye[(size_t)i * K + i] = 1.0;
+    const CorrFold& cf = corrTable(K, 1, &id, eye.data());
+    const bool tr = timeStages != 0, tm = timeStages == 1;
+    auto span = [&](int stage, int a, int b) {
+        if (a >= 0 && b >= 0) spans.push_back({stage, a, b});
+    };
+    const int* operm = dPerm.as<int>();
+    const double scale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
+    const int nl = (int)plan.leaves.size();
+    const int ntier = (int)plan.upTierTask.size() - 1;  // 0: a lone leaf
+    const int e0 = tr ? mark(s) : -1;
+    launch_prepare(K, geo.N, x, ldx, 0, dPerm.as<int>(), sigT, dWT.as<double>(), dFT.as<double>(), dCT.as<double>(), s);
+    launch_near_mode(K, id, nl, plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(),
+                     dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
+                     dSigDiag.as<double>(), dFT.as<double>(), operm, 0, ldo, scale, out, s);
+    const int e1 = tr ? mark(s) : -1;
+    span(4, e0, e1);
+    launch_corr(K, geo.d, plan.ownBegin, plan.ownEnd, dPerm.as<int>(), dIperm.as<int>(), dCT.as<double>(),
+                dFT.as<double>(), cf.Wc.as<double>(), cf.Wm.as<double>(), P, kStageAll, scale, false, ldo, out, s);
+    const int e2 = tr ? mark(s) : -1;
+    if (tm) span(6, e1, e2);
+    // (the up tiers form their charges from the input again and store none: launch_prepare did)
+    for (int k = 0; k < ntier; ++k)
+        launch_up_tier(K, plan.upTierTask[k + 1] - plan.upTierTask[k], plan.upTierTask[k], nullptr, plan.upTierMaxTask[k],
+                       dUpDesc.as<int4>(), dUpGrpFix.as<int>(), dUpNode.as<int>(), dUpCode.as<int4>(),
+                       dUpGeom.as<double4>(), dUpLeaf.as<int2>(), dPxT.as<double>(), dPyT.as<double>(), x, ldx, 0,
+                       dPerm.as<int>(), sigT, dWT.as<double>(), nullptr, nullptr, P, dMult.as<double>(), nullptr, nullptr,
+                       nullptr, nullptr, s);
+    const int e3 = tr ? mark(s) : -1;
+    if (tm) span(1, e2, e3);
+    launch_m2l_mode16(K, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
+                      dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
+                      dNry.as<double>(), P, dMult.as<double>(), dLocal.as<double>(), s);
+    const int e4 = tr ? mark(s) : -1;
+    span(2, e3, e4);
+    launch_down_tier(K, (int)plan.dnDesc.size() / 3, plan.dnMaxTask, plan.dnMaxLeaves, dDnDesc.as<int4>(),
+                     dDnGrpFix.as<int>(), dDnNode.as<int4>(), dLocal.as<double>(), P, dDnLeafSlot.as<int>(),
+                     dDnLeafPts.as<int>(), dDnLeafNear.as<int2>(), dDnLeafGeom.as<double4>(), dPxT.as<double>(),
+                     dPyT.as<double>(), operm, 0, ldo, dDnNearOff.as<int>(), plan.dnMaxNear, nullptr, dDnChain.as<int2>(),
+                     plan.dnMaxChain, kStageAll, scale, out, minuend, minuendLd, s, nullptr, dDnChainFold.as<int>());
+    if (tr) {
+        const int e5 = mark(s);
+        if (tm) span(5, e4, e5);
+        span(7, e0, e5);
+        ++applies;
+    }
+}
+
 void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, const double* sigT, bool minuend,
-                            double* out, int64_t ldo, hipStream_t s) {
+                            double* out, int64_t ldo, hipStream_t s, bool keepCalls) {
     if (!modeApplyCheck("mode apply", id, nrhs, x, ldx, out, ldo, minuend)) return;
     checkDeviceErrors();
     ensureDevice();
+    if (!keepCalls) modeCalls.clear();
     const int64_t N = geo.N;
-    if (highOrder()) {
+    // a lean mode of an np = 4 handle on the mode-shared caches (leanMapping's conditions;
+    // the mode kernels read the directed near blocks)
+    const bool lean16 = !highOrder() && !modes[id].resident && useAtt && attReady && plan.nearPartTotal == 0 &&
+                        !plan.nearSymHsOn;
+    // its down tiers are the last writer of every point and fuse the forward form's
+    // subtraction; a lone leaf has none and goes through the buffer below
+    const bool viaBuffer = minuend && !highOrder() && !(lean16 && !plan.dnDesc.empty());
+    if (highOrder() || lean16) {
+        double* dst = out;
+        int64_t ldd = ldo;
+        if (viaBuffer) {
+            if (dBlk.bytes < (size_t)nrhs * N * sizeof(double)) dBlk.alloc((size_t)nrhs * N * sizeof(double));
+            dst = dBlk.as<double>();
+            ldd = N;
+        }
+        const bool sub = minuend && !viaBuffer;
+        auto chunk = [&](int K, const double* xc, int64_t ldc, double* oc, int64_t ldoc) {
+            if (lean16) modeApplyLean16(id, K, xc, ldc, sigT, sub ? xc : nullptr, ldc, oc, ldoc, s);
+            else modeApplyHigh(id, K, xc, ldc, sigT, sub ? xc : nullptr, ldc, oc, ldoc, s);
+            modeCalls.push_back(K);
+        };
         for (int j0 = 0; j0 < nrhs; j0 += kMaxRhs) {
             const int nb = std::min(kMaxRhs, nrhs - j0);
             const int K = nb == 1 ? 2 : rhs_padded(nb);  // (the mode kernels start at 2 columns)
             const double* xc = x + (size_t)j0 * ldx;
-            double* oc = out + (size_t)j0 * ldo;
+            double* oc = dst + (size_t)j0 * ldd;
             if (K == nb) {
-                modeApplyHigh(id, K, xc, ldx, sigT, minuend ? xc : nullptr, ldx, oc, ldo, s);
+                chunk(K, xc, ldx, oc, ldd);
                 continue;
             }
             // zero columns pad the chunk to the next compiled count, as applyBlock pads
-            dPadIn.alloc((size_t)K * N * sizeof(double));
-            dPadOut.alloc((size_t)K * N * sizeof(double));
-            HIP_CHECK(hipMemsetAsync(dPadIn.p, 0, (size_t)K * N * sizeof(double), s));
+            // (the buffers grow and never shrink: a solve's active columns change the count)
+            const size_t pb = (size_t)K * N * sizeof(double);
+            if (dPadIn.bytes < pb) dPadIn.alloc(pb);
+            if (dPadOut.bytes < pb) dPadOut.alloc(pb);
+            HIP_CHECK(hipMemsetAsync(dPadIn.p, 0, pb, s));
             HIP_CHECK(hipMemcpy2DAsync(dPadIn.p, N * sizeof(double), xc, ldx * sizeof(double), N * sizeof(double), nb,
                                        hipMemcpyDeviceToDevice, s));
-            modeApplyHigh(id, K, dPadIn.as<double>(), N, sigT, minuend ? dPadIn.as<double>() : nullptr, N,
-                          dPadOut.as<double>(), N, s);
-            HIP_CHECK(hipMemcpy2DAsync(oc, ldo * sizeof(double), dPadOut.p, N * sizeof(double), N * sizeof(double), nb,
+            chunk(K, dPadIn.as<double>(), N, dPadOut.as<double>(), N);
+            HIP_CHECK(hipMemcpy2DAsync(oc, ldd * sizeof(double), dPadOut.p, N * sizeof(double), N * sizeof(double), nb,
                                        hipMemcpyDeviceToDevice, s));
         }
+        if (viaBuffer) launch_sub_slice(N, nrhs, x, ldx, dBlk.as<double>(), N, out, ldo, s);
         return;
     }
     // np = 4.  The forward form goes through a buffer: the applies store K_id(...) there
@@ -1668,9 +1753,13 @@ void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, cons
             ApplyCall call;
             applyBlock(nb, x + (size_t)j0 * ldx, ldx, false, sigT, 1, &id, eye.data(), dst + (size_t)j0 * ldd, ldd, false,
                        s, kStageAll, call);
+            modeCalls.push_back(rootRhs(nb));  // (applyBlock pads the chunk to the next compiled count)
         }
-    } else {  // a lean mode: one pass of the offset form per column
-        for (int j = 0; j < nrhs; ++j) leanMapping(x + (size_t)j * ldx, id, dst + (size_t)j * ldd, s, kStageAll, sigT);
+    } else {  // a lean mode the mode kernels do not serve: one pass of the offset form per column
+        for (int j = 0; j < nrhs; ++j) {
+            leanMapping(x + (size_t)j * ldx, id, dst + (size_t)j * ldd, s, kStageAll, sigT);
+            modeCalls.push_back(kMaxRhs);
+        }
     }
     if (minuend) launch_sub_slice(N, nrhs, x, ldx, dBlk.as<double>(), N, out, ldo, s);
 }
@@ -1684,10 +1773,11 @@ void Operator::mappingMultiHost(const double* Q, int k, int id, double* Out) {
     DevBuf dq, dout;
     dq.alloc((size_t)kb * N * sizeof(double));
     dout.alloc((size_t)kb * N * sizeof(double));
+    modeCalls.clear();
     for (int j0 = 0; j0 < k; j0 += kb) {
         const int nb = std::min(kb, k - j0);
         HIP_CHECK(hipMemcpyAsync(dq.p, Q + (size_t)j0 * N, (size_t)nb * N * sizeof(double), hipMemcpyHostToDevice, own));
-        modeApplyDev(id, nb, dq.as<double>(), N, nullptr, false, dout.as<double>(), N, own);
+        modeApplyDev(id, nb, dq.as<double>(), N, nullptr, false, dout.as<double>(), N, own, true);
         HIP_CHECK(hipMemcpyAsync(Out + (size_t)j0 * N, dout.p, (size_t)nb * N * sizeof(double), hipMemcpyDeviceToHost,
                                  own));
         HIP_CHECK(hipStreamSynchronize(own));

@@ -124,14 +124,21 @@ public:
     // A high-order handle runs chunks of 8 columns (a remainder zero-padded to 2, 4 or 8)
     // through the mode kernels of mode_apply.hip on the mode-shared caches: the entry's
     // factor is formed once per chunk.  np = 4: a resident mode runs applyBlock's identity
-    // mix in chunks of 8; a lean mode runs ONE leanMapping PER COLUMN -- correct, and a
-    // whole 8-row pass over the shared caches for every column (no rank-16 mode kernel).
+    // mix in chunks of 8; a lean mode runs the same chunks through modeApplyLean16 (the
+    // near-field mode kernel and the rank-16 mode M2L between the up and down tiers), one
+    // read of the shared caches per chunk.  (A handle whose harmonic near field keeps
+    // symmetric U storage, ANISO_NEAR_HS_SYM, runs one leanMapping per column.)
     // modeApplyCheck raises everything that can be refused before the device is touched
     // (false: nrhs = 0, nothing to do).
     bool modeApplyCheck(const char* what, int id, int nrhs, const void* x, int64_t ldx, const void* out, int64_t ldo,
                         bool minuend) const;
+    // keepCalls: append to modeApplyCalls() (a caller that cuts one call into several)
     void modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, const double* sigT, bool minuend, double* out,
-                      int64_t ldo, hipStream_t s);
+                      int64_t ldo, hipStream_t s, bool keepCalls = false);
+    // the compiled column count K of every operator pass of the last modeApplyDev /
+    // mappingMultiHost call, in order: a mode-kernel chunk (2, 4, 5 or 8), a resident
+    // np = 4 mode's applyBlock chunk (1, 2, 4, 5 or 8), 8 for a per-column leanMapping pass
+    const std::vector<int>& modeApplyCalls() const { return modeCalls; }
     void mappingMultiHost(const double* Q, int k, int id, double* Out);  // N x k column-major
     const double* sigmaSTree() const { return dSigmaT.as<double>(); }    // sigma_s in tree order (device)
     void mappingDev(const double* charge, int id, double* out, hipStream_t s, int stageMask = 0x3f);
@@ -478,6 +485,9 @@ private:
     // modeApplyDev's chunk of K = 2, 4, 5 or 8 columns on a high-order handle
     void modeApplyHigh(int id, int K, const double* x, int64_t ldx, const double* sigT, const double* minuend,
                        int64_t minuendLd, double* out, int64_t ldo, hipStream_t s);
+    // modeApplyDev's chunk of K = 2, 4, 5 or 8 columns on a lean mode of an np = 4 handle
+    void modeApplyLean16(int id, int K, const double* x, int64_t ldx, const double* sigT, const double* minuend,
+                         int64_t minuendLd, double* out, int64_t ldo, hipStream_t s);
     // the modes of a batched apply are usable by it: tables for the harmonic launches,
     // resident operators for the per-mode stream (checked before anything is launched)
     void checkModes(int K, int nterm, const int* ids, const double* mixes, const ApplyCall& call) const;
@@ -547,6 +557,7 @@ private:
     int gmresRestarted(const GmresSystem& g, StatusBlock& hs, double tol, int maxit, double* hist, int maxhist,
                        double* relres, hipStream_t s);
     std::vector<int> solveCalls;
+    std::vector<int> modeCalls;  // modeApplyCalls()
     void arnoldiParts(int rows);  // dKryPart for sweeps of `rows` rows
     bool topTraceOn = false;
     int hmRing = 0;  // the cluster M2L's LDS ring depth (ANISO_HM_RING; 0: the one-block-in-flight form)

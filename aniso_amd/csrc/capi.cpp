@@ -301,6 +301,17 @@ int aniso_forward_solve_calls(aniso_handle h, int* counts, int cap, int* n) {
     });
 }
 
+int aniso_mode_apply_calls(aniso_handle h, int* counts, int cap, int* n) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(n);
+        const auto& c = get(h).modeApplyCalls();
+        *n = (int)c.size();
+        if (counts)
+            for (int i = 0; i < cap && i < (int)c.size(); ++i) counts[i] = c[i];
+    });
+}
+
 int aniso_forward_dev(aniso_handle h, const double* u, double* out, void* stream) {
     ENTER(h);
     return guarded([&] {

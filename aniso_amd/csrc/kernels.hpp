@@ -422,8 +422,9 @@ void launch_ho_l2p(int np, int K, int nl, const int4* leafInfo, const double* nc
                    const double* nrx, const double* nry, const double* pxT, const double* pyT, const HoTables* T,
                    const double* local, const int* operm, int64_t obase, int64_t ldo, double scale, double* out,
                    const double* xsub, int64_t ldx, hipStream_t s);
-// ---- one mode on K columns of a high-order handle (mode_apply.hip): K in
-// {2, 4, 5, 8}, the entry's factor (E / r) T_id(c) formed once for all K columns.
+// ---- one mode on K columns on the mode-shared caches (mode_apply.hip): a
+// high-order handle, or a lean mode of an np = 4 one.  K in {2, 4, 5, 8}, the entry's factor
+// (E / r) T_id(c) formed once for all K columns.
 // launch_near_hm's unstaged kernel for mode id: out (stored) = scale * (near field + the
 // sigma_t diagonal when id = 0); fT from launch_prepare
 void launch_near_mode(int K, int id, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
@@ -434,6 +435,12 @@ void launch_near_mode(int K, int id, int nl, int maxLeaf, const int4* leafInfo, 
 void launch_ho_m2l_mode(int np, int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
                         const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
                         const double* nry, const HoTables* T, const double* mult, double* local, hipStream_t s);
+// launch_m2l_hm for mode id on a rank-16 (np = 4) handle: mult [node][16][K] as the up tiers
+// leave it, local = the plain sums of every listed target (the down tiers read them as they
+// are); ntgt = 0 launches nothing.  A column's bits do not depend on K or on its slot.
+void launch_m2l_mode16(int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk,
+                       const double* E, const double* ncx, const double* ncy, const double* nrx, const double* nry,
+                       const Params* P, const double* mult, double* local, hipStream_t s);
 // ---- the block operator for S sources per read of the E blocks (block_multi.hip, DESIGN.md
 // §3.18.3): launch_ho_m2l (whole operator, no window) on S in {1, 2, 4} multipole buffers
 // mult + j * mstride into S local buffers local + j * lstride, each [node][R][K].  A

@@ -9,6 +9,8 @@
 // id -- is formed once and applied to the K columns with one FMA each.  There are no
 // harmonic weights: the staged multipole is the P2M's own and the stored local is the
 // plain sum, so P2M, M2M, L2L and L2P of high_order.hip run unchanged around the M2L.
+// A lean np = 4 handle runs the same near field and the rank-16 M2L k_m2l_mode16 between
+// the up and down tiers of apply.hip.
 // Every sum runs in a fixed order and there are no atomics: repeats are bitwise equal.
 #include <hip/hip_runtime.h>
 
@@ -113,6 +115,120 @@ __global__ void __launch_bounds__(256) k_ho_m2l_mode(const int* __restrict__ tgt
 #pragma unroll
         for (int p = 1; p < NPH; ++p) v += TL[p * RK + i];
         local[(size_t)n * RK + i] = v;
+    }
+}
+
+// ----------------------------------------------------------------- M2L, rank 16
+
+// PG blocks of one wave's pair list, as lane (s, q) holds them: rows 4q .. 4q+3 of column s
+// of each E block, the K columns of entry s of each source's multipole, the source nodes
+template <int K, int PG>
+struct M16Group {
+    double e4[PG][4];
+    double xm[PG][K];
+    int B[PG];
+};
+
+// issue the loads of blocks j0 .. j0 + PG - 1 of the wave's cnt pairs (mySrc / myBlk: lane
+// j holds pair j).  A block past cnt is a valid clamp with E = 0: its factor is 0.
+template <int K, int PG>
+__device__ __forceinline__ void m16_load(M16Group<K, PG>& g, int j0, int cnt, int mySrc, int myBlk, int s, int q,
+                                         const double* __restrict__ E, const double* __restrict__ mult) {
+#pragma unroll
+    for (int i = 0; i < PG; ++i) {
+        const int b = __builtin_amdgcn_readlane(myBlk, min(j0 + i, cnt - 1));
+        const bool tr = b < 0;
+        const double* p = E + (size_t)(tr ? ~b : b) * 256 + (tr ? 64 * q + s : 16 * s + 4 * q);
+        const int st = tr ? 16 : 1;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) g.e4[i][j] = j0 + i < cnt ? p[j * st] : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < PG; ++i) {
+        g.B[i] = __builtin_amdgcn_readlane(mySrc, min(j0 + i, cnt - 1));
+        const double* m = mult + ((size_t)g.B[i] * kRank + s) * K;
+#pragma unroll
+        for (int k = 0; k < K; ++k) g.xm[i][k] = m[k];
+    }
+}
+
+// k_m2l_hm for one mode and K columns (np = 4): one wave per target node, four targets per
+// workgroup; every directed pair's 2 KB E block read once as 64 lanes x 32 B (column-major:
+// lane (s, q) holds column s, rows 4q .. 4q+3), a pair listed as ~blk read transposed
+// (stride 16).  Two groups of PG blocks rotate: the next group's loads are issued before
+// the current group's arithmetic (the rank-16 M2L is bound by load latency, DESIGN.md
+// §3.10), so 2 PG blocks are in flight per wave.  Per entry the factor (E / r) T_id(c) and
+// one FMA per column; the 16 columns are summed with k_m2l_hm's __shfl_xor tree.  The
+// stored local is the plain sum (no harmonic weights): the rank-16 up and down tiers run
+// unchanged around it.  Every target of the list is stored, one with no pair as zero.
+template <int K, int PG, int WPE>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) k_m2l_mode16(int ntgt, const int* __restrict__ tgt, const int64_t* __restrict__ ptr,
+                                                    const int* __restrict__ src, const int* __restrict__ blk,
+                                                    const double* __restrict__ E, const double* __restrict__ ncx,
+                                                    const double* __restrict__ ncy, const double* __restrict__ nrx,
+                                                    const double* __restrict__ nry, const Params* __restrict__ P, int id,
+                                                    const double* __restrict__ mult, double* __restrict__ local) {
+    const int wave =
+        __builtin_amdgcn_readfirstlane((int)blockIdx.x * (int)(blockDim.x / kWave) + (int)(threadIdx.x / kWave));
+    const int lane = threadIdx.x & (kWave - 1);
+    if (wave >= ntgt) return;
+    const int n = tgt[wave];
+    const int s = lane >> 2, q = lane & 3;
+    double bx[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bx[j] = ncx[n] + nrx[n] * P->cheb[j];
+    const double by = ncy[n] + nry[n] * P->cheb[q];
+    const double chx = P->cheb[s & 3], chy = P->cheb[s >> 2];
+    double c[4][K];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < K; ++k) c[j][k] = 0.0;
+    // a group's arithmetic: dx = source minus target, so an odd mode keeps its sign
+    auto apply = [&](const M16Group<K, PG>& g) {
+#pragma unroll
+        for (int i = 0; i < PG; ++i) {
+            const double ax = ncx[g.B[i]] + nrx[g.B[i]] * chx;
+            const double dy = (ncy[g.B[i]] + nry[g.B[i]] * chy) - by;
+            const double dy2 = dy * dy;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double f = mode_factor<false>(g.e4[i][j], ax - bx[j], dy2, id);
+#pragma unroll
+                for (int k = 0; k < K; ++k) c[j][k] = __builtin_fma(f, g.xm[i][k], c[j][k]);
+            }
+        }
+    };
+    const int64_t p0 = ptr[wave], p1 = ptr[wave + 1];
+    for (int64_t cb = p0; cb < p1; cb += kWave) {
+        const int cnt = (int)min<int64_t>(kWave, p1 - cb);
+        const int mySrc = lane < cnt ? src[cb + lane] : 0;
+        const int myBlk = lane < cnt ? blk[cb + lane] : 0;
+        M16Group<K, PG> ga, gb;
+        m16_load<K, PG>(ga, 0, cnt, mySrc, myBlk, s, q, E, mult);
+        for (int j0 = 0; j0 < cnt; j0 += 2 * PG) {
+            const bool more = j0 + PG < cnt;  // (wave-uniform)
+            if (more) m16_load<K, PG>(gb, j0 + PG, cnt, mySrc, myBlk, s, q, E, mult);
+            apply(ga);
+            if (j0 + 2 * PG < cnt) m16_load<K, PG>(ga, j0 + 2 * PG, cnt, mySrc, myBlk, s, q, E, mult);
+            if (more) apply(gb);
+        }
+    }
+    // sum over the 16 columns (lane bits 2..5); row t = 4q' + j is entry j of the lanes
+    // with q == q' (lane 4t + (t >> 2) holds row t = s), as k_m2l_hm
+#pragma unroll
+    for (int off = 4; off < kWave; off <<= 1)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int k = 0; k < K; ++k) c[j][k] += __shfl_xor(c[j][k], off);
+    const int jr = s & 3, srcLane = 4 * s + (s >> 2);
+    double* dst = local + ((size_t)n * kRank + s) * K;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double sel = jr == 0 ? c[0][k] : jr == 1 ? c[1][k] : jr == 2 ? c[2][k] : c[3][k];
+        const double v = __shfl(sel, srcLane);
+        if ((k & 3) == q) dst[k] = v;
     }
 }
 
@@ -289,6 +405,19 @@ void launch_ho_m2l_mode(int np, int K, int id, int ntgt, const int* tgt, const i
     } else {
         throw std::invalid_argument("mode apply: np must be 6 or 8");
     }
+    HIP_LAUNCH_CHECK();
+}
+
+void launch_m2l_mode16(int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk,
+                       const double* E, const double* ncx, const double* ncy, const double* nrx, const double* nry,
+                       const Params* P, const double* mult, double* local, hipStream_t s) {
+    if (ntgt <= 0) return;
+    if (id < 0) throw std::invalid_argument("mode apply: negative mode");
+    const unsigned nb = blocks_for((int64_t)ntgt * kWave, 256);
+    // one block per group, two groups: 2 blocks in flight per wave at 4 (K = 2), 3 (K = 4, 5) and
+    // 2 (K = 8) waves per SIMD, the most each instance holds without scratch
+    ANISO_MODE_DISPATCH_K(K, (k_m2l_mode16<KK, 1, (KK <= 2 ? 4 : KK <= 5 ? 3 : 2)><<<nb, 256, 0, s>>>(
+                                 ntgt, tgt, ptr, src, blk, E, ncx, ncy, nrx, nry, P, id, mult, local)));
     HIP_LAUNCH_CHECK();
 }
 

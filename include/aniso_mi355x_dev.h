@@ -144,6 +144,18 @@ int aniso_arnoldi16_solution(aniso_handle h, int64_t n16, int m, int used, const
  * group's forward(charge) call)
  * (tools/forward_solve_time.py, tools/block_multi_time.py).  Host only. */
 int aniso_forward_solve_calls(aniso_handle h, int *counts, int cap, int *n);
+/* ---- one mode on several vectors ---- */
+/* the operator passes of the handle's last aniso_mapping_multi(_dev) / aniso_forward_multi_dev
+ * call (an operator call of aniso_forward_solve_multi(_dev) counts as one: after a solve the
+ * list is its last call's): *n = their number, counts (cap >= 0 entries, may be NULL) = the
+ * compiled column count K of each, in order.  A pass through the mode kernels (np = 6, 8,
+ * or a lean mode at np = 4) is one chunk of up to 8 columns padded to K = 2, 4, 5 or 8: 11
+ * columns report {8, 4}, one column {2}.  A mode made resident by aniso_cache(h, id) at
+ * np = 4 runs the batched branch of the block apply: one entry per chunk of up to 8 columns,
+ * K = 1, 2, 4, 5 or 8 (11 columns: {8, 4}; one column: {1}).  A lean np = 4 mode the mode
+ * kernels do not serve (ANISO_NEAR_HS_SYM=1) reports 8, the offset form's rows, once per
+ * column.  Host only. */
+int aniso_mode_apply_calls(aniso_handle h, int *counts, int cap, int *n);
 
 #ifdef __cplusplus
 }
