@@ -62,6 +62,7 @@ def lib():
         fp = ctypes.POINTER(ctypes.c_float)
         sig = {
             "aniso_create": [I, I, I, D, I, I, I, ctypes.POINTER(P)],
+            "aniso_create_sharded": [I, I, I, D, I, I, I, I, I, ctypes.POINTER(P)],
             "aniso_destroy": [P],
             "aniso_num_nodes": [P, lp],
             "aniso_num_blocks": [P, ip],
@@ -277,12 +278,21 @@ class Aniso:
     ds: squares per side, qr: quadrature rule, ks: kernel size (modes 0..2ks-2),
     as: anisotropy g, sr: singular rule, fn: FMM np (4, or 6 / 8: a high-order handle,
     which runs mapping, the block operator and its solve on the mode-shared caches only),
-    fm: FMM maxLevel.
+    fm: FMM maxLevel.  shard=(rank, nranks): the handle of one rank of a sharded operator
+    (aniso_create_sharded) -- at fn = 4 the same as set_shard(rank, nranks) afterwards, at
+    fn = 6 / 8 a sharded high-order handle, which runs block_op_sharded_dev,
+    block_op_dev(tree=True) and block_solve_sharded_dev only (ks <= 8).
     """
 
-    def __init__(self, ds, qr, ks, as_, sr, fn, fm):
+    def __init__(self, ds, qr, ks, as_, sr, fn, fm, shard=None):
         h = ctypes.c_void_p()
-        _check(lib().aniso_create(int(ds), int(qr), int(ks), float(as_), int(sr), int(fn), int(fm), ctypes.byref(h)))
+        if shard is None:
+            _check(lib().aniso_create(int(ds), int(qr), int(ks), float(as_), int(sr), int(fn), int(fm),
+                                      ctypes.byref(h)))
+        else:
+            rank, nranks = shard
+            _check(lib().aniso_create_sharded(int(ds), int(qr), int(ks), float(as_), int(sr), int(fn), int(fm),
+                                              int(rank), int(nranks), ctypes.byref(h)))
         self.address = h
         n = ctypes.c_int64()
         _check(lib().aniso_num_nodes(h, ctypes.byref(n)))
@@ -1121,7 +1131,9 @@ class Aniso:
     def block_op_sharded_dev(self, which, x, y, stream=None):
         """One call of the sharded aniso.m operator: x (ks, N) tree order holds this
         rank's own range (its halo is filled here), y's owned slice receives the result.
-        Any ks: more than 8 blocks run as passes with ceil(ks / 8) exchanges per call."""
+        Any ks: more than 8 blocks run as passes with ceil(ks / 8) exchanges per call.
+        On a sharded high-order handle (shard=..., fn = 6 / 8; ks <= 8) one all-gather fills
+        the whole of x, not a halo."""
         import torch
 
         _dev_rows(x, self.ks, self.N, "x")

@@ -67,7 +67,7 @@ static int host_threads() {
     return n ? (int)std::min(n, 16u) : 4;
 }
 
-Operator::Operator(int sz, int d, int ks_, double g_, int ns_, int np_, int maxLevel_)
+Operator::Operator(int sz, int d, int ks_, double g_, int ns_, int np_, int maxLevel_, int shardRank, int shardRanks)
     : ks(ks_), ns(ns_), np(np_), maxLevel(maxLevel_), g(g_) {
     if (ks < 1) throw std::invalid_argument("kernel size must be >= 1");
     if (np != 4 && np != 6 && np != 8)
@@ -95,8 +95,10 @@ Operator::Operator(int sz, int d, int ks_, double g_, int ns_, int np_, int maxL
     if (highOrder()) {  // the mode-shared caches only (ks = 1 too), directed near lists, no rank-16 schedules
         plan.nearSymmetric = plan.nearSymHs = false;
         plan.listsOnly = true;
+        hoShard = shardRanks != 0;  // the rank's own lists; setShard keeps refusing
     }
-    plan.build(tree, np, 0, 1);
+    if (hoShard) plan.build(tree, np, shardRank, shardRanks);
+    else plan.build(tree, np, 0, 1);
     if (!highOrder()) {
         plan.buildExchange(tree, geo.sz, geo.d2);
         plan.buildTopWait(tree);
@@ -183,6 +185,22 @@ void Operator::setShard(int rank, int nranks) {
     mrhsPlanReady = false;
     m64.clear();
     if (device >= 0) uploadPlan();
+    if (device >= 0 && hoShard) uploadHighPlan();  // (rank 0 of 1: its L2L lists follow the own range)
+}
+
+void Operator::refuseHighPlain(const char* what) const {
+    if (highOrder() && !hoShard)
+        throw std::logic_error(std::string(what) + ": a high-order handle (np = " + std::to_string(np) +
+                               ") made by aniso_create is unsharded only; aniso_create_sharded makes the handle "
+                               "of one rank of a sharded high-order operator");
+}
+
+void Operator::refuseHoShard(const char* what) const {
+    if (hoShard)
+        throw std::logic_error(std::string(what) + ": a sharded high-order handle (aniso_create_sharded, np = " +
+                               std::to_string(np) + ", rank " + std::to_string(plan.rank) + " of " +
+                               std::to_string(plan.nranks) + ") runs aniso_block_op_sharded_dev, aniso_block_op_dev in "
+                               "tree order and aniso_block_solve_sharded_dev only");
 }
 
 void Operator::ensureDevice() {
@@ -333,10 +351,22 @@ void Operator::uploadHighPlan() {
     up(dHoChild, ch);
     const int D = t.maxLevel;
     std::vector<std::vector<int>> m2m(D + 1), l2l(D + 1);
+    // a sharded handle (hoShard): the up pass covers the whole tree on every rank, the L2L
+    // only the nodes that intersect the own range -- no other local is ever read
+    auto mine = [&](int n) {
+        return !hoShard || (t.begin[n] < plan.ownEnd && t.begin[n] + t.count[n] > plan.ownBegin);
+    };
     for (int i = 0; i < t.nn; ++i) {
         if (t.isEmpty[i] || t.parent[i] < 0) continue;
         if (!t.isLeaf[i]) m2m[t.level[i]].push_back(i);
-        if (t.level[i] >= 2) l2l[t.level[i]].push_back(i);
+        if (t.level[i] >= 2 && mine(i)) l2l[t.level[i]].push_back(i);
+    }
+    if (hoShard) {  // every non-empty leaf, as Plan::leafInfo's {node, begin, count, -}: the replicated P2M
+        std::vector<int4> all;
+        for (int i = 0; i < t.nn; ++i)
+            if (t.isLeaf[i] && !t.isEmpty[i]) all.push_back(make_int4(i, (int)t.begin[i], (int)t.count[i], 0));
+        hoLeafAll = (int)all.size();
+        up(dHoLeafAll, all);
     }
     std::vector<int> a, b;
     hoM2mPtr.assign(1, 0);
@@ -736,6 +766,7 @@ bool Operator::harmonicWeights(int K, int nterm, const int* ids, const double* m
 }
 
 void Operator::mappingHost(const double* charge, int id, double* out) {
+    refuseHoShard("aniso_mapping");
     if (id < 0 || id >= kernelSize) throw std::out_of_range("kernel id out of range");
     if (!modes[id].tables) throw std::runtime_error("mapping on kernel id " + std::to_string(id) + " before cache(" + std::to_string(id) + ")");
     ensureDevice();
@@ -813,6 +844,7 @@ void Operator::mappingBatchedHost(const double* Q, int k, int id, double* Out) {
 // mapping (AnisoWrapper.cpp:92-136) on device pointers, enqueued on stream s.
 // Only owned targets of `out` are written when the operator is sharded.
 void Operator::mappingDev(const double* charge, int id, double* out, hipStream_t s, int mask) {
+    refuseHoShard("aniso_mapping_dev");
     if (id >= 0 && id < kernelSize && modes[id].tables && !modes[id].resident) {
         leanMapping(charge, id, out, s, mask);
         return;
@@ -901,6 +933,7 @@ void Operator::apply(const double* charge, bool treeIn, const double* sigT, int 
 void Operator::applyBlockDev(int nrhs, const double* x, int64_t ldx, bool treeIn, bool useSigma, int nterm,
                              const int* ids, const double* mixes, double* out, int64_t ldo, bool treeOut,
                              hipStream_t s, int mask) {
+    refuseHoShard("aniso_apply_block_dev");
     if (useSigma && !coeffSet) throw std::runtime_error("block apply with sigma_s before setCoeff");
     ensureDevice();
     ApplyCall call;
@@ -1016,6 +1049,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     const int phase = call.phase;
     double* const rootsSend = call.rootsSend;
     const double* const rootsRecv = call.rootsRecv;
+    if (!(call.hoShard && treeIn && treeOut)) refuseHoShard("a block apply");  // before anything is staged
     if (K < 1 || K > 8) throw std::invalid_argument("block apply supports 1..8 right-hand sides, got " + std::to_string(K));
     checkDeviceErrors();
     if (nterm < 1) throw std::invalid_argument("block apply needs at least one mode term");
@@ -1458,7 +1492,10 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
 void Operator::applyBlockHigh(int K, const double* x, int64_t ldx, bool treeIn, const double* sigT, int nterm,
                               const int* ids, const double* mixes, double* out, int64_t ldo, bool treeOut,
                               hipStream_t s, int mask, const ApplyCall& call) {
-    if (call.phase != 0 || plan.nranks > 1) refuseHighOrder("a sharded apply");
+    // a shard: only the matvec of a handle made by createSharded (call.hoShard), on the rank's
+    // own lists below -- the whole input in tree order in, the owned slice out
+    if (call.phase != 0 || (plan.nranks > 1 && !(hoShard && call.hoShard))) refuseHighOrder("a sharded apply");
+    if (hoShard && !(call.hoShard && treeIn && treeOut)) refuseHoShard("a block apply");
     if (mask != kStageAll) refuseHighOrder("a per-stage apply");
     if (!attReady) throw std::runtime_error("high-order apply before cache()");
     HarmWeights hw;
@@ -1499,8 +1536,10 @@ void Operator::applyBlockHigh(int K, const double* x, int64_t ldx, bool treeIn, 
                 dFT.as<double>(), cf.Wc.as<double>(), cf.Wm.as<double>(), P, mask, scale, treeOut, ldo, out, s);
     const int e2 = tr ? mark(s) : -1;
     if (tm) span(6, e1, e2);
-    launch_ho_p2m(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                  dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), dFT.as<double>(), T, dHoMult.as<double>(), s);
+    // (a shard: the up pass over every leaf of the tree -- the M2L reads any node's multipole)
+    launch_ho_p2m(np, K, hoShard ? hoLeafAll : nl, (hoShard ? dHoLeafAll : dLeafInfo).as<int4>(), dNcx.as<double>(),
+                  dNcy.as<double>(), dNrx.as<double>(), dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
+                  dFT.as<double>(), T, dHoMult.as<double>(), s);
     for (size_t l = 0; l + 1 < hoM2mPtr.size(); ++l)
         launch_ho_m2m(np, K, hoM2mPtr[l + 1] - hoM2mPtr[l], dHoM2m.as<int>() + hoM2mPtr[l], dHoChild.as<int4>(), T,
                       dHoMult.as<double>(), s);
@@ -1544,6 +1583,7 @@ bool Operator::modeApplyCheck(const char* what, int id, int nrhs, const void* x,
         const size_t xs = ((size_t)(nrhs - 1) * ldx + geo.N) * sizeof(double), os = ((size_t)(nrhs - 1) * ldo + geo.N) * sizeof(double);
         if (xb < ob + os && ob < xb + xs) throw std::invalid_argument(w + ": x and out overlap");
     }
+    refuseHoShard(what);
     if (plan.nranks > 1)
         throw std::logic_error(w + " on a sharded handle: it writes every target (use an unsharded handle)");
     if (!coeffSet)
@@ -1835,6 +1875,9 @@ void Operator::blockOpDev(int which, const double* x, int64_t ldx, double* out, 
                           const double* rootsRecv) {
     if (which < 0 || which > 2) throw std::invalid_argument("block operator: which must be 0, 1 or 2");
     if (phase != 0) refuseHighOrder("the two-phase block operator");
+    // a sharded high-order handle: the matvec of blockOpShardedHigh for a caller who gathered
+    // the input -- the whole vector in tree order in, the owned slice out
+    if (hoShard && !treeIo) refuseHoShard("aniso_block_op_dev in original order");
     checkBlockLimit(phase != 0);
     if (!coeffSet) throw std::runtime_error("block operator before setCoeff");
     ensureDevice();
@@ -1845,6 +1888,8 @@ void Operator::blockOpDev(int which, const double* x, int64_t ldx, double* out, 
     }
     ApplyCall call;
     call.phased(phase, rootsSend, rootsRecv);
+    call.hoShard = hoShard;
+    if (hoShard && plan.ownEnd == plan.ownBegin) return;  // a rank that owns nothing
     blockOp(which, x, ldx, out, ldo, treeIo, s, gval, sigT, call);
 }
 
@@ -1901,6 +1946,9 @@ void Operator::blockPassPlan(int ks, int* chunk, int* nchunks) {
 // a sharded handle and the caller-driven two-phase forms are refused, before anything
 // is launched or any pending-call state is set
 void Operator::checkBlockLimit(bool shardedCall) const {
+    if (ks > kMaxRhs && hoShard)
+        throw std::invalid_argument("block operator: ks = " + std::to_string(ks) + " blocks on a sharded high-order handle "
+                                    "(its matvec holds at most " + std::to_string(kMaxRhs) + " blocks)");
     if (ks > kMaxRhs && (plan.nranks > 1 || shardedCall))
         throw std::invalid_argument("block operator: ks = " + std::to_string(ks) + " blocks on a sharded handle (more than " +
                                     std::to_string(kMaxRhs) + " blocks run on unsharded handles, and on shards through "
@@ -1984,6 +2032,7 @@ void Operator::blockOpPasses(int which, const double* x, int64_t ldx, double* ou
 void Operator::blockPassDev(int which, int I, int J, const double* x, int64_t ldx, double* out, int64_t ldo,
                             hipStream_t s) {
     if (which < 0 || which > 1) throw std::invalid_argument("block pass: which must be 0 or 1");
+    refuseHoShard("aniso_block_pass_dev");
     if (plan.nranks > 1) throw std::invalid_argument("block pass: unsharded handles only");
     int chunk = 0, P = 0;
     blockPassPlan(ks, &chunk, &P);
@@ -1999,6 +2048,7 @@ void Operator::blockPassDev(int which, int I, int J, const double* x, int64_t ld
 }
 
 void Operator::blockOpHost(int which, const double* u, const double* sigmaS, double gval, double* out) {
+    refuseHoShard("the host block operator");
     checkBlockLimit(false);
     if (plan.nranks != 1) throw std::logic_error("host block operator on a sharded handle");
     if (!coeffSet) throw std::runtime_error("block operator before setCoeff");
@@ -2051,6 +2101,7 @@ bool Operator::blockOpMultiCheck(const char* what, int which, int nsrc, const vo
         const size_t xs = (rows * ldx + N) * sizeof(double), os = (rows * ldo + N) * sizeof(double);
         if (xb < ob + os && ob < xb + xs) throw std::invalid_argument(w + ": the input and output rows overlap");
     }
+    refuseHoShard(what);
     if (plan.nranks > 1)
         throw std::logic_error(w + " on a sharded handle: it writes every target (use an unsharded handle)");
     if (!coeffSet) throw std::runtime_error(w + " before aniso_set_coeff and aniso_cache_block");
@@ -2210,6 +2261,7 @@ void Operator::blockOpMultiHost(int which, const double* U, int nsrc, double* Ou
 bool Operator::directCheck(const char* what, bool block, int id, int which, const void* in, const char* inName,
                            int64_t ldx, const int64_t* targets, int64_t nt, const void* out, int64_t ldo) const {
     const std::string w(what);
+    refuseHoShard(what);
     if (plan.nranks > 1)
         throw std::logic_error(w + " on a sharded handle: a direct sum needs every source (use an unsharded handle)");
     if (block) {
@@ -2773,7 +2825,11 @@ void Operator::forwardF32Dev(const float* X, float* Y, hipStream_t s, int mask) 
 // what it sends to peer p is p's halo inside its own range, so every rank's halo
 // ranges are exchanged once (one all-gather of the counts, one of the ranges).
 void Operator::commInit(std::unique_ptr<Collectives> c) {
-    refuseHighOrder("aniso_comm_init");
+    refuseHighPlain("aniso_comm_init");
+    if (hoShard) {
+        commInitHigh(std::move(c));
+        return;
+    }
     if (!c) throw std::invalid_argument("null communicator");
     if (c->nranks != plan.nranks || c->rank != plan.rank)
         throw std::logic_error("communicator rank / size (" + std::to_string(c->rank) + " of " +
@@ -3068,6 +3124,93 @@ void Operator::commInit(std::unique_ptr<Collectives> c) {
     comm = std::move(c);
 }
 
+// commInit on a sharded high-order handle: no halo plan -- a matvec gathers
+// the whole input, and every rank derives every rank's range from shard_cuts.  ONE small
+// all-gather of {N, ks, np, nranks, caches ready} makes the call fail on every rank when the
+// ranks' handles disagree or one has not cached its modes (each rank compares every record
+// with its own, so a single odd rank fails all of them).  A loopback communicator has no
+// peers: their records are taken to be this rank's.
+void Operator::commInitHigh(std::unique_ptr<Collectives> c) {
+    if (!c) throw std::invalid_argument("null communicator");
+    if (c->nranks != plan.nranks || c->rank != plan.rank)
+        throw std::logic_error("communicator rank / size (" + std::to_string(c->rank) + " of " +
+                               std::to_string(c->nranks) + ") differ from the handle's shard (" +
+                               std::to_string(plan.rank) + " of " + std::to_string(plan.nranks) + ")");
+    ensureDevice();
+    if (comm && device >= 0) HIP_CHECK(hipDeviceSynchronize());  // collectives in flight on the old one
+    comm.reset();
+    const int P = c->nranks, me = c->rank;
+    constexpr int kRec = 5;
+    const double mine[kRec] = {(double)geo.N, (double)ks, (double)np, (double)P, cachesReady() ? 1.0 : 0.0};
+    std::vector<double> all((size_t)P * kRec);
+    if (c->loopback()) {
+        for (int r = 0; r < P; ++r) std::copy(mine, mine + kRec, all.begin() + (size_t)r * kRec);
+    } else {
+        DevBuf a, b;
+        a.upload(mine, sizeof(mine));
+        b.alloc(all.size() * sizeof(double));
+        c->allgather(a.as<double>(), b.as<double>(), kRec, own);
+        HIP_CHECK(hipStreamSynchronize(own));
+        HIP_CHECK(hipMemcpy(all.data(), b.p, all.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    for (int r = 0; r < P; ++r) {
+        const double* o = all.data() + (size_t)r * kRec;
+        if (!std::equal(o, o + 4, mine))
+            throw std::logic_error("comm_init: rank " + std::to_string(r) + "'s handle (N, ks, np, nranks = " +
+                                   std::to_string((int64_t)o[0]) + ", " + std::to_string((int)o[1]) + ", " +
+                                   std::to_string((int)o[2]) + ", " + std::to_string((int)o[3]) + ") differs from rank " +
+                                   std::to_string(me) + "'s");
+    }
+    for (int r = 0; r < P; ++r)  // (after the comparison: every rank names the same first rank)
+        if (all[(size_t)r * kRec + 4] < 0.5)
+            throw std::logic_error("comm_init: rank " + std::to_string(r) +
+                                   " has not cached every mode; every rank caches its modes before comm_init");
+    const auto cuts = shard_cuts(tree, P);
+    if (cuts[me] != plan.ownBegin || cuts[me + 1] != plan.ownEnd) throw std::logic_error("shard cuts disagree with the plan");
+    hgMax = 0;
+    for (int r = 0; r < P; ++r) hgMax = std::max(hgMax, cuts[r + 1] - cuts[r]);
+    up(dHgCuts, cuts);
+    // the parts of the matvec's all-gather: min(ks, 8) rows of hgMax doubles per rank (the
+    // padding behind a shorter rank's rows is never unpacked; zeroed once so that a
+    // host-staged transport moves finite values)
+    const size_t part = (size_t)std::min(ks, kMaxRhs) * (size_t)hgMax;
+    dHgSend.alloc(std::max<size_t>(part, 1) * sizeof(double));
+    dHgRecv.alloc(std::max<size_t>(part * P, 1) * sizeof(double));
+    HIP_CHECK(hipMemset(dHgSend.p, 0, dHgSend.bytes));
+    HIP_CHECK(hipMemset(dHgRecv.p, 0, dHgRecv.bytes));
+    oxReady = false;
+    comm = std::move(c);
+}
+
+// The sharded matvec of a high-order handle: pack the own slice of the ks rows, ONE
+// all-gather (every part padded to the largest owned count: the same count on every rank,
+// which an all-gather needs; the cuts are balanced to within a frontier node, so the
+// padding is small unless ranks own nothing), unpack every peer's part into its range of x -- x then holds the whole
+// vector -- and the apply on the rank's own lists.  A loopback communicator moves the own
+// part only (the caller supplies the rest of x), and it alone is unpacked.  A rank that
+// owns nothing takes part in the collective and launches nothing else.
+void Operator::blockOpShardedHigh(int which, double* x, int64_t ldx, double* yo, int64_t ldo, hipStream_t s) {
+    const int P = plan.nranks, me = plan.rank;
+    const int64_t owned = plan.ownEnd - plan.ownBegin;
+    const bool tm = timeStages == 1;
+    const int e0 = tm ? mark(s) : -1;
+    launch_slice_pack(owned, ks, x + plan.ownBegin, ldx, hgMax, dHgSend.as<double>(), s);
+    const int e1 = tm ? mark(s) : -1;
+    comm->allgather(dHgSend.as<double>(), dHgRecv.as<double>(), (size_t)ks * (size_t)hgMax, s);
+    const int e2 = tm ? mark(s) : -1;
+    if (comm->loopback()) launch_slice_unpack(me, me + 1, -1, dHgCuts.as<int64_t>(), ks, hgMax, dHgRecv.as<double>(), x, ldx, s);
+    else launch_slice_unpack(0, P, me, dHgCuts.as<int64_t>(), ks, hgMax, dHgRecv.as<double>(), x, ldx, s);
+    if (tm) {  // stage 0: the pack; stage 3 (the rank-16 M2L gather, unused here): the unpack
+        const int e3 = mark(s);
+        spans.push_back({0, e0, e1});
+        spans.push_back({3, e2, e3});
+    }
+    if (owned == 0) return;
+    ApplyCall call;
+    call.hoShard = true;
+    blockOp(which, x, ldx, yo, ldo, true, s, NAN, nullptr, call);
+}
+
 // Can this sharded matvec take the one-collective exchange?  Its phase 1 must leave
 // nothing to the halo: the harmonic block apply with the near field formed from the
 // input (run in phase 2, after the exchange) and no padded right-hand sides -- exactly
@@ -3105,7 +3248,7 @@ bool Operator::oneExchangeUsable(int which) {
 }
 
 void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s) {
-    refuseHighOrder("aniso_block_op_sharded_dev");
+    refuseHighPlain("aniso_block_op_sharded_dev");
     if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
     if (ldx < geo.N || ldy < geo.N) throw std::invalid_argument("sharded block operator: leading dimension below N");
     blockOpShardedOwned(which, x, ldx, y + plan.ownBegin, ldy, s);
@@ -3117,6 +3260,10 @@ void Operator::blockOpShardedDev(int which, double* x, int64_t ldx, double* y, i
 void Operator::blockOpShardedOwned(int which, double* x, int64_t ldx, double* yo, int64_t ldo, hipStream_t s) {
     prepareShardedMatvec(which);
     checkDeviceErrors();
+    if (hoShard) {  // one all-gather of the input, then the rank's own targets
+        blockOpShardedHigh(which, x, ldx, yo, ldo, s);
+        return;
+    }
     const bool one = ks > kMaxRhs ? oxReady : oneExchangeUsable(which);
     auto phase = [&](ApplyCall& call, int ph) {
         call.phased(ph, ph == 1 ? dXRootsSend.as<double>() : nullptr, ph == 2 ? dXRootsRecv.as<double>() : nullptr);
@@ -3142,6 +3289,21 @@ void Operator::prepareShardedMatvec(int which) {
     if (which < 0 || which > 2) throw std::invalid_argument("block operator: which must be 0, 1 or 2");
     if (!coeffSet) throw std::runtime_error("block operator before setCoeff");
     constexpr int K = kMaxRhs;
+    if (hoShard) {  // one apply of ks <= 8 blocks on the high-order launches: no tiers, no passes
+        checkBlockLimit(true);
+        if (!cachesReady())
+            throw std::logic_error("sharded block operator before cache(): every rank caches its modes first");
+        ensureDevice();
+        const int Kp = ks == 1 ? 2 : rootRhs(ks);
+        if (Kp != ks) {
+            dPadIn.alloc((size_t)Kp * geo.N * sizeof(double));
+            dPadOut.alloc((size_t)Kp * geo.N * sizeof(double));
+        }
+        if (which == 2 && !(fuseSub && rhs_supported(ks) && ks > 1))
+            dBlk.alloc((size_t)ks * (plan.ownEnd - plan.ownBegin) * sizeof(double));
+        ensureWork(Kp);
+        return;
+    }
     if (ks > K && useAtt && !attReady)
         throw std::logic_error("sharded block operator before cache(): every rank caches its modes first");
     if (ks > K && (!useAtt || plan.nearPartTotal != 0))

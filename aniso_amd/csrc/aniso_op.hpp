@@ -96,12 +96,18 @@ struct ApplyCall {
     HarmWindow win{0, 0};
     HarmWeights hw{};
     bool shardedPass = false;  // inside blockOpShardedPasses: phase 2 keeps the pending state for its repeats
+    // the apply of a sharded high-order matvec (blockOpShardedHigh, blockOpDev in tree order):
+    // the only applies a handle made by createSharded at np = 6, 8 runs
+    bool hoShard = false;
     ExchangeForm exch;
 };
 
 class Operator {
 public:
-    Operator(int sz, int d, int ks, double g, int ns, int np, int maxLevel);
+    // shardRank / shardRanks: the shard of a handle made by aniso_create_sharded at np = 6, 8
+    // (shardRanks = 0: a plain handle; np = 4 ignores them, its shard is set by setShard;
+    // the entry point checks the pair, and Plan::build once more)
+    Operator(int sz, int d, int ks, double g, int ns, int np, int maxLevel, int shardRank = 0, int shardRanks = 0);
     ~Operator();
 
     // --- the reference's MEX ops (AnisoWrapper.cpp:10-136)
@@ -206,6 +212,18 @@ public:
     // input's halo all-to-all, phase 1, the root all-gather and phase 2 in one call
     // (any ks: more than kMaxRhs blocks as passes, one exchange per input chunk)
     void commInit(std::unique_ptr<Collectives> c);
+    // A sharded high-order handle (aniso_create_sharded at np = 6, 8): a rank
+    // computes its own targets from the WHOLE input.  Its plan is Plan::build's lists for
+    // (rank, nranks); P2M and M2M run over the whole tree on every rank, the near field, the
+    // corrections, the M2L, L2L and L2P over the rank's lists.  commInit runs one all-gather
+    // of {N, ks, np, nranks, caches ready} and builds no halo plan; a matvec gathers every
+    // rank's owned slice of the ks rows into x with ONE all-gather (parts padded to the
+    // largest owned count).  Everything but blockOpShardedDev, blockOpDev in tree order and
+    // blockSolveShardedDev raises ANISO_ERR_STATE on such a handle (refuseHoShard).
+    bool hoSharded() const { return hoShard; }
+    void refuseHoShard(const char* what) const;
+    // raise (ANISO_ERR_STATE) on a high-order handle made by aniso_create: the sharded routes
+    void refuseHighPlain(const char* what) const;
     void blockOpShardedDev(int which, double* x, int64_t ldx, double* y, int64_t ldy, hipStream_t s);
     bool commReady() const { return comm != nullptr; }
     void getShard(int64_t* ownBegin, int64_t* ownEnd) const { *ownBegin = plan.ownBegin; *ownEnd = plan.ownEnd; }
@@ -470,6 +488,15 @@ private:
                         const ApplyCall& call);
     void uploadHighPlan();  // its tables and level lists (ensureDevice: they follow the tree alone)
     DevBuf dHoTab, dHoChild, dHoM2m, dHoL2l, dHoMult, dHoLocal;
+    // a sharded high-order handle: every non-empty leaf (the replicated P2M; dLeafInfo keeps
+    // the owned leaves), the all-gather's send part and receive buffer (ks x hgMax doubles
+    // per rank, hgMax the largest owned count) and every rank's cut on the device
+    bool hoShard = false;
+    DevBuf dHoLeafAll, dHgSend, dHgRecv, dHgCuts;
+    int hoLeafAll = 0;
+    int64_t hgMax = 0;
+    void commInitHigh(std::unique_ptr<Collectives> c);
+    void blockOpShardedHigh(int which, double* x, int64_t ldx, double* yo, int64_t ldo, hipStream_t s);
     std::vector<int> hoM2mPtr, hoL2lPtr;  // per level: its range of dHoM2m (bottom-up) / dHoL2l (top-down)
     int hoWorkK = 0;
     // blockOpMultiDev's chunk of S in {1, 2, 4} sources (nreal of them present, the rest zero)

@@ -102,6 +102,29 @@ int aniso_create(int sz, int d, int ks, double g, int ns, int np, int maxLevel, 
     });
 }
 
+int aniso_create_sharded(int sz, int d, int ks, double g, int ns, int np, int maxLevel, int rank, int nranks,
+                         aniso_handle* out) {
+    return guarded([&] {
+        CHECK_PTR(out);
+        *out = nullptr;
+        if (nranks < 1 || rank < 0 || rank >= nranks)
+            throw std::invalid_argument("aniso_create_sharded: need nranks >= 1 and 0 <= rank < nranks, got rank " +
+                                        std::to_string(rank) + " of " + std::to_string(nranks));
+        if (np == 4) {  // exactly aniso_create + aniso_set_shard
+            aniso_op_s* h = new aniso_op_s(sz, d, ks, g, ns, np, maxLevel);
+            try {
+                h->op.setShard(rank, nranks);
+            } catch (...) {
+                delete h;
+                throw;
+            }
+            *out = h;
+            return;
+        }
+        *out = new aniso_op_s(sz, d, ks, g, ns, np, maxLevel, rank, nranks);
+    });
+}
+
 int aniso_destroy(aniso_handle h) {
     ENTER(h);
     return guarded([&] {
@@ -656,6 +679,7 @@ int aniso_shard_exchange(aniso_handle h, int nrhs, int64_t* info) {
     return guarded([&] {
         CHECK_PTR(info);
         if (nrhs < 1 || nrhs > 8) throw std::invalid_argument("nrhs must be in 1..8");
+        get(h).refuseHoShard("aniso_shard_exchange");
         const auto& p = get(h).plan;
         info[0] = p.xRootChunk;
         info[1] = (int64_t)aniso::kRank * aniso::Operator::rootRhs(nrhs);
@@ -673,6 +697,7 @@ int aniso_shard_exchange_one(aniso_handle h, int64_t* info) {
     ENTER(h);
     return guarded([&] {
         CHECK_PTR(info);
+        get(h).refuseHoShard("aniso_shard_exchange_one");
         const auto& p = get(h).plan;
         info[0] = p.xOneOk ? 1 : 0;
         info[1] = (int64_t)p.xOwnT0Tasks.size();
@@ -686,6 +711,7 @@ int aniso_shard_upper_partials(aniso_handle h, int64_t* info) {
     ENTER(h);
     return guarded([&] {
         CHECK_PTR(info);
+        get(h).refuseHoShard("aniso_shard_upper_partials");
         const auto& p = get(h).plan;
         info[0] = p.xUpPartial ? 1 : 0;
         info[1] = (int64_t)(p.xUpTask.size() / aniso::Plan::kUpTaskInts);
@@ -712,6 +738,7 @@ int aniso_shard_one_halo(aniso_handle h, int64_t* ranges) {
     ENTER(h);
     return guarded([&] {
         CHECK_PTR(ranges);
+        get(h).refuseHoShard("aniso_shard_one_halo");
         const auto& p = get(h).plan;
         std::copy(p.xOneHalo.begin(), p.xOneHalo.end(), ranges);
     });
@@ -721,6 +748,7 @@ int aniso_shard_halo(aniso_handle h, int64_t* ranges) {
     ENTER(h);
     return guarded([&] {
         CHECK_PTR(ranges);
+        get(h).refuseHoShard("aniso_shard_halo");
         const auto& p = get(h).plan;
         std::copy(p.xHalo.begin(), p.xHalo.end(), ranges);
     });
@@ -934,7 +962,7 @@ int aniso_comm_init_rccl(aniso_handle h, const unsigned char* id) {
     return guarded([&] {
         CHECK_PTR(id);
         auto& op = get(h);
-        op.refuseHighOrder("aniso_comm_init");  // before a communicator is made
+        op.refuseHighPlain("aniso_comm_init");  // before a communicator is made
         op.commInit(aniso::make_rccl_collectives(id, op.plan.nranks, op.plan.rank));
     });
 }
@@ -944,7 +972,7 @@ int aniso_comm_init_callbacks(aniso_handle h, const aniso_collectives* c) {
     return guarded([&] {
         CHECK_PTR(c);
         auto& op = get(h);
-        op.refuseHighOrder("aniso_comm_init");  // before a communicator is made
+        op.refuseHighPlain("aniso_comm_init");  // before a communicator is made
         op.commInit(aniso::make_callback_collectives(*c, op.plan.nranks, op.plan.rank));
     });
 }
@@ -1088,7 +1116,7 @@ int aniso_comm_init_loopback(aniso_handle h) {
     ENTER(h);
     return guarded([&] {
         auto& op = get(h);
-        op.refuseHighOrder("aniso_comm_init");  // before a communicator is made
+        op.refuseHighPlain("aniso_comm_init");  // before a communicator is made
         op.commInit(aniso::make_loopback_collectives(op.plan.nranks, op.plan.rank));
     });
 }

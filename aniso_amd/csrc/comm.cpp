@@ -140,7 +140,8 @@ class CallbackCollectives : public Collectives {
 // Development: one rank's exchange with the others' data left out -- its own part of
 // the all-gather copied into place on the stream, nothing sent or received.  Times a
 // rank's schedule (streams, events, kernels) on one GPU; its results are not the
-// sharded operator's.
+// sharded operator's.  (A sharded high-order matvec gathers its whole input through
+// allgather: here the own part alone lands in the receive buffer, and only it is unpacked.)
 class LoopbackCollectives : public Collectives {
   public:
     LoopbackCollectives(int n, int r) {

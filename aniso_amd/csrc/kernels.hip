@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <stdexcept>
 
 #include "device_common.hpp"
 #include "line_integral.hpp"
@@ -214,6 +215,45 @@ void launch_halo_unpack(int64_t n, int nb, const int64_t* pos, const int64_t* ba
                         const double* buf, double* x, int64_t ldx, hipStream_t s) {
     if (n <= 0) return;
     k_halo_unpack<<<blocks_for(n, 256), 256, 0, s>>>(n, nb, pos, base, stride, buf, x, ldx);
+    HIP_LAUNCH_CHECK();
+}
+
+// ---- the gathered input of a sharded high-order matvec: a rank's part of
+// the all-gather is its owned slice of the nb rows, row b at b * stride (stride: the largest
+// owned count of any rank).  Grid: x over the positions of a slice, y the row, z the part.
+__global__ void k_slice_pack(int64_t own, const double* __restrict__ xo, int64_t ldx, int64_t stride,
+                             double* __restrict__ buf) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t b = blockIdx.y;
+    if (k < own) buf[b * stride + k] = xo[b * ldx + k];
+}
+
+// parts p0 + blockIdx.z (all but `skip`, the rank's own) into [cuts[p], cuts[p + 1]) of the rows of x
+__global__ void k_slice_unpack(int p0, int skip, const int64_t* __restrict__ cuts, int nb, int64_t stride,
+                               const double* __restrict__ buf, double* __restrict__ x, int64_t ldx) {
+    const int p = p0 + (int)blockIdx.z;
+    if (p == skip) return;
+    const int64_t lo = cuts[p], cnt = cuts[p + 1] - lo;
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t b = blockIdx.y;
+    if (k < cnt && k < stride) x[b * ldx + lo + k] = buf[((int64_t)p * nb + b) * stride + k];
+}
+
+void launch_slice_pack(int64_t own, int nb, const double* xo, int64_t ldx, int64_t stride, double* buf,
+                       hipStream_t s) {
+    if (own <= 0 || nb <= 0) return;
+    if (own > stride) throw std::invalid_argument("slice pack: the owned count exceeds the part's row stride");
+    k_slice_pack<<<dim3(blocks_for(own, 256), (unsigned)nb), 256, 0, s>>>(own, xo, ldx, stride, buf);
+    HIP_LAUNCH_CHECK();
+}
+
+void launch_slice_unpack(int p0, int p1, int skip, const int64_t* cuts, int nb, int64_t stride, const double* buf,
+                         double* x, int64_t ldx, hipStream_t s) {
+    // (nothing to do: no part but the skipped one, or every rank owns nothing)
+    if (p1 <= p0 || nb <= 0 || stride <= 0 || (p1 - p0 == 1 && p0 == skip)) return;
+    if (p1 - p0 > 65535) throw std::invalid_argument("slice unpack: more than 65535 parts");
+    k_slice_unpack<<<dim3(blocks_for(stride, 256), (unsigned)nb, (unsigned)(p1 - p0)), 256, 0, s>>>(p0, skip, cuts, nb,
+                                                                                                 stride, buf, x, ldx);
     HIP_LAUNCH_CHECK();
 }
 

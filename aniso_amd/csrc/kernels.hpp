@@ -472,6 +472,15 @@ void launch_halo_pack(int64_t n, int nb, const int64_t* pos, const int64_t* base
                       const double* x, int64_t ldx, double* buf, hipStream_t s);
 void launch_halo_unpack(int64_t n, int nb, const int64_t* pos, const int64_t* base, const int64_t* stride,
                         const double* buf, double* x, int64_t ldx, hipStream_t s);
+// the gathered input of a sharded high-order matvec.  pack: the own slice xo
+// (own positions of nb rows at stride ldx) into one contiguous part, row b at b * stride
+// (stride >= own: the largest owned count of any rank).  unpack: parts p0 .. p1 - 1 of buf
+// (part p at p * nb * stride), all but `skip`, into [cuts[p], cuts[p + 1]) of the rows of x.
+// Zero-size launches (a rank or a peer that owns nothing) are skipped.
+void launch_slice_pack(int64_t own, int nb, const double* xo, int64_t ldx, int64_t stride, double* buf,
+                       hipStream_t s);
+void launch_slice_unpack(int p0, int p1, int skip, const int64_t* cuts, int nb, int64_t stride, const double* buf,
+                         double* x, int64_t ldx, hipStream_t s);
 // the one-collective exchange's pack (send) or unpack (receive) in one launch: root
 // records (nRoot parts of rec doubles at rootOff in buf; unpack: to rootDst in roots,
 // and this rank's own record from ownRoots), input positions (pos / base / stride as

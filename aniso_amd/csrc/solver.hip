@@ -666,6 +666,7 @@ int Operator::gmresRestarted(const GmresSystem& g, StatusBlock& hs, double tol, 
 // hist gets the relative residual estimate after every step.
 int Operator::blockSolveDev(const double* rhs, double* x, int restart, double tol, int maxit, double* hist,
                             int maxhist, double* relresOut, hipStream_t s) {
+    refuseHoShard("aniso_block_solve");
     checkBlockLimit(false);
     if (plan.nranks != 1) throw std::logic_error("block solve on a sharded handle");
     if (!coeffSet) throw std::runtime_error("block solve before setCoeff");
@@ -772,7 +773,8 @@ static void rows_copy(int rows, int64_t len, const double* src, int64_t lds, dou
 // every rank at the same step.
 int Operator::blockSolveShardedDev(const double* rhs, int64_t ldr, double* x, int64_t ldx, int restart, double tol,
                                    int maxit, double* hist, int maxhist, double* relresOut, hipStream_t s) {
-    refuseHighOrder("aniso_block_solve_sharded_dev");
+    refuseHighPlain("aniso_block_solve_sharded_dev");
+    if (hoShard) checkBlockLimit(true);  // (ks is the same on every rank, commInitHigh: all return alike, no collective)
     if (!comm) throw std::logic_error("sharded block operator before aniso_comm_init");
     ensureDevice();
     const int64_t N = geo.N, ob = plan.ownBegin, owned = plan.ownEnd - plan.ownBegin, L = (int64_t)ks * owned;

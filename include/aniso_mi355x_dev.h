@@ -28,7 +28,9 @@ int aniso_shard_roots(aniso_handle h, int *send_nodes, int *recv_nodes, int *t0_
 /* development: a loopback communicator -- this rank's own part of the all-gather
  * copied into place, nothing sent or received -- to time one rank's schedule of an
  * N-GPU run on one GPU (tools/shard_time.py --native); its results are not the
- * sharded operator's */
+ * sharded operator's.  On a sharded high-order handle (tools/high_shard_time.py) only the
+ * own part of the matvec's all-gather is packed and unpacked: a caller who supplies the
+ * whole input gets the rank's launches and the operator's values. */
 int aniso_comm_init_loopback(aniso_handle h);
 /* the same restricted to the stages in mask (ANISO_STAGE_*; the identity x is always there) */
 int aniso_forward_f32_stages_dev(aniso_handle h, const float *x, int mask, float *y, void *stream);
@@ -93,7 +95,10 @@ int aniso_stats(aniso_handle h, int64_t *stats);
  * P2M/M2M tiers), m2l, gather (transposed M2L products), near, down (L2L/L2P tiers + transposed
  * near products), corr, total.  A block apply sums each stage over its mode terms.
  * aniso_set_timing(h, 2) records the m2l and near spans only (the others read 0):
- * fewer in-stream events inside a timed region.  Other levels: ANISO_ERR_INVALID. */
+ * fewer in-stream events inside a timed region.  Other levels: ANISO_ERR_INVALID.
+ * A sharded high-order handle (aniso_create_sharded, np = 6, 8) reports, at level 1, the
+ * pack kernel of its all-gather as exchange and the unpack kernel as gather; total spans
+ * the apply after them. */
 int aniso_set_timing(aniso_handle h, int on);
 int aniso_stage_times(aniso_handle h, float *t8);
 /* development: the per-block timeline of the last fused top-of-tree launch, recorded
