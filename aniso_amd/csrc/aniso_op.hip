@@ -67,6 +67,13 @@ static int host_threads() {
     return n ? (int)std::min(n, 16u) : 4;
 }
 
+// the K x K mix of one mode applied to K columns
+static std::vector<double> identityMix(int K) {
+    std::vector<double> mix((size_t)K * K, 0.0);
+    for (int i = 0; i < K; ++i) mix[(size_t)i * K + i] = 1.0;
+    return mix;
+}
+
 Operator::Operator(int sz, int d, int ks_, double g_, int ns_, int np_, int maxLevel_, int shardRank, int shardRanks)
     : ks(ks_), ns(ns_), np(np_), maxLevel(maxLevel_), g(g_) {
     if (ks < 1) throw std::invalid_argument("kernel size must be >= 1");
@@ -827,13 +834,11 @@ void Operator::mappingBatchedHost(const double* Q, int k, int id, double* Out) {
     dout.alloc((size_t)kb * N * sizeof(double));
     for (int j0 = 0; j0 < k; j0 += kb) {
         const int nb = std::min(kb, k - j0);
-        std::vector<double> eye((size_t)nb * nb, 0.0);
-        for (int i = 0; i < nb; ++i) eye[(size_t)i * nb + i] = 1.0;
         HIP_CHECK(hipMemcpyAsync(dq.p, Q + (size_t)j0 * N, (size_t)nb * N * sizeof(double), hipMemcpyHostToDevice, own));
         if (plan.nranks > 1) HIP_CHECK(hipMemsetAsync(dout.p, 0, dout.bytes, own));
         ApplyCall call;
-        applyBlock(nb, dq.as<double>(), N, false, nullptr, 1, &id, eye.data(), dout.as<double>(), N, false, own,
-                   kStageAll, call);
+        applyBlock(nb, dq.as<double>(), N, false, nullptr, 1, &id, identityMix(nb).data(), dout.as<double>(), N, false,
+                   own, kStageAll, call);
         HIP_CHECK(hipMemcpyAsync(Out + (size_t)j0 * N, dout.p, (size_t)nb * N * sizeof(double), hipMemcpyDeviceToHost,
                                  own));
         HIP_CHECK(hipStreamSynchronize(own));
@@ -1032,6 +1037,105 @@ static std::vector<int> modeIds(int nm) {
     return ids;
 }
 
+constexpr double kScale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
+
+// ---- the stages of the un-fused applies ----
+// One stream, every sum in a fixed order: the weighted charges; the near field, which stores
+// the output rows; the corrections, which add to them; the up pass; one M2L launch; the down
+// pass, the last writer of the rows (it carries the minuend).
+
+void Operator::prepareCharges(int K, const InRows& in, double* fT, double* cT, hipStream_t s) {
+    launch_prepare(K, geo.N, in.x, in.ld, in.tree ? 1 : 0, dPerm.as<int>(), in.sigT, dWT.as<double>(), fT, cT, s);
+}
+
+void Operator::nearUnstaged(int K, const HarmWeights& hw, const HarmWindow* win, int mask, const OutRows& o,
+                            hipStream_t s) {
+    launch_near_hm(K, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
+                   dNearPts.as<int>(), dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(),
+                   dPyT.as<double>(), dSigDiag.as<double>(), hw, dFT.as<double>(), o.perm, o.base, o.ld, mask, kScale,
+                   o.out, nullptr, nullptr, nullptr, 0, nullptr, nearWpe, s, nullptr, win);
+}
+
+void Operator::nearMode(int K, int id, const OutRows& o, hipStream_t s) {
+    launch_near_mode(K, id, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
+                     dNearPts.as<int>(), dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(),
+                     dPyT.as<double>(), dSigDiag.as<double>(), dFT.as<double>(), o.perm, o.base, o.ld, kScale, o.out,
+                     s);
+}
+
+void Operator::corrections(int K, const CorrFold& cf, const double* fT, const double* cT, int64_t begin, int64_t end,
+                           int mask, const OutRows& o, hipStream_t s) {
+    launch_corr(K, geo.d, begin, end, dPerm.as<int>(), dIperm.as<int>(), cT, fT, cf.Wc.as<double>(), cf.Wm.as<double>(),
+                dParams.as<Params>(), mask, kScale, o.tree, o.ld, o.out, s);
+}
+
+void Operator::hoReserve(int K, hipStream_t s) {
+    if (K > hoWorkK) {
+        dHoMult.alloc(hoDoubles(K) * sizeof(double));
+        dHoLocal.alloc(hoDoubles(K) * sizeof(double));
+        hoWorkK = K;
+    }
+    // nodes that are no M2L target (the root, empty nodes) keep zero locals; a smaller K
+    // re-uses the buffers with its own strides
+    HIP_CHECK(hipMemsetAsync(dHoLocal.p, 0, hoDoubles(K) * sizeof(double), s));
+}
+
+void Operator::hoUpPass(int K, double* mult, bool allLeaves, hipStream_t s) {
+    const int nl = allLeaves ? hoLeafAll : (int)plan.leaves.size();
+    launch_ho_p2m(np, K, nl, (allLeaves ? dHoLeafAll : dLeafInfo).as<int4>(), dNcx.as<double>(), dNcy.as<double>(),
+                  dNrx.as<double>(), dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), dFT.as<double>(),
+                  dHoTab.as<HoTables>(), mult, s);
+    for (size_t l = 0; l + 1 < hoM2mPtr.size(); ++l)
+        launch_ho_m2m(np, K, hoM2mPtr[l + 1] - hoM2mPtr[l], dHoM2m.as<int>() + hoM2mPtr[l], dHoChild.as<int4>(),
+                      dHoTab.as<HoTables>(), mult, s);
+}
+
+void Operator::hoDownPass(int K, double* local, const OutRows& o, hipStream_t s) {
+    const HoTables* T = dHoTab.as<HoTables>();
+    for (size_t l = 0; l + 1 < hoL2lPtr.size(); ++l)
+        launch_ho_l2l(np, K, hoL2lPtr[l + 1] - hoL2lPtr[l], dHoL2l.as<int>() + hoL2lPtr[l], dParent.as<int>(),
+                      dSlot.as<int>(), T, local, s);
+    launch_ho_l2p(np, K, (int)plan.leaves.size(), dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(),
+                  dNrx.as<double>(), dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), T, local, o.perm, o.base,
+                  o.ld, kScale, o.out, o.minuend, o.minuendLd, s);
+}
+
+// tier k: `list` (nullptr: every task of the tier) names ntask tasks; fT / cT (nullptr: none)
+// receive the charges its P2M forms; recv / send: the tier-0 roots of a sharded apply
+void Operator::upTier16(int K, int k, const int* list, int ntask, double* fT, double* cT, const double* recv,
+                        double* send, unsigned* zeroCnt, const UpTail* tail, const InRows& in, hipStream_t s) {
+    launch_up_tier(K, ntask, plan.upTierTask[k], list, plan.upTierMaxTask[k], dUpDesc.as<int4>(), dUpGrpFix.as<int>(),
+                   dUpNode.as<int>(), dUpCode.as<int4>(), dUpGeom.as<double4>(), dUpLeaf.as<int2>(), dPxT.as<double>(),
+                   dPyT.as<double>(), in.x, in.ld, in.tree ? 1 : 0, dPerm.as<int>(), in.sigT, dWT.as<double>(), fT, cT,
+                   dParams.as<Params>(), dMult.as<double>(), recv ? dXRootSlot.as<int>() : nullptr, recv,
+                   send ? dXSendSlot.as<int>() : nullptr, send, s, zeroCnt, tail);
+}
+
+// L2L + L2P + the gathered partials (nearPart: transposed near products; hpart: the clustered
+// M2L's halo), once for the sum over the terms
+void Operator::downPass16(int K, int mask, const double* nearPart, const double* hpart, const OutRows& o,
+                          hipStream_t s) {
+    launch_down_tier(K, (int)plan.dnDesc.size() / 3, plan.dnMaxTask, plan.dnMaxLeaves, dDnDesc.as<int4>(),
+                     dDnGrpFix.as<int>(), dDnNode.as<int4>(), dLocal.as<double>(), dParams.as<Params>(),
+                     dDnLeafSlot.as<int>(), dDnLeafPts.as<int>(), dDnLeafNear.as<int2>(), dDnLeafGeom.as<double4>(),
+                     dPxT.as<double>(), dPyT.as<double>(), o.perm, o.base, o.ld, dDnNearOff.as<int>(), plan.dnMaxNear,
+                     nearPart, dDnChain.as<int2>(), plan.dnMaxChain, mask, kScale, o.out, o.minuend, o.minuendLd, s,
+                     hpart, dDnChainFold.as<int>());
+}
+
+void Operator::padRowsIn(DevBuf& buf, int groups, int nb, int K, const double* x, int64_t ldx, hipStream_t s) {
+    const int64_t N = geo.N;
+    HIP_CHECK(hipMemsetAsync(buf.p, 0, (size_t)groups * K * N * sizeof(double), s));
+    for (int j = 0; j < groups; ++j)
+        HIP_CHECK(hipMemcpy2DAsync(buf.as<double>() + (size_t)j * K * N, N * sizeof(double), x + (size_t)j * nb * ldx,
+                                   ldx * sizeof(double), N * sizeof(double), nb, hipMemcpyDeviceToDevice, s));
+}
+
+void Operator::padRowsOut(const double* group, int nb, int64_t n, double* out, int64_t ldo, hipStream_t s) {
+    HIP_CHECK(hipMemcpy2DAsync(out, ldo * sizeof(double), group, geo.N * sizeof(double), n * sizeof(double), nb,
+                               hipMemcpyDeviceToDevice, s));
+}
+
 // One batched apply: the up pass over the K base vectors, then per term t (mode
 // ids[t], mix mixes[t]) the near field, the corrections, the M2L stream and its
 // gather, each accumulating; then one down pass.  sigT (sigma_s in tree order, or
@@ -1069,22 +1173,18 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         const int Kp = padHigh ? 2 : rhs_padded(K);
         dPadIn.alloc((size_t)Kp * geo.N * sizeof(double));
         dPadOut.alloc((size_t)Kp * geo.N * sizeof(double));
-        if (phase != 2) {  // phase 2 reads what phase 1 staged
-            HIP_CHECK(hipMemsetAsync(dPadIn.p, 0, dPadIn.bytes, s));
-            HIP_CHECK(hipMemcpy2DAsync(dPadIn.p, geo.N * sizeof(double), x, ldx * sizeof(double),
-                                       geo.N * sizeof(double), K, hipMemcpyDeviceToDevice, s));
-        }
+        if (phase != 2) padRowsIn(dPadIn, 1, K, Kp, x, ldx, s);  // phase 2 reads what phase 1 staged
         const std::vector<double> mp = padMixes(K, Kp, nterm, mixes);
         applyBlock(Kp, dPadIn.as<double>(), geo.N, treeIn, sigT, nterm, ids, mp.data(), dPadOut.as<double>(), geo.N,
                    treeOut, s, mask, call);
-        if (phase != 1)
-            HIP_CHECK(hipMemcpy2DAsync(out, ldo * sizeof(double), dPadOut.p, geo.N * sizeof(double),
-                                       nOut * sizeof(double), K, hipMemcpyDeviceToDevice, s));
+        if (phase != 1) padRowsOut(dPadOut.as<double>(), K, nOut, out, ldo, s);
         return;
     }
     ensureWork(K);
+    const InRows in{x, ldx, treeIn, sigT};
+    const OutRows o = outRows(out, ldo, treeOut, call.minuend, call.minuendLd);
     if (highOrder()) {
-        applyBlockHigh(K, x, ldx, treeIn, sigT, nterm, ids, mixes, out, ldo, treeOut, s, mask, call);
+        applyBlockHigh(K, in, nterm, ids, mixes, o, s, mask, call);
         return;
     }
     if (up_tier_lds(plan.upMaxTask, K) > 160 * 1024 ||
@@ -1096,9 +1196,6 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     auto span = [&](int stage, int a, int b) {
         if (a >= 0 && b >= 0) spans.push_back({stage, a, b});
     };
-    const int* operm = treeOut ? nullptr : dPerm.as<int>();
-    const int64_t obase = treeOut ? plan.ownBegin : 0;
-    const double scale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
     HarmWeights hw;
     // one pass of a block operator of more than kMaxRhs blocks (blockPass): its weights
     // come with it, and it runs the plain harmonic launches in their offset form; without
@@ -1171,12 +1268,8 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         tail.buf = dOxSendBuf.as<double>();
     }
     auto upTier = [&](int k, const int* list, int ntask, const double* recv, double* send, const UpTail* tl = nullptr) {
-        launch_up_tier(K, ntask, plan.upTierTask[k], list, plan.upTierMaxTask[k], dUpDesc.as<int4>(), dUpGrpFix.as<int>(),
-                       dUpNode.as<int>(), dUpCode.as<int4>(), dUpGeom.as<double4>(), dUpLeaf.as<int2>(),
-                       dPxT.as<double>(), dPyT.as<double>(), x, ldx, treeIn ? 1 : 0, dPerm.as<int>(), sigT,
-                       dWT.as<double>(), fTw, cTw, P, dMult.as<double>(),
-                       recv ? dXRootSlot.as<int>() : nullptr, recv, send ? dXSendSlot.as<int>() : nullptr, send, s,
-                       topFused && k == 0 ? dTopCnt.as<unsigned>() : nullptr, tl);
+        unsigned* const zeroCnt = topFused && k == 0 ? dTopCnt.as<unsigned>() : nullptr;
+        upTier16(K, k, list, ntask, fTw, cTw, recv, send, zeroCnt, tl, in, s);
         if (fork && !nearIn && k == forkTier) HIP_CHECK(hipEventRecord(evFork, s));
     };
     auto tierTasks = [&](int k) { return plan.upTierTask[k + 1] - plan.upTierTask[k]; };
@@ -1218,14 +1311,14 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     // near field + corrections (they need only fT / cT, or with nearIn the input)
     auto nearStage = [&] {
         if (fork) HIP_CHECK(hipStreamWaitEvent(side, evFork, 0));
-        const int en = tr ? mark(sn) : -1;
+        StageSpans ns(*this, sn);
         bool corrFused = false;
         if (harmonic) {
             // the corrections ride in the staged near kernel (d = 1, its table holds
             // every stencil neighbour; Plan::nearCorrRow)
             corrFused = launch_near_hm(K, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), hmPtsPtr,
                            dNearPts.as<int>(), hmKOff, dAttNear.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
-                           dSigDiag.as<double>(), hw, dFT.as<double>(), operm, obase, ldo, mask, scale, out, hmLoc,
+                           dSigDiag.as<double>(), hw, dFT.as<double>(), o.perm, o.base, ldo, mask, kScale, out, hmLoc,
                            dNsPtr.as<int64_t>(), dNsPts.as<int>(), plan.nsMax, plan.nearCorrOk ? &nc : nullptr,
                            nearWpe, sn, &nin, win);
         } else if (plan.nearPartTotal > 0) {
@@ -1237,21 +1330,19 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
                 const double sgn = (id % 2 == 0) ? 1.0 : -1.0;
                 launch_near_sym(K, (int)plan.leaves.size(), dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
                                 dNearPts.as<int>(), dNearKOff.as<int64_t>(), dNearSym.as<int2>(),
-                                modes[id].Knear.as<double>(), dFT.as<double>(), mixes + (size_t)t * K * K, operm,
-                                obase, ldo, maxNearS, mask, sgn, scale, t > 0 ? 1 : 0, dNearPart.as<double>(), out, s);
+                                modes[id].Knear.as<double>(), dFT.as<double>(), mixes + (size_t)t * K * K, o.perm,
+                                o.base, ldo, maxNearS, mask, sgn, kScale, t > 0 ? 1 : 0, dNearPart.as<double>(), out,
+                                s);
             }
         } else {  // directed storage: all terms in one launch
             launch_near(K, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
-                        dNearPts.as<int>(), dNearKOff.as<int64_t>(), tab, nterm, dFT.as<double>(), operm, obase, ldo,
-                        mask, scale, 0, out, s);
+                        dNearPts.as<int>(), dNearKOff.as<int64_t>(), tab, nterm, dFT.as<double>(), o.perm, o.base, ldo,
+                        mask, kScale, 0, out, s);
         }
-        const int e1 = tr ? mark(sn) : -1;
-        span(4, en, e1);
+        ns.end(4);
         if (!corrFused)
-            launch_corr(K, geo.d, plan.ownBegin, plan.ownEnd, dPerm.as<int>(), dIperm.as<int>(), dCT.as<double>(),
-                        dFT.as<double>(), cf.Wc.as<double>(), cf.Wm.as<double>(), P, mask, scale, treeOut, ldo, out, sn);
-        const int e2 = tm ? mark(sn) : -1;
-        span(6, e1, e2);
+            corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, mask, o, sn);
+        ns.end(6);
         if (fork) HIP_CHECK(hipEventRecord(evJoin, side));
     };
     const bool clustered = harmonic && useClusters && !win;  // a pass: the per-target launch (its offset form)
@@ -1328,8 +1419,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
             if (!fork && tm) e0 = mark(s);  // serial: the up span starts after the near field
         }
         if (ntier < 1) {  // a lone leaf: no up pass
-            launch_prepare(K, geo.N, x, ldx, treeIn ? 1 : 0, dPerm.as<int>(), sigT, dWT.as<double>(),
-                           dFT.as<double>(), dCT.as<double>(), s);
+            prepareCharges(K, in, dFT.as<double>(), dCT.as<double>(), s);
             if (fork) HIP_CHECK(hipEventRecord(evFork, s));
         }
         if (phase == 1 && ntier >= 1) {
@@ -1396,15 +1486,15 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         }
         e0 = ex;  // the up span of phase 2: upper tiers
     }
-    int ep = tr ? mark(s) : -1;
+    const int ep = tr ? mark(s) : -1;
     span(1, e0, ep);
-    if (phase >= 2) e0 = pend.e0;
+    StageSpans sp(*this, s, eStart, ep);  // the tail's spans: M2L, gather, down pass, total
     if (!nearDone && !nearFused) {
         // a sharded pass in the two-collective form: the side stream waits here, behind the
         // previous window's k_add_rows, which reads the rows this near field writes
         if (passShard && fork) HIP_CHECK(hipEventRecord(evFork, s));
         nearStage();
-        if (tr && sn == s) ep = mark(s);  // serial (ANISO_OVERLAP=0): the M2L span starts after the near field
+        if (sn == s) sp.start();  // serial (ANISO_OVERLAP=0): the M2L span starts after the near field
     }
     if (mask & kStageFar) {
         if (topFused) {
@@ -1429,8 +1519,8 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
             HIP_CHECK(hipHostGetDevicePointer((void**)&ta.err, topErr, 0));
             const NearHsArgs na{(int)plan.leaves.size(), plan.nsMax, dLeafInfo.as<int4>(), hmPtsPtr, hmLoc,
                           dNsPtr.as<int64_t>(), dNsPts.as<int>(), hmKOff, dAttNear.as<double>(), dPxT.as<double>(),
-                          dPyT.as<double>(), dSigDiag.as<double>(), hw, dFT.as<double>(), operm, obase, ldo, mask,
-                          scale, out, nc};
+                          dPyT.as<double>(), dSigDiag.as<double>(), hw, dFT.as<double>(), o.perm, o.base, ldo, mask,
+                          kScale, out, nc};
 
             if (topTraceOn) {
                 topTraceNear = nearFused ? (na.nl + 15) / 16 : 0;
@@ -1453,49 +1543,32 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
                        dMult.as<double>(), plan.m2lMaxCanon, dM2LPart.as<double>(), dLocal.as<double>(), s);
         }
     }
-    int e = tr ? mark(s) : -1;
-    span(2, ep, e);
-    ep = e;
+    sp.end(2);
     if (!harmonic && (mask & kStageFar) && plan.m2lCanon > 0) {
         launch_m2l_gather(K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dM2LInPtr.as<int>(), dM2LPart.as<double>(),
                           dLocal.as<double>(), s);
-        e = tm ? mark(s) : -1;
-        span(3, ep, e);
-        ep = e;
+        sp.end(3);
     }
     if (fork) HIP_CHECK(hipStreamWaitEvent(s, evJoin, 0));
-    // down pass (owned part): L2L + L2P + gathered transposed near products, once
-    // for the sum over the terms (both are linear in the locals / partials)
+    // down pass (owned part), once for the sum over the terms (it is linear in the locals and
+    // the partials).  The near partials: a single-RHS symmetric plan, or the harmonic one's
     if (mask & (kStageFar | kStageNear))
-        launch_down_tier(K, (int)plan.dnDesc.size() / 3, plan.dnMaxTask, plan.dnMaxLeaves, dDnDesc.as<int4>(),
-                         dDnGrpFix.as<int>(), dDnNode.as<int4>(), dLocal.as<double>(), P, dDnLeafSlot.as<int>(),
-                         dDnLeafPts.as<int>(), dDnLeafNear.as<int2>(), dDnLeafGeom.as<double4>(), dPxT.as<double>(),
-                         dPyT.as<double>(), operm, obase, ldo, dDnNearOff.as<int>(), plan.dnMaxNear,
-                         // the near partials: a single-RHS symmetric plan, or the harmonic one's
-                         (harmonic ? hsSym : plan.nearPartTotal > 0) ? dNearPart.as<double>() : nullptr,
-                         dDnChain.as<int2>(), plan.dnMaxChain, mask, scale, out, call.minuend, call.minuendLd,
-                         s, halo && clustered ? dHmPart.as<double>() : nullptr, dDnChainFold.as<int>());
-    if (tr) {
-        const int e2 = tm ? mark(s) : -1;
-        span(5, ep, e2);
-        span(7, eStart, e2);
-        ++applies;
-    }
+        downPass16(K, mask, (harmonic ? hsSym : plan.nearPartTotal > 0) ? dNearPart.as<double>() : nullptr,
+                   halo && clustered ? dHmPart.as<double>() : nullptr, o, s);
+    sp.end(5);
+    sp.total();  // (at level 2 this route has no first mark, so no total: DESIGN.md §3.18.4)
 }
 
-// applyBlock on a high-order handle (np = 6, 8): the harmonic block
-// apply with the far field of high_order.hip.  launch_prepare forms the weighted
-// charges, the unstaged harmonic near field stores `out` and the corrections add to it
-// (neither depends on the order); then P2M and M2M level by level, one M2L launch that
-// reads every stored E block once for all modes, L2L level by level and L2P, the last
-// writer (call.minuend: x - mforward(x)).  One stream, every sum in a fixed order.
-void Operator::applyBlockHigh(int K, const double* x, int64_t ldx, bool treeIn, const double* sigT, int nterm,
-                              const int* ids, const double* mixes, double* out, int64_t ldo, bool treeOut,
+// applyBlock on a high-order handle (np = 6, 8): the harmonic block apply
+// with the far field of high_order.hip, as the un-fused sequence above.  The unstaged
+// harmonic near field (it and the corrections do not depend on the order), and one M2L
+// launch that reads every stored E block once for all modes (o.minuend: x - mforward(x)).
+void Operator::applyBlockHigh(int K, const InRows& in, int nterm, const int* ids, const double* mixes, const OutRows& o,
                               hipStream_t s, int mask, const ApplyCall& call) {
     // a shard: only the matvec of a handle made by createSharded (call.hoShard), on the rank's
     // own lists below -- the whole input in tree order in, the owned slice out
     if (call.phase != 0 || (plan.nranks > 1 && !(hoShard && call.hoShard))) refuseHighOrder("a sharded apply");
-    if (hoShard && !(call.hoShard && treeIn && treeOut)) refuseHoShard("a block apply");
+    if (hoShard && !(call.hoShard && in.tree && o.tree)) refuseHoShard("a block apply");
     if (mask != kStageAll) refuseHighOrder("a per-stage apply");
     if (!attReady) throw std::runtime_error("high-order apply before cache()");
     HarmWeights hw;
@@ -1503,65 +1576,25 @@ void Operator::applyBlockHigh(int K, const double* x, int64_t ldx, bool treeIn, 
     if (win) hw = call.hw;
     else if (!harmonicWeights(K, nterm, ids, mixes, hw))
         refuseHighOrder("a block apply whose mixes are not aniso.m's forward / mforward");
-    const Params* P = dParams.as<Params>();
-    const HoTables* T = dHoTab.as<HoTables>();
-    const size_t R = (size_t)np * np;
-    if (K > hoWorkK) {
-        dHoMult.alloc((size_t)tree.nn * R * K * sizeof(double));
-        dHoLocal.alloc((size_t)tree.nn * R * K * sizeof(double));
-        hoWorkK = K;
-    }
-    // nodes that are no M2L target (the root, empty nodes) keep zero locals; a smaller K
-    // re-uses the buffers with its own strides
-    HIP_CHECK(hipMemsetAsync(dHoLocal.p, 0, (size_t)tree.nn * R * K * sizeof(double), s));
+    hoReserve(K, s);
     const CorrFold& cf = corrTable(K, nterm, ids, mixes);
-    const bool tr = timeStages != 0, tm = timeStages == 1;
-    auto span = [&](int stage, int a, int b) {
-        if (a >= 0 && b >= 0) spans.push_back({stage, a, b});
-    };
-    const int* operm = treeOut ? nullptr : dPerm.as<int>();
-    const int64_t obase = treeOut ? plan.ownBegin : 0;
-    const double scale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
-    const int nl = (int)plan.leaves.size();
-    const int e0 = tr ? mark(s) : -1;
-    launch_prepare(K, geo.N, x, ldx, treeIn ? 1 : 0, dPerm.as<int>(), sigT, dWT.as<double>(), dFT.as<double>(),
-                   dCT.as<double>(), s);
-    launch_near_hm(K, nl, plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(),
-                   dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
-                   dSigDiag.as<double>(), hw, dFT.as<double>(), operm, obase, ldo, mask, scale, out, nullptr, nullptr,
-                   nullptr, 0, nullptr, nearWpe, s, nullptr, win);
-    const int e1 = tr ? mark(s) : -1;
-    span(4, e0, e1);
-    launch_corr(K, geo.d, plan.ownBegin, plan.ownEnd, dPerm.as<int>(), dIperm.as<int>(), dCT.as<double>(),
-                dFT.as<double>(), cf.Wc.as<double>(), cf.Wm.as<double>(), P, mask, scale, treeOut, ldo, out, s);
-    const int e2 = tr ? mark(s) : -1;
-    if (tm) span(6, e1, e2);
+    StageSpans sp(*this, s);
+    prepareCharges(K, in, dFT.as<double>(), dCT.as<double>(), s);
+    nearUnstaged(K, hw, win, mask, o, s);
+    sp.end(4);
+    corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, mask, o, s);
+    sp.end(6);
     // (a shard: the up pass over every leaf of the tree -- the M2L reads any node's multipole)
-    launch_ho_p2m(np, K, hoShard ? hoLeafAll : nl, (hoShard ? dHoLeafAll : dLeafInfo).as<int4>(), dNcx.as<double>(),
-                  dNcy.as<double>(), dNrx.as<double>(), dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
-                  dFT.as<double>(), T, dHoMult.as<double>(), s);
-    for (size_t l = 0; l + 1 < hoM2mPtr.size(); ++l)
-        launch_ho_m2m(np, K, hoM2mPtr[l + 1] - hoM2mPtr[l], dHoM2m.as<int>() + hoM2mPtr[l], dHoChild.as<int4>(), T,
-                      dHoMult.as<double>(), s);
-    const int e3 = tr ? mark(s) : -1;
-    if (tm) span(1, e2, e3);
+    hoUpPass(K, dHoMult.as<double>(), hoShard, s);
+    sp.end(1);
+    sp.startRoofline();
     launch_ho_m2l(np, K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
                   dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                  dNry.as<double>(), T, hw, win, dHoMult.as<double>(), dHoLocal.as<double>(), s);
-    const int e4 = tr ? mark(s) : -1;
-    span(2, e3, e4);
-    for (size_t l = 0; l + 1 < hoL2lPtr.size(); ++l)
-        launch_ho_l2l(np, K, hoL2lPtr[l + 1] - hoL2lPtr[l], dHoL2l.as<int>() + hoL2lPtr[l], dParent.as<int>(),
-                      dSlot.as<int>(), T, dHoLocal.as<double>(), s);
-    launch_ho_l2p(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                  dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), T, dHoLocal.as<double>(), operm, obase, ldo,
-                  scale, out, call.minuend, call.minuendLd, s);
-    if (tr) {
-        const int e5 = mark(s);
-        if (tm) span(5, e4, e5);
-        span(7, e0, e5);
-        ++applies;
-    }
+                  dNry.as<double>(), dHoTab.as<HoTables>(), hw, win, dHoMult.as<double>(), dHoLocal.as<double>(), s);
+    sp.end(2);
+    hoDownPass(K, dHoLocal.as<double>(), o, s);
+    sp.end(5);
+    sp.total();
 }
 
 // ---- one mode on several vectors ----
@@ -1596,132 +1629,62 @@ bool Operator::modeApplyCheck(const char* what, int id, int nrhs, const void* x,
     return true;
 }
 
-// One chunk on a high-order handle: applyBlockHigh's launch sequence with the mode
-// kernels in place of launch_near_hm and launch_ho_m2l.  launch_prepare forms the
-// (sigma-weighted) charges; the near field stores `out`, the corrections of mode id
-// (identity fold) add to it; P2M and M2M level by level, the mode M2L, L2L level by
-// level and L2P, the last writer (minuend: x - K_id(...)).  The expansions live in the
-// block path's dHoMult / dHoLocal.
-void Operator::modeApplyHigh(int id, int K, const double* x, int64_t ldx, const double* sigT, const double* minuend,
-                             int64_t minuendLd, double* out, int64_t ldo, hipStream_t s) {
-    const Params* P = dParams.as<Params>();
-    const HoTables* T = dHoTab.as<HoTables>();
-    const size_t R = (size_t)np * np;
+// One chunk on a high-order handle: applyBlockHigh's sequence with the mode kernels in
+// place of launch_near_hm and launch_ho_m2l, and the corrections of mode id (identity
+// fold; o.minuend: x - K_id(...)).  The expansions live in the block path's dHoMult / dHoLocal.
+void Operator::modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, hipStream_t s) {
     ensureWork(K);
-    if (K > hoWorkK) {
-        dHoMult.alloc((size_t)tree.nn * R * K * sizeof(double));
-        dHoLocal.alloc((size_t)tree.nn * R * K * sizeof(double));
-        hoWorkK = K;
-    }
-    // nodes that are no M2L target keep zero locals (as applyBlockHigh)
-    HIP_CHECK(hipMemsetAsync(dHoLocal.p, 0, (size_t)tree.nn * R * K * sizeof(double), s));
-    std::vector<double> eye((size_t)K * K, 0.0);
-    for (int i = 0; i < K; ++i) eye[(size_t)i * K + i] = 1.0;
-    const CorrFold& cf = corrTable(K, 1, &id, eye.data());
-    const bool tr = timeStages != 0, tm = timeStages == 1;
-    auto span = [&](int stage, int a, int b) {
-        if (a >= 0 && b >= 0) spans.push_back({stage, a, b});
-    };
-    const int* operm = dPerm.as<int>();
-    const double scale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
-    const int nl = (int)plan.leaves.size();
-    const int e0 = tr ? mark(s) : -1;
-    launch_prepare(K, geo.N, x, ldx, 0, dPerm.as<int>(), sigT, dWT.as<double>(), dFT.as<double>(), dCT.as<double>(), s);
-    launch_near_mode(K, id, nl, plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(),
-                     dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
-                     dSigDiag.as<double>(), dFT.as<double>(), operm, 0, ldo, scale, out, s);
-    const int e1 = tr ? mark(s) : -1;
-    span(4, e0, e1);
-    launch_corr(K, geo.d, plan.ownBegin, plan.ownEnd, dPerm.as<int>(), dIperm.as<int>(), dCT.as<double>(),
-                dFT.as<double>(), cf.Wc.as<double>(), cf.Wm.as<double>(), P, kStageAll, scale, false, ldo, out, s);
-    const int e2 = tr ? mark(s) : -1;
-    if (tm) span(6, e1, e2);
-    launch_ho_p2m(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                  dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), dFT.as<double>(), T, dHoMult.as<double>(), s);
-    for (size_t l = 0; l + 1 < hoM2mPtr.size(); ++l)
-        launch_ho_m2m(np, K, hoM2mPtr[l + 1] - hoM2mPtr[l], dHoM2m.as<int>() + hoM2mPtr[l], dHoChild.as<int4>(), T,
-                      dHoMult.as<double>(), s);
-    const int e3 = tr ? mark(s) : -1;
-    if (tm) span(1, e2, e3);
+    hoReserve(K, s);
+    const CorrFold& cf = corrTable(K, 1, &id, identityMix(K).data());
+    StageSpans sp(*this, s);
+    prepareCharges(K, in, dFT.as<double>(), dCT.as<double>(), s);
+    nearMode(K, id, o, s);
+    sp.end(4);
+    corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
+    sp.end(6);
+    hoUpPass(K, dHoMult.as<double>(), false, s);
+    sp.end(1);
+    sp.startRoofline();
     launch_ho_m2l_mode(np, K, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
                        dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                       dNry.as<double>(), T, dHoMult.as<double>(), dHoLocal.as<double>(), s);
-    const int e4 = tr ? mark(s) : -1;
-    span(2, e3, e4);
-    for (size_t l = 0; l + 1 < hoL2lPtr.size(); ++l)
-        launch_ho_l2l(np, K, hoL2lPtr[l + 1] - hoL2lPtr[l], dHoL2l.as<int>() + hoL2lPtr[l], dParent.as<int>(),
-                      dSlot.as<int>(), T, dHoLocal.as<double>(), s);
-    launch_ho_l2p(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                  dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), T, dHoLocal.as<double>(), operm, 0, ldo, scale,
-                  out, minuend, minuendLd, s);
-    if (tr) {
-        const int e5 = mark(s);
-        if (tm) span(5, e4, e5);
-        span(7, e0, e5);
-        ++applies;
-    }
+                       dNry.as<double>(), dHoTab.as<HoTables>(), dHoMult.as<double>(), dHoLocal.as<double>(), s);
+    sp.end(2);
+    hoDownPass(K, dHoLocal.as<double>(), o, s);
+    sp.end(5);
+    sp.total();
 }
 
 // One chunk on a lean mode of an np = 4 handle: one pass of the offset form as leanMapping
-// ends up running it, un-fused, with the mode kernels in place of the offset near field and
-// M2L.  launch_prepare forms the (sigma-weighted) charges; the near field stores `out`, the
-// corrections of mode id (identity fold) add to it; the rank-16 up tiers on the K plain
-// columns, the mode M2L (plain sums into dLocal) and the down tiers, the last writer
-// (minuend: x - K_id(...), original order).  One stream, every sum in a fixed order.
-void Operator::modeApplyLean16(int id, int K, const double* x, int64_t ldx, const double* sigT, const double* minuend,
-                               int64_t minuendLd, double* out, int64_t ldo, hipStream_t s) {
+// ends up running it, as the un-fused sequence, with the mode kernels in place of the offset
+// near field and M2L: the corrections of mode id (identity fold), the rank-16 up tiers on the
+// K plain columns, the mode M2L (plain sums into dLocal) and the down tiers (o.minuend:
+// x - K_id(...), original order).
+void Operator::modeApplyLean16(int id, int K, const InRows& in, const OutRows& o, hipStream_t s) {
     ensureWork(K);
     if (up_tier_lds(plan.upMaxTask, K) > 160 * 1024 ||
         down_tier_lds(plan.dnMaxTask, plan.dnMaxLeaves, plan.dnMaxNear, plan.dnMaxChain, K) > 160 * 1024)
         throw std::logic_error("up/down pass task exceeds one workgroup's LDS at " + std::to_string(K) + " right-hand sides");
-    const Params* P = dParams.as<Params>();
-    std::vector<double> eye((size_t)K * K, 0.0);
-    for (int i = 0; i < K; ++i) eye[(size_t)i * K + i] = 1.0;
-    const CorrFold& cf = corrTable(K, 1, &id, eye.data());
-    const bool tr = timeStages != 0, tm = timeStages == 1;
-    auto span = [&](int stage, int a, int b) {
-        if (a >= 0 && b >= 0) spans.push_back({stage, a, b});
-    };
-    const int* operm = dPerm.as<int>();
-    const double scale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
-    const int nl = (int)plan.leaves.size();
+    const CorrFold& cf = corrTable(K, 1, &id, identityMix(K).data());
     const int ntier = (int)plan.upTierTask.size() - 1;  // 0: a lone leaf
-    const int e0 = tr ? mark(s) : -1;
-    launch_prepare(K, geo.N, x, ldx, 0, dPerm.as<int>(), sigT, dWT.as<double>(), dFT.as<double>(), dCT.as<double>(), s);
-    launch_near_mode(K, id, nl, plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(),
-                     dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
-                     dSigDiag.as<double>(), dFT.as<double>(), operm, 0, ldo, scale, out, s);
-    const int e1 = tr ? mark(s) : -1;
-    span(4, e0, e1);
-    launch_corr(K, geo.d, plan.ownBegin, plan.ownEnd, dPerm.as<int>(), dIperm.as<int>(), dCT.as<double>(),
-                dFT.as<double>(), cf.Wc.as<double>(), cf.Wm.as<double>(), P, kStageAll, scale, false, ldo, out, s);
-    const int e2 = tr ? mark(s) : -1;
-    if (tm) span(6, e1, e2);
+    StageSpans sp(*this, s);
+    prepareCharges(K, in, dFT.as<double>(), dCT.as<double>(), s);
+    nearMode(K, id, o, s);
+    sp.end(4);
+    corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
+    sp.end(6);
     // (the up tiers form their charges from the input again and store none: launch_prepare did)
     for (int k = 0; k < ntier; ++k)
-        launch_up_tier(K, plan.upTierTask[k + 1] - plan.upTierTask[k], plan.upTierTask[k], nullptr, plan.upTierMaxTask[k],
-                       dUpDesc.as<int4>(), dUpGrpFix.as<int>(), dUpNode.as<int>(), dUpCode.as<int4>(),
-                       dUpGeom.as<double4>(), dUpLeaf.as<int2>(), dPxT.as<double>(), dPyT.as<double>(), x, ldx, 0,
-                       dPerm.as<int>(), sigT, dWT.as<double>(), nullptr, nullptr, P, dMult.as<double>(), nullptr, nullptr,
-                       nullptr, nullptr, s);
-    const int e3 = tr ? mark(s) : -1;
-    if (tm) span(1, e2, e3);
+        upTier16(K, k, nullptr, plan.upTierTask[k + 1] - plan.upTierTask[k], nullptr, nullptr, nullptr, nullptr,
+                 nullptr, nullptr, in, s);
+    sp.end(1);
+    sp.startRoofline();
     launch_m2l_mode16(K, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
                       dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                      dNry.as<double>(), P, dMult.as<double>(), dLocal.as<double>(), s);
-    const int e4 = tr ? mark(s) : -1;
-    span(2, e3, e4);
-    launch_down_tier(K, (int)plan.dnDesc.size() / 3, plan.dnMaxTask, plan.dnMaxLeaves, dDnDesc.as<int4>(),
-                     dDnGrpFix.as<int>(), dDnNode.as<int4>(), dLocal.as<double>(), P, dDnLeafSlot.as<int>(),
-                     dDnLeafPts.as<int>(), dDnLeafNear.as<int2>(), dDnLeafGeom.as<double4>(), dPxT.as<double>(),
-                     dPyT.as<double>(), operm, 0, ldo, dDnNearOff.as<int>(), plan.dnMaxNear, nullptr, dDnChain.as<int2>(),
-                     plan.dnMaxChain, kStageAll, scale, out, minuend, minuendLd, s, nullptr, dDnChainFold.as<int>());
-    if (tr) {
-        const int e5 = mark(s);
-        if (tm) span(5, e4, e5);
-        span(7, e0, e5);
-        ++applies;
-    }
+                      dNry.as<double>(), dParams.as<Params>(), dMult.as<double>(), dLocal.as<double>(), s);
+    sp.end(2);
+    downPass16(K, kStageAll, nullptr, nullptr, o, s);
+    sp.end(5);
+    sp.total();
 }
 
 void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, const double* sigT, bool minuend,
@@ -1748,8 +1711,10 @@ void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, cons
         }
         const bool sub = minuend && !viaBuffer;
         auto chunk = [&](int K, const double* xc, int64_t ldc, double* oc, int64_t ldoc) {
-            if (lean16) modeApplyLean16(id, K, xc, ldc, sigT, sub ? xc : nullptr, ldc, oc, ldoc, s);
-            else modeApplyHigh(id, K, xc, ldc, sigT, sub ? xc : nullptr, ldc, oc, ldoc, s);
+            const InRows in{xc, ldc, false, sigT};
+            const OutRows o = outRows(oc, ldoc, false, sub ? xc : nullptr, ldc);
+            if (lean16) modeApplyLean16(id, K, in, o, s);
+            else modeApplyHigh(id, K, in, o, s);
             modeCalls.push_back(K);
         };
         for (int j0 = 0; j0 < nrhs; j0 += kMaxRhs) {
@@ -1766,12 +1731,9 @@ void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, cons
             const size_t pb = (size_t)K * N * sizeof(double);
             if (dPadIn.bytes < pb) dPadIn.alloc(pb);
             if (dPadOut.bytes < pb) dPadOut.alloc(pb);
-            HIP_CHECK(hipMemsetAsync(dPadIn.p, 0, pb, s));
-            HIP_CHECK(hipMemcpy2DAsync(dPadIn.p, N * sizeof(double), xc, ldx * sizeof(double), N * sizeof(double), nb,
-                                       hipMemcpyDeviceToDevice, s));
+            padRowsIn(dPadIn, 1, nb, K, xc, ldx, s);
             chunk(K, dPadIn.as<double>(), N, dPadOut.as<double>(), N);
-            HIP_CHECK(hipMemcpy2DAsync(oc, ldd * sizeof(double), dPadOut.p, N * sizeof(double), N * sizeof(double), nb,
-                                       hipMemcpyDeviceToDevice, s));
+            padRowsOut(dPadOut.as<double>(), nb, N, oc, ldd, s);
         }
         if (viaBuffer) launch_sub_slice(N, nrhs, x, ldx, dBlk.as<double>(), N, out, ldo, s);
         return;
@@ -1788,11 +1750,9 @@ void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, cons
     if (modes[id].resident) {  // mappingBatchedHost's 8-column branch on device pointers
         for (int j0 = 0; j0 < nrhs; j0 += kMaxRhs) {
             const int nb = std::min(kMaxRhs, nrhs - j0);
-            std::vector<double> eye((size_t)nb * nb, 0.0);
-            for (int i = 0; i < nb; ++i) eye[(size_t)i * nb + i] = 1.0;
             ApplyCall call;
-            applyBlock(nb, x + (size_t)j0 * ldx, ldx, false, sigT, 1, &id, eye.data(), dst + (size_t)j0 * ldd, ldd, false,
-                       s, kStageAll, call);
+            applyBlock(nb, x + (size_t)j0 * ldx, ldx, false, sigT, 1, &id, identityMix(nb).data(),
+                       dst + (size_t)j0 * ldd, ldd, false, s, kStageAll, call);
             modeCalls.push_back(rootRhs(nb));  // (applyBlock pads the chunk to the next compiled count)
         }
     } else {  // a lean mode the mode kernels do not serve: one pass of the offset form per column
@@ -1999,9 +1959,7 @@ std::pair<double*, int64_t> Operator::stagePassInput(double* x, int64_t ldx, int
     double* const xin = x + (size_t)b0 * ldx;
     if (nin == K) return {xin, ldx};
     dPassIn.alloc((size_t)K * N * sizeof(double));
-    HIP_CHECK(hipMemsetAsync(dPassIn.p, 0, dPassIn.bytes, s));
-    HIP_CHECK(hipMemcpy2DAsync(dPassIn.p, N * sizeof(double), xin, ldx * sizeof(double), N * sizeof(double), nin,
-                               hipMemcpyDeviceToDevice, s));
+    padRowsIn(dPassIn, 1, nin, K, xin, ldx, s);
     return {dPassIn.as<double>(), N};
 }
 
@@ -2146,78 +2104,49 @@ void Operator::blockMultiChunk(int which, int S, int nreal, const double* x, int
     if (!harmonicWeights(K, nm, ids.data(), mix.data(), hw))
         throw std::logic_error("multi-source block operator: the mode-shared caches are not ready");
     const double* sigT = which != 0 ? dSigmaT.as<double>() : nullptr;
-    const Params* P = dParams.as<Params>();
-    const HoTables* T = dHoTab.as<HoTables>();
     blockMultiReserve(S);
-    const size_t exp = (size_t)tree.nn * np * np * K;  // doubles of one expansion buffer
+    const size_t exp = hoDoubles(K);
     const CorrFold& cf = corrTable(K, nm, ids.data(), mix.data());
+    // source j's rows: the caller's, or its K rows of the padded buffers (stride N)
     const bool padded = K != nb;
-    auto xin = [&](int j) { return padded ? dMsIn.as<double>() + (size_t)j * K * N : x + (size_t)j * nb * ldx; };
-    auto xout = [&](int j) { return padded ? dMsOut.as<double>() + (size_t)j * K * N : out + (size_t)j * nb * ldo; };
-    const int64_t ldi = padded ? N : ldx, ldw = padded ? N : ldo;  // the strides of xin / xout
-    const bool tr = timeStages != 0, tm = timeStages == 1;
-    auto span = [&](int stage, int a, int b) {
-        if (a >= 0 && b >= 0) spans.push_back({stage, a, b});
+    const double* const xs = padded ? dMsIn.as<double>() : x;
+    double* const os = padded ? dMsOut.as<double>() : out;
+    const int64_t ldi = padded ? N : ldx, ldw = padded ? N : ldo;
+    const size_t rows = padded ? K : nb;
+    auto rowsIn = [&](int j) { return InRows{xs + j * rows * ldi, ldi, false, sigT}; };
+    auto rowsOut = [&](int j) {
+        return outRows(os + j * rows * ldw, ldw, false, which == 2 ? xs + j * rows * ldi : nullptr, ldi);
     };
-    const int* operm = dPerm.as<int>();
-    const double scale = M_1_PI / 2.0;  // AnisoWrapper.cpp:129-130
-    const int nl = (int)plan.leaves.size();
-    const int e0 = tr ? mark(s) : -1;
-    if (padded) {
-        HIP_CHECK(hipMemsetAsync(dMsIn.p, 0, (size_t)nreal * K * N * sizeof(double), s));
-        for (int j = 0; j < nreal; ++j)
-            HIP_CHECK(hipMemcpy2DAsync(dMsIn.as<double>() + (size_t)j * K * N, N * sizeof(double), x + (size_t)j * nb * ldx,
-                                       ldx * sizeof(double), N * sizeof(double), nb, hipMemcpyDeviceToDevice, s));
-    }
+    StageSpans sp(*this, s);
+    if (padded) padRowsIn(dMsIn, nreal, nb, K, x, ldx, s);
     // nodes that are no M2L target (the root, empty nodes) keep zero locals
     HIP_CHECK(hipMemsetAsync(dMsLocal.p, 0, (size_t)S * exp * sizeof(double), s));
     if (nreal < S)
         HIP_CHECK(hipMemsetAsync(dMsMult.as<double>() + (size_t)nreal * exp, 0, (size_t)(S - nreal) * exp * sizeof(double), s));
     for (int j = 0; j < nreal; ++j) {
-        double* mj = dMsMult.as<double>() + (size_t)j * exp;
-        const int a0 = tr ? mark(s) : -1;
-        launch_prepare(K, N, xin(j), ldi, 0, dPerm.as<int>(), sigT, dWT.as<double>(), dFT.as<double>(), dCT.as<double>(), s);
-        launch_near_hm(K, nl, plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(),
-                       dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
-                       dSigDiag.as<double>(), hw, dFT.as<double>(), operm, 0, ldw, kStageAll, scale, xout(j), nullptr,
-                       nullptr, nullptr, 0, nullptr, nearWpe, s, nullptr, nullptr);
-        const int a1 = tr ? mark(s) : -1;
-        span(4, a0, a1);
-        launch_corr(K, geo.d, plan.ownBegin, plan.ownEnd, dPerm.as<int>(), dIperm.as<int>(), dCT.as<double>(),
-                    dFT.as<double>(), cf.Wc.as<double>(), cf.Wm.as<double>(), P, kStageAll, scale, false, ldw, xout(j), s);
-        const int a2 = tr ? mark(s) : -1;
-        if (tm) span(6, a1, a2);
-        launch_ho_p2m(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                      dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), dFT.as<double>(), T, mj, s);
-        for (size_t l = 0; l + 1 < hoM2mPtr.size(); ++l)
-            launch_ho_m2m(np, K, hoM2mPtr[l + 1] - hoM2mPtr[l], dHoM2m.as<int>() + hoM2mPtr[l], dHoChild.as<int4>(), T, mj,
-                          s);
-        if (tm) span(1, a2, mark(s));
+        const OutRows o = rowsOut(j);
+        sp.start();
+        prepareCharges(K, rowsIn(j), dFT.as<double>(), dCT.as<double>(), s);
+        nearUnstaged(K, hw, nullptr, kStageAll, o, s);
+        sp.end(4);
+        corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
+        sp.end(6);
+        hoUpPass(K, dMsMult.as<double>() + (size_t)j * exp, false, s);
+        sp.end(1);
     }
-    const int e3 = tr ? mark(s) : -1;
+    sp.start();
     launch_ho_m2l_src(np, K, S, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
                       dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                      dNry.as<double>(), T, hw, dMsMult.as<double>(), (int64_t)exp, dMsLocal.as<double>(), (int64_t)exp, s);
-    const int e4 = tr ? mark(s) : -1;
-    span(2, e3, e4);
+                      dNry.as<double>(), dHoTab.as<HoTables>(), hw, dMsMult.as<double>(), (int64_t)exp,
+                      dMsLocal.as<double>(), (int64_t)exp, s);
+    sp.end(2);
     for (int j = 0; j < nreal; ++j) {
-        double* lj = dMsLocal.as<double>() + (size_t)j * exp;
-        for (size_t l = 0; l + 1 < hoL2lPtr.size(); ++l)
-            launch_ho_l2l(np, K, hoL2lPtr[l + 1] - hoL2lPtr[l], dHoL2l.as<int>() + hoL2lPtr[l], dParent.as<int>(),
-                          dSlot.as<int>(), T, lj, s);
-        launch_ho_l2p(np, K, nl, dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                      dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), T, lj, operm, 0, ldw, scale, xout(j),
-                      which == 2 ? xin(j) : nullptr, ldi, s);
-        if (padded)
-            HIP_CHECK(hipMemcpy2DAsync(out + (size_t)j * nb * ldo, ldo * sizeof(double), xout(j), N * sizeof(double),
-                                       N * sizeof(double), nb, hipMemcpyDeviceToDevice, s));
+        const OutRows o = rowsOut(j);
+        hoDownPass(K, dMsLocal.as<double>() + (size_t)j * exp, o, s);
+        if (padded) padRowsOut(o.out, nb, N, out + (size_t)j * nb * ldo, ldo, s);
     }
-    if (tr) {
-        const int e5 = mark(s);
-        if (tm) span(5, e4, e5);
-        span(7, e0, e5);
-        ++applies;
-    }
+    sp.end(5);
+    sp.total();
 }
 
 void Operator::blockOpMultiDev(int which, int nsrc, const double* x, int64_t ldx, double* out, int64_t ldo,
@@ -2314,10 +2243,9 @@ void Operator::directCorr(int K, const double* x, int64_t ldx, const double* sig
         dDirC.alloc(cb);
     }
     const CorrFold& cf = corrTable(K, nterm, ids, mixes);
-    launch_prepare(K, N, x, ldx, 0, dPerm.as<int>(), sig, dWT.as<double>(), dDirF.as<double>(), dDirC.as<double>(), s);
-    launch_corr(K, geo.d, 0, N, dPerm.as<int>(), dIperm.as<int>(), dDirC.as<double>(), dDirF.as<double>(),
-                cf.Wc.as<double>(), cf.Wm.as<double>(), dParams.as<Params>(), kStageStencil | kStageSing,
-                M_1_PI / 2.0, false, N, corr, s);
+    prepareCharges(K, InRows{x, ldx, false, sig}, dDirF.as<double>(), dDirC.as<double>(), s);
+    corrections(K, cf, dDirF.as<double>(), dDirC.as<double>(), 0, N, kStageStencil | kStageSing,
+                outRows(corr, N, false), s);
 }
 
 // One window's rows for every target, a bounded number of targets per launch.
@@ -2410,9 +2338,7 @@ void Operator::blockOpDirectDev(int which, const double* x, int64_t ldx, const i
         int64_t ldi = ldx;
         if (nin < K) {  // the last chunk zero-padded to 8 rows
             if (dDirIn.bytes < (size_t)K * N * sizeof(double)) dDirIn.alloc((size_t)K * N * sizeof(double));
-            HIP_CHECK(hipMemsetAsync(dDirIn.p, 0, (size_t)K * N * sizeof(double), s));
-            HIP_CHECK(hipMemcpy2DAsync(dDirIn.p, N * sizeof(double), xin, ldx * sizeof(double), N * sizeof(double), nin,
-                                       hipMemcpyDeviceToDevice, s));
+            padRowsIn(dDirIn, 1, nin, K, xin, ldx, s);
             xin = dDirIn.as<double>();
             ldi = N;
         }
@@ -3380,9 +3306,8 @@ void Operator::blockOpShardedPasses(int which, double* x, int64_t ldx, double* y
         shardedExchange(
             K, xin, ldin, one, s, [&](ApplyCall& call) { pass(call, 0, 1); },
             [&](ApplyCall& call) {
-                if (nin < K)  // the caller's x has its halo filled for every row
-                    HIP_CHECK(hipMemcpy2DAsync(x + (size_t)b0 * ldx, ldx * sizeof(double), xin, N * sizeof(double),
-                                               N * sizeof(double), nin, hipMemcpyDeviceToDevice, s));
+                // the caller's x has its halo filled for every row
+                if (nin < K) padRowsOut(xin, nin, N, x + (size_t)b0 * ldx, ldx, s);
                 for (int I = 0; I < P; ++I) {
                     pass(call, I, I == 0 ? 2 : 3);
                     launch_add_rows(own, std::min(K, ks - I * K), dPassOut.as<double>(), own, acc + (size_t)I * K * lda,

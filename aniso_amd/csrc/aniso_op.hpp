@@ -102,6 +102,23 @@ struct ApplyCall {
     ExchangeForm exch;
 };
 
+// The K input rows of an apply (tree: in tree order; sigT: sigma_s in tree order, multiplied
+// into the charges, or nullptr) and its output rows (Operator::outRows: perm / base place a
+// tree position in `out`; the last writer stores minuend - (...) where minuend is set).
+struct InRows {
+    const double* x;
+    int64_t ld;
+    bool tree;
+    const double* sigT;
+};
+struct OutRows {
+    double* out;
+    const double* minuend;
+    const int* perm;
+    int64_t ld, base, minuendLd;
+    bool tree;
+};
+
 class Operator {
 public:
     // shardRank / shardRanks: the shard of a handle made by aniso_create_sharded at np = 6, 8
@@ -483,9 +500,8 @@ private:
     void shardedExchange(int nb, double* x, int64_t ldx, bool one, hipStream_t s, const PhaseFn& phase1,
                          const PhaseFn& phase2);
     // the far field of a high-order handle (high_order.hip): applyBlock's branch for np != 4
-    void applyBlockHigh(int K, const double* x, int64_t ldx, bool treeIn, const double* sigT, int nterm, const int* ids,
-                        const double* mixes, double* out, int64_t ldo, bool treeOut, hipStream_t s, int mask,
-                        const ApplyCall& call);
+    void applyBlockHigh(int K, const InRows& in, int nterm, const int* ids, const double* mixes, const OutRows& o,
+                        hipStream_t s, int mask, const ApplyCall& call);
     void uploadHighPlan();  // its tables and level lists (ensureDevice: they follow the tree alone)
     DevBuf dHoTab, dHoChild, dHoM2m, dHoL2l, dHoMult, dHoLocal;
     // a sharded high-order handle: every non-empty leaf (the replicated P2M; dLeafInfo keeps
@@ -499,6 +515,26 @@ private:
     void blockOpShardedHigh(int which, double* x, int64_t ldx, double* yo, int64_t ldo, hipStream_t s);
     std::vector<int> hoM2mPtr, hoL2lPtr;  // per level: its range of dHoM2m (bottom-up) / dHoL2l (top-down)
     int hoWorkK = 0;
+    // the stages of the un-fused applies, one launcher's arguments each
+    OutRows outRows(double* out, int64_t ld, bool tree, const double* minuend = nullptr, int64_t minuendLd = 0) const {
+        return {out, minuend, tree ? nullptr : dPerm.as<int>(), ld, tree ? plan.ownBegin : 0, minuendLd, tree};
+    }
+    void prepareCharges(int K, const InRows& in, double* fT, double* cT, hipStream_t s);
+    void nearUnstaged(int K, const HarmWeights& hw, const HarmWindow* win, int mask, const OutRows& o, hipStream_t s);
+    void nearMode(int K, int id, const OutRows& o, hipStream_t s);
+    void corrections(int K, const CorrFold& cf, const double* fT, const double* cT, int64_t begin, int64_t end,
+                     int mask, const OutRows& o, hipStream_t s);
+    void hoReserve(int K, hipStream_t s);  // dHoMult / dHoLocal for K columns (grown, never shrunk), the locals zeroed
+    size_t hoDoubles(int K) const { return (size_t)tree.nn * np * np * K; }  // one expansion buffer
+    void hoUpPass(int K, double* mult, bool allLeaves, hipStream_t s);  // allLeaves: a shard's replicated P2M
+    void hoDownPass(int K, double* local, const OutRows& o, hipStream_t s);
+    void upTier16(int K, int k, const int* list, int ntask, double* fT, double* cT, const double* recv, double* send,
+                  unsigned* zeroCnt, const UpTail* tail, const InRows& in, hipStream_t s);
+    void downPass16(int K, int mask, const double* nearPart, const double* hpart, const OutRows& o, hipStream_t s);
+    // groups of nb rows (stride ldx) into the first nb of each group's K rows of buf (stride N),
+    // the other rows zero; and the first n points of the nb rows of one group back out
+    void padRowsIn(DevBuf& buf, int groups, int nb, int K, const double* x, int64_t ldx, hipStream_t s);
+    void padRowsOut(const double* group, int nb, int64_t n, double* out, int64_t ldo, hipStream_t s);
     // blockOpMultiDev's chunk of S in {1, 2, 4} sources (nreal of them present, the rest zero)
     // on a high-order handle: its S multipole and S local buffers, and the chunk's rows padded
     // to the compiled block count (grown, never shrunk: a hipFree synchronises the device)
@@ -510,11 +546,9 @@ private:
     // (sigT: tree-order sigma_s multiplied into the charge by the pass's launch_prepare)
     void leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask, const double* sigT = nullptr);
     // modeApplyDev's chunk of K = 2, 4, 5 or 8 columns on a high-order handle
-    void modeApplyHigh(int id, int K, const double* x, int64_t ldx, const double* sigT, const double* minuend,
-                       int64_t minuendLd, double* out, int64_t ldo, hipStream_t s);
+    void modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, hipStream_t s);
     // modeApplyDev's chunk of K = 2, 4, 5 or 8 columns on a lean mode of an np = 4 handle
-    void modeApplyLean16(int id, int K, const double* x, int64_t ldx, const double* sigT, const double* minuend,
-                         int64_t minuendLd, double* out, int64_t ldo, hipStream_t s);
+    void modeApplyLean16(int id, int K, const InRows& in, const OutRows& o, hipStream_t s);
     // the modes of a batched apply are usable by it: tables for the harmonic launches,
     // resident operators for the per-mode stream (checked before anything is launched)
     void checkModes(int K, int nterm, const int* ids, const double* mixes, const ApplyCall& call) const;
@@ -693,6 +727,31 @@ private:
     std::vector<Span> spans;
     int applies = 0;
     int mark(hipStream_t s);
+    // The spans of one apply on stream s: a stage ends where end(stage) stands and starts at the
+    // previous mark.  Level 1 records every stage, level 2 the roofline stages only (M2L, 2; near
+    // field, 4): one that follows another stage has startRoofline() before it.  total(): the
+    // span from the first mark (none: no total) to the last, and the apply is counted.
+    struct StageSpans {
+        Operator& op;
+        const hipStream_t s;
+        const bool tr = op.timeStages != 0, tm = op.timeStages == 1;
+        int first, prev;  // the apply's first mark and its latest (-1: none): a new one, or the caller's (resumes)
+        StageSpans(Operator& o, hipStream_t st) : op(o), s(st) { first = prev = tr ? op.mark(s) : -1; }
+        StageSpans(Operator& o, hipStream_t st, int e0, int e) : op(o), s(st), first(e0), prev(e) {}  // resumes
+        void start() { if (tr) prev = op.mark(s); }
+        void startRoofline() { if (tr && !tm) prev = op.mark(s); }
+        void end(int stage) {
+            if (!(tm || (tr && (stage == 2 || stage == 4)))) return;
+            const int e = op.mark(s);
+            if (prev >= 0) op.spans.push_back({stage, prev, e});
+            prev = e;
+        }
+        void total() {
+            if (tr && !tm && first >= 0) prev = op.mark(s);
+            if (tr && first >= 0 && prev >= 0) op.spans.push_back({7, first, prev});
+            if (tr) ++op.applies;
+        }
+    };
     int maxNearS = 0;
     // geometry / tree on device
     DevBuf dPxT, dPyT, dPerm, dW, dNcx, dNcy, dNrx, dNry, dBegin, dCount, dParent, dSlot, dChild, dIsLeaf, dNodeGeo;
