@@ -23,11 +23,12 @@ SHAPES = {
     "A": (32, 1, 5, 6, "demo"),
     "B": (32, 1, 3, 8, "demo"),   # K padded to 4
     "C": (19, 3, 2, 6, "rough"),  # W and X lists
+    "D": (11, 3, 2, 8, "rough"),  # W and X lists at np = 8, leaves of 12..64 points
     "T": (16, 1, 2, 8, "demo"),   # N = 256, four leaves, no M2L pair, ranks that own nothing
     "S": (32, 1, 3, 6, "demo"),   # the solve (55 steps unsharded)
     "K9": (16, 1, 9, 6, "demo"),  # more blocks than the sharded matvec holds
 }
-CASES = [("A", 2), ("A", 3), ("A", 4), ("B", 2), ("C", 3), ("T", 8)]
+CASES = [("A", 2), ("A", 3), ("A", 4), ("B", 2), ("C", 3), ("D", 3), ("T", 8)]
 
 
 def _torch():
@@ -260,7 +261,7 @@ def _case(shape, world):
 @pytest.mark.parametrize("shape,world", CASES, ids=[f"{s}w{w}" for s, w in CASES])
 def test_owned_slices_compose_the_unsharded_operator(shape, world):
     """Checks 1 and 2: the assembled owned slices against the unsharded handle (1e-12) and,
-    on A and C, the oracle (1e-10); no NaN inside an owned slice, nothing written outside
+    on A, C and D, the oracle (1e-10); no NaN inside an owned slice, nothing written outside
     it; every rank's x is the whole input afterwards, bit for bit; one all-gather per
     matvec and nothing else; the second matvec returns the first's bits."""
     torch = _torch()
@@ -288,14 +289,15 @@ def test_owned_slices_compose_the_unsharded_operator(shape, world):
         err = float(torch.linalg.norm(Y - refs[which]) / torch.linalg.norm(refs[which]))
         print(f"{shape} world {world} which {which}: rel err vs unsharded {err:.3e}")
         assert err <= TOL_ROUNDING, (which, err)
-        if shape in ("A", "C"):
+        if shape in ("A", "C", "D"):
             ref = _oracle_refs(shape)[which]
             oerr = float(np.linalg.norm(Y.cpu().numpy() - ref) / np.linalg.norm(ref))
             print(f"{shape} world {world} which {which}: rel err vs oracle {oerr:.3e}")
             assert oerr <= TOL_ORACLE, (which, oerr)
 
 
-@pytest.mark.parametrize("shape,world", [("A", 3), ("B", 2), ("T", 8)], ids=["Aw3", "Bw2", "Tw8"])
+@pytest.mark.parametrize("shape,world", [("A", 3), ("B", 2), ("D", 3), ("T", 8)],
+                         ids=["Aw3", "Bw2", "Dw3", "Tw8"])
 def test_caller_gathered_form_returns_the_same_bits(shape, world):
     """Check 3: block_op_dev(tree=True) on the whole input, no collective."""
     torch = _torch()
