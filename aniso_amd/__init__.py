@@ -85,6 +85,13 @@ def lib():
             "aniso_block_op_multi": [P, I, dp, I, dp],
             "aniso_block_solve_multi_dev": [P, I, P, I64, I, P, I64, I, D, I, ip, dp, dp, I, P],
             "aniso_block_solve_multi": [P, dp, I, I, dp, I, D, I, ip, dp],
+            "aniso_cache_f32": [P],
+            "aniso_cache_f32_bytes": [P, lp],
+            "aniso_mapping_multi_f32_dev": [P, I, I, P, I64, P, I64, P],
+            "aniso_forward_multi_f32_dev": [P, I, P, I64, P, I64, P],
+            "aniso_forward_solve_multi_mixed_dev": [P, I, P, I64, I, P, I64, I, D, D, I, I, ip, ip, dp, P],
+            "aniso_forward_solve_multi_mixed": [P, dp, I, I, dp, I, D, D, I, I, ip, ip, dp],
+            "aniso_forward_solve_mixed_calls": [P, ip, I, ip],
             "aniso_forward_solve_calls": [P, ip, I, ip],
             "aniso_mode_apply_calls": [P, ip, I, ip],
             "aniso_mapping_stages_dev": [P, P, I, I, P, P],
@@ -443,6 +450,97 @@ class Aniso:
                                                float(tol), int(maxit),
                                                iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(relres)))
         return X, iters, relres
+
+    # ---- the reduced-precision route of a high-order handle (np = 6, 8)
+    def cache_f32(self):
+        """Float mirrors of the mode-shared caches' M2L and near blocks (aniso_cache_f32): what
+        the f32 entries read.  They build them on first use; this call only moves that cost."""
+        _check(lib().aniso_cache_f32(self.address))
+
+    def cache_f32_bytes(self):
+        """Device bytes of the float mirrors, 0 when there are none."""
+        b = ctypes.c_int64()
+        _check(lib().aniso_cache_f32_bytes(self.address, ctypes.byref(b)))
+        return int(b.value)
+
+    def mapping_multi_f32_dev(self, X, id_, Out, stream=None):
+        """mapping_multi_dev with the M2L and the near field in fp32 (float64 tensors in and
+        out): the inexact operator of the mixed solve, about 1e-7 .. 1e-6 from the fp64 entry."""
+        import torch
+
+        nrhs = int(X.shape[0]) if isinstance(X, torch.Tensor) and X.dim() == 2 else -1
+        px, po = _dev_rows(X, nrhs, self.N, "X"), _dev_rows(Out, nrhs, self.N, "Out")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _check(lib().aniso_mapping_multi_f32_dev(self.address, int(id_), nrhs, px, max(X.stride(0), self.N), po,
+                                                 max(Out.stride(0), self.N), ctypes.c_void_p(s)))
+        return Out
+
+    def forward_multi_f32_dev(self, X, Out, stream=None):
+        """forward_multi_dev on the f32 operator: Out[k] = X[k] - K~_0(sigma_s .* X[k])."""
+        import torch
+
+        nrhs = int(X.shape[0]) if isinstance(X, torch.Tensor) and X.dim() == 2 else -1
+        px, po = _dev_rows(X, nrhs, self.N, "X"), _dev_rows(Out, nrhs, self.N, "Out")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _check(lib().aniso_forward_multi_f32_dev(self.address, nrhs, px, max(X.stride(0), self.N), po,
+                                                 max(Out.stride(0), self.N), ctypes.c_void_p(s)))
+        return Out
+
+    def forward_solve_multi_mixed_dev(self, Q, X, restart=80, tol=1e-12, inner_tol=1e-4, maxit=5, max_outer=10,
+                                      rhs_is_source=True, stream=None):
+        """forward_solve_multi_dev in mixed precision (aniso_forward_solve_multi_mixed_dev): an
+        fp64 refinement loop on explicit fp64 residuals around inner GMRES solves over the f32
+        operator (inner_tol, restart, maxit cycles each), at most max_outer refinements per
+        column.  Q and X as forward_solve_multi_dev takes them.  Returns (iters, outer, relres):
+        the inner steps per column (negative: not converged), its refinements, and its last
+        explicit fp64 relative residual."""
+        import torch
+
+        nrhs = int(Q.shape[0]) if isinstance(Q, torch.Tensor) and Q.dim() == 2 else -1
+        pq, px = _dev_rows(Q, nrhs, self.N, "Q"), _dev_rows(X, nrhs, self.N, "X")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        iters = np.zeros(max(nrhs, 1), dtype=np.int32)
+        outer = np.zeros(max(nrhs, 1), dtype=np.int32)
+        relres = np.zeros(max(nrhs, 1))
+        ipt = ctypes.POINTER(ctypes.c_int)
+        _check(lib().aniso_forward_solve_multi_mixed_dev(
+            self.address, nrhs, pq, max(Q.stride(0), self.N), int(bool(rhs_is_source)), px, max(X.stride(0), self.N),
+            int(restart), float(tol), float(inner_tol), int(maxit), int(max_outer), iters.ctypes.data_as(ipt),
+            outer.ctypes.data_as(ipt), _dp(relres), ctypes.c_void_p(s)))
+        return iters[:nrhs], outer[:nrhs], relres[:nrhs]
+
+    def forward_solve_multi_mixed(self, Q, restart=80, tol=1e-12, inner_tol=1e-4, maxit=5, max_outer=10,
+                                  rhs_is_source=True, x0=None):
+        """The same on numpy arrays (aniso_forward_solve_multi_mixed): Q is N x k; x0 (N x k) is
+        the initial guess, zero if None.  Returns (X (N x k), iters, outer, relres)."""
+        Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
+        if Q.ndim != 2 or Q.shape[0] != self.N:
+            raise AnisoError(1, f"Q must be N x k with N = {self.N}")
+        if x0 is None:
+            X = np.zeros(Q.shape, order="F")
+        else:
+            X = np.array(x0, dtype=np.float64, order="F")
+            if X.shape != Q.shape:
+                raise AnisoError(1, f"x0 must have Q's shape {Q.shape}")
+        k = Q.shape[1]
+        iters = np.zeros(max(k, 1), dtype=np.int32)
+        outer = np.zeros(max(k, 1), dtype=np.int32)
+        relres = np.zeros(max(k, 1))
+        ipt = ctypes.POINTER(ctypes.c_int)
+        _check(lib().aniso_forward_solve_multi_mixed(
+            self.address, _dp(Q), k, int(bool(rhs_is_source)), _dp(X), int(restart), float(tol), float(inner_tol),
+            int(maxit), int(max_outer), iters.ctypes.data_as(ipt), outer.ctypes.data_as(ipt), _dp(relres)))
+        return X, iters[:k], outer[:k], relres[:k]
+
+    def forward_solve_mixed_calls(self):
+        """Every operator pass of the last forward_solve_multi_mixed(_dev), in order: an (n, 2)
+        array of (precision 64 / 32, columns)."""
+        n = ctypes.c_int()
+        _check(lib().aniso_forward_solve_mixed_calls(self.address, None, 0, ctypes.byref(n)))
+        calls = np.zeros((max(n.value, 1), 2), dtype=np.int32)
+        _check(lib().aniso_forward_solve_mixed_calls(self.address, calls.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                     n.value, ctypes.byref(n)))
+        return calls[: n.value]
 
     def forward_solve_calls(self):
         """The column count of every operator call of the last forward_solve_multi(_dev), or the

@@ -449,6 +449,7 @@ void Operator::uploadPlan() {
         dTopSteals.alloc(sizeof(unsigned));
         HIP_CHECK(hipMemset(dTopSteals.p, 0, sizeof(unsigned)));
         attReady = false;
+        dropCacheF32();
     }
     up(dM2LCanonBase, plan.m2lCanonBase);
     up(dM2LInPtr, plan.m2lInPtr);
@@ -555,6 +556,7 @@ void Operator::setCoeff(const double* ss, const double* st) {
     up(dSigmaT, sT);
     for (auto& m : modes) m.tables = m.resident = false;
     attReady = false;
+    dropCacheF32();    // the float mirrors are rounded from the shared caches of sigma_t
     f32Ready = false;  // config 5's fp32 caches are rounded from the mode-0 operators of sigma_t
     m64.clear();       // ... and the fp64 16-RHS caches are the modes' operators
     coeffSet = true;
@@ -649,6 +651,35 @@ void Operator::cacheBytes(int64_t bytes[2]) const {
     bytes[1] = (int64_t)(dAttM2L.bytes + dAttNear.bytes + dSigDiag.bytes);
 }
 
+void Operator::dropCacheF32() {
+    dAttM2LF.alloc(0);
+    dAttNearF.alloc(0);
+}
+
+// The float mirrors of dAttM2L and dAttNear: one conversion launch.
+void Operator::cacheF32() {
+    if (!highOrder())
+        throw std::logic_error("aniso_cache_f32: an np = 4 handle has no f32 mode operator (its reduced-precision "
+                               "route is aniso_solve_mixed_dev)");
+    refuseHoShard("aniso_cache_f32");
+    if (!coeffSet || !attReady || !modes[0].tables)
+        throw std::runtime_error("aniso_cache_f32 before aniso_set_coeff and aniso_cache(0) or aniso_cache_block");
+    if (dAttM2LF.p && dAttNearF.p) return;
+    ensureDevice();
+    const size_t na = dAttM2L.bytes / sizeof(double), nb = dAttNear.bytes / sizeof(double);
+    try {
+        dAttM2LF.alloc(na * sizeof(float));
+        dAttNearF.alloc(nb * sizeof(float));
+    } catch (const std::exception& e) {
+        dropCacheF32();
+        throw std::runtime_error("aniso_cache_f32: the float mirrors of " + std::to_string(na * sizeof(float)) + " + " +
+                                 std::to_string(nb * sizeof(float)) + " bytes could not be allocated: " + e.what());
+    }
+    launch_cache_f32((int64_t)na, dAttM2L.as<double>(), dAttM2LF.as<float>(), (int64_t)nb, dAttNear.as<double>(),
+                     dAttNearF.as<float>(), own);
+    HIP_CHECK(hipStreamSynchronize(own));
+}
+
 void Operator::refuseHighOrder(const char* what) const {
     if (highOrder())
         throw std::logic_error(std::string(what) + ": a high-order handle (np = " + std::to_string(np) +
@@ -668,6 +699,7 @@ void Operator::needResident(int id, const char* what) const {
 // (column-major 16 x 16) and near block (the directed near layout), and sigma_t at
 // every point (the mode-0 diagonal).  Built once per setCoeff on a block handle.
 void Operator::buildAttCache() {
+    dropCacheF32();
     const Params* P = dParams.as<Params>();
     const int64_t npairs = (int64_t)(plan.attOwner.size() + plan.hmCopyOwner.size());  // stored blocks + copies
     const size_t rank = (size_t)np * np;
@@ -1056,7 +1088,15 @@ void Operator::nearUnstaged(int K, const HarmWeights& hw, const HarmWindow* win,
                    o.out, nullptr, nullptr, nullptr, 0, nullptr, nearWpe, s, nullptr, win);
 }
 
-void Operator::nearMode(int K, int id, const OutRows& o, hipStream_t s) {
+void Operator::nearMode(int K, int id, const OutRows& o, hipStream_t s, ApplyPrec prec) {
+    if (prec == ApplyPrec::F32) {
+        launch_near_mode_f32(K, id, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(),
+                             dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(), dNearKOff.as<int64_t>(),
+                             dAttNearF.as<float>(), dNcx.as<double>(), dNcy.as<double>(), dPxT.as<double>(),
+                             dPyT.as<double>(), dSigDiag.as<double>(), dFT.as<double>(), o.perm, o.base, o.ld, kScale,
+                             o.out, s);
+        return;
+    }
     launch_near_mode(K, id, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
                      dNearPts.as<int>(), dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(),
                      dPyT.as<double>(), dSigDiag.as<double>(), dFT.as<double>(), o.perm, o.base, o.ld, kScale, o.out,
@@ -1600,7 +1640,7 @@ void Operator::applyBlockHigh(int K, const InRows& in, int nterm, const int* ids
 // ---- one mode on several vectors ----
 
 bool Operator::modeApplyCheck(const char* what, int id, int nrhs, const void* x, int64_t ldx, const void* out,
-                              int64_t ldo, bool minuend) const {
+                              int64_t ldo, bool minuend, bool f32) const {
     const std::string w(what);
     if (nrhs < 0) throw std::invalid_argument(w + ": nrhs must be >= 0, got " + std::to_string(nrhs));
     if (ldx < geo.N) throw std::invalid_argument(w + ": ldx = " + std::to_string(ldx) + " is below N = " + std::to_string(geo.N));
@@ -1616,6 +1656,9 @@ bool Operator::modeApplyCheck(const char* what, int id, int nrhs, const void* x,
         const size_t xs = ((size_t)(nrhs - 1) * ldx + geo.N) * sizeof(double), os = ((size_t)(nrhs - 1) * ldo + geo.N) * sizeof(double);
         if (xb < ob + os && ob < xb + xs) throw std::invalid_argument(w + ": x and out overlap");
     }
+    if (f32 && !highOrder())
+        throw std::logic_error(w + ": the f32 mode operator is built for np = 6, 8; the reduced-precision route of an "
+                                   "np = 4 handle is aniso_solve_mixed_dev");
     refuseHoShard(what);
     if (plan.nranks > 1)
         throw std::logic_error(w + " on a sharded handle: it writes every target (use an unsharded handle)");
@@ -1632,22 +1675,30 @@ bool Operator::modeApplyCheck(const char* what, int id, int nrhs, const void* x,
 // One chunk on a high-order handle: applyBlockHigh's sequence with the mode kernels in
 // place of launch_near_hm and launch_ho_m2l, and the corrections of mode id (identity
 // fold; o.minuend: x - K_id(...)).  The expansions live in the block path's dHoMult / dHoLocal.
-void Operator::modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, hipStream_t s) {
+void Operator::modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, hipStream_t s, ApplyPrec prec) {
+    const bool f32 = prec == ApplyPrec::F32;
     ensureWork(K);
     hoReserve(K, s);
     const CorrFold& cf = corrTable(K, 1, &id, identityMix(K).data());
     StageSpans sp(*this, s);
     prepareCharges(K, in, dFT.as<double>(), dCT.as<double>(), s);
-    nearMode(K, id, o, s);
+    nearMode(K, id, o, s, prec);
     sp.end(4);
     corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
     sp.end(6);
     hoUpPass(K, dHoMult.as<double>(), false, s);
     sp.end(1);
     sp.startRoofline();
-    launch_ho_m2l_mode(np, K, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
-                       dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                       dNry.as<double>(), dHoTab.as<HoTables>(), dHoMult.as<double>(), dHoLocal.as<double>(), s);
+    if (f32)
+        launch_ho_m2l_mode_f32(np, K, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
+                               dAttSrc.as<int>(), dAttBlk.as<int>(), dAttM2LF.as<float>(), dNcx.as<double>(),
+                               dNcy.as<double>(), dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(),
+                               dHoMult.as<double>(), dHoLocal.as<double>(), s);
+    else
+        launch_ho_m2l_mode(np, K, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
+                           dAttSrc.as<int>(), dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(),
+                           dNcy.as<double>(), dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(),
+                           dHoMult.as<double>(), dHoLocal.as<double>(), s);
     sp.end(2);
     hoDownPass(K, dHoLocal.as<double>(), o, s);
     sp.end(5);
@@ -1688,10 +1739,11 @@ void Operator::modeApplyLean16(int id, int K, const InRows& in, const OutRows& o
 }
 
 void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, const double* sigT, bool minuend,
-                            double* out, int64_t ldo, hipStream_t s, bool keepCalls) {
-    if (!modeApplyCheck("mode apply", id, nrhs, x, ldx, out, ldo, minuend)) return;
+                            double* out, int64_t ldo, hipStream_t s, bool keepCalls, ApplyPrec prec) {
+    if (!modeApplyCheck("mode apply", id, nrhs, x, ldx, out, ldo, minuend, prec == ApplyPrec::F32)) return;
     checkDeviceErrors();
     ensureDevice();
+    if (prec == ApplyPrec::F32) cacheF32();  // (built on first use)
     if (!keepCalls) modeCalls.clear();
     const int64_t N = geo.N;
     // a lean mode of an np = 4 handle on the mode-shared caches (leanMapping's conditions;
@@ -1714,7 +1766,7 @@ void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, cons
             const InRows in{xc, ldc, false, sigT};
             const OutRows o = outRows(oc, ldoc, false, sub ? xc : nullptr, ldc);
             if (lean16) modeApplyLean16(id, K, in, o, s);
-            else modeApplyHigh(id, K, in, o, s);
+            else modeApplyHigh(id, K, in, o, s, prec);
             modeCalls.push_back(K);
         };
         for (int j0 = 0; j0 < nrhs; j0 += kMaxRhs) {

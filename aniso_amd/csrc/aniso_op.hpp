@@ -111,6 +111,9 @@ struct InRows {
     bool tree;
     const double* sigT;
 };
+// The precision of a mode apply's M2L and near field on a high-order handle (an argument of
+// modeApplyDev, not Operator state): F32 runs mode_apply_f32.hip on the float mirrors.
+enum class ApplyPrec { F64, F32 };
 struct OutRows {
     double* out;
     const double* minuend;
@@ -138,6 +141,12 @@ public:
     // device bytes of the operator caches: per-mode Km2l + Knear over all modes, the
     // mode-shared caches
     void cacheBytes(int64_t bytes[2]) const;
+    // float mirrors of the mode-shared caches' M2L blocks and directed near blocks (same
+    // indexing), read by the f32 mode applies of a high-order handle.  They
+    // live until setCoeff, a rebuild of the shared caches or the handle's end; the f32 applies
+    // build them on first use.  cacheF32Bytes: their device bytes, 0 when there are none.
+    void cacheF32();
+    int64_t cacheF32Bytes() const { return (int64_t)(dAttM2LF.bytes + dAttNearF.bytes); }
     void mappingHost(const double* charge, int id, double* out);
     void mappingBatchedHost(const double* Q, int k, int id, double* Out);  // N x k column-major
     // One mode on nrhs vectors wherever the mode is ready: rows of N
@@ -153,11 +162,13 @@ public:
     // symmetric U storage, ANISO_NEAR_HS_SYM, runs one leanMapping per column.)
     // modeApplyCheck raises everything that can be refused before the device is touched
     // (false: nrhs = 0, nothing to do).
+    // f32: the reduced-precision entries, refused on np = 4 and on sharded handles.
     bool modeApplyCheck(const char* what, int id, int nrhs, const void* x, int64_t ldx, const void* out, int64_t ldo,
-                        bool minuend) const;
+                        bool minuend, bool f32 = false) const;
     // keepCalls: append to modeApplyCalls() (a caller that cuts one call into several)
+    // prec = F32 (high-order handles): the M2L and the near field in fp32 on the float mirrors
     void modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, const double* sigT, bool minuend, double* out,
-                      int64_t ldo, hipStream_t s, bool keepCalls = false);
+                      int64_t ldo, hipStream_t s, bool keepCalls = false, ApplyPrec prec = ApplyPrec::F64);
     // the compiled column count K of every operator pass of the last modeApplyDev /
     // mappingMultiHost call, in order: a mode-kernel chunk (2, 4, 5 or 8), a resident
     // np = 4 mode's applyBlock chunk (1, 2, 4, 5 or 8), 8 for a per-column leanMapping pass
@@ -282,13 +293,36 @@ public:
     // maxhist) are host arrays.  Every unsharded handle whose mode 0 is ready.  Returns the
     // steps of all columns.  forwardSolveMultiCheck raises everything that can be refused
     // before the device is touched (false: nrhs = 0, nothing to do).
+    // (mixed: the mixed solve's innerTol and maxOuter, checked with the other parameters, and the
+    // f32 operator's refusals)
+    struct MixedParams {
+        double innerTol;
+        int maxOuter;
+        const int* outer;
+    };
     bool forwardSolveMultiCheck(const char* what, int nrhs, const void* q, int64_t ldq, const void* x, int64_t ldx,
-                                const int* iters, int restart, double tol, int maxit) const;
+                                const int* iters, int restart, double tol, int maxit,
+                                const MixedParams* mixed = nullptr) const;
     int forwardSolveMultiDev(int nrhs, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx,
                              int restart, double tol, int maxit, int* iters, double* relres, double* hist, int maxhist,
                              hipStream_t s);
     int forwardSolveMultiHost(const double* Q, int k, bool rhsIsSource, double* X, int restart, double tol, int maxit,
                               int* iters, double* relres);  // N x k column-major
+    // The same solve in mixed precision on a high-order handle: per group
+    // of 8 columns an fp64 refinement loop -- explicit fp64 residuals, converged at
+    // |r| <= tol |b| -- around colsSolveGroup over the f32 operator on the residuals scaled to
+    // unit norm (zero guess, innerTol, restart, maxit cycles).  A column stops when it has
+    // converged, at maxOuter refinements, or when a refinement does not reduce its fp64
+    // residual (the previous iterate is kept).  iters: a column's inner steps, negative if it
+    // did not converge; outer: its refinements; relres: its last explicit fp64 residual.
+    // Every buffer is allocated before the first launch (x untouched on failure).
+    int forwardSolveMultiMixedDev(int nrhs, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx,
+                                  int restart, double tol, double innerTol, int maxit, int maxOuter, int* iters,
+                                  int* outer, double* relres, hipStream_t s);
+    int forwardSolveMultiMixedHost(const double* Q, int k, bool rhsIsSource, double* X, int restart, double tol,
+                                   double innerTol, int maxit, int maxOuter, int* iters, int* outer, double* relres);
+    // every operator pass of the last mixed forward solve, in order: {precision (64 / 32), columns}
+    const std::vector<std::pair<int, int>>& forwardSolveMixedCalls() const { return mixedCalls; }
     // the column count of every operator call of the last forward solve, in order
     const std::vector<int>& forwardSolveCalls() const { return solveCalls; }
     // --- the block operator and its solve for several sources (aniso.m:121-173
@@ -521,7 +555,7 @@ private:
     }
     void prepareCharges(int K, const InRows& in, double* fT, double* cT, hipStream_t s);
     void nearUnstaged(int K, const HarmWeights& hw, const HarmWindow* win, int mask, const OutRows& o, hipStream_t s);
-    void nearMode(int K, int id, const OutRows& o, hipStream_t s);
+    void nearMode(int K, int id, const OutRows& o, hipStream_t s, ApplyPrec prec = ApplyPrec::F64);
     void corrections(int K, const CorrFold& cf, const double* fT, const double* cT, int64_t begin, int64_t end,
                      int mask, const OutRows& o, hipStream_t s);
     void hoReserve(int K, hipStream_t s);  // dHoMult / dHoLocal for K columns (grown, never shrunk), the locals zeroed
@@ -546,7 +580,7 @@ private:
     // (sigT: tree-order sigma_s multiplied into the charge by the pass's launch_prepare)
     void leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask, const double* sigT = nullptr);
     // modeApplyDev's chunk of K = 2, 4, 5 or 8 columns on a high-order handle
-    void modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, hipStream_t s);
+    void modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, hipStream_t s, ApplyPrec prec);
     // modeApplyDev's chunk of K = 2, 4, 5 or 8 columns on a lean mode of an np = 4 handle
     void modeApplyLean16(int id, int K, const InRows& in, const OutRows& o, hipStream_t s);
     // the modes of a batched apply are usable by it: tables for the harmonic launches,
@@ -581,6 +615,8 @@ private:
     void buildAttCache();
     bool useAtt = false, attReady = false;
     DevBuf dAttM2L, dAttNear, dSigDiag, dAttPtr, dAttSrc, dAttBlk, dAttOwner, dAttOther;
+    DevBuf dAttM2LF, dAttNearF;    // their float mirrors (cacheF32; none: empty)
+    void dropCacheF32();
     DevBuf dAttMax;                // max |E| of dAttM2L (the deterministic sums' bound)
     DevBuf dHmClBound, dNodeWmax;  // the deterministic sums: per cluster, per node
     DevBuf dHmClPtr, dHmTgt, dHmPtr, dHmSrc, dHmBlk, dHmSlot, dHmNDir;  // cluster plan
@@ -618,6 +654,7 @@ private:
     int gmresRestarted(const GmresSystem& g, StatusBlock& hs, double tol, int maxit, double* hist, int maxhist,
                        double* relres, hipStream_t s);
     std::vector<int> solveCalls;
+    std::vector<std::pair<int, int>> mixedCalls;  // forwardSolveMixedCalls()
     std::vector<int> modeCalls;  // modeApplyCalls()
     void arnoldiParts(int rows);  // dKryPart for sweeps of `rows` rows
     bool topTraceOn = false;

@@ -280,6 +280,74 @@ int aniso_forward_solve_multi(aniso_handle h, const double* Q, int k, int rhs_is
     });
 }
 
+int aniso_cache_f32(aniso_handle h) {
+    ENTER(h);
+    return guarded([&] { get(h).cacheF32(); });
+}
+
+int aniso_cache_f32_bytes(aniso_handle h, int64_t* bytes) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(bytes);
+        *bytes = get(h).cacheF32Bytes();
+    });
+}
+
+int aniso_mapping_multi_f32_dev(aniso_handle h, int id, int nrhs, const double* x, int64_t ldx, double* out,
+                                int64_t ldo, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        auto& op = get(h);
+        if (!op.modeApplyCheck("aniso_mapping_multi_f32_dev", id, nrhs, x, ldx, out, ldo, false, true)) return;
+        op.modeApplyDev(id, nrhs, x, ldx, nullptr, false, out, ldo, (hipStream_t)stream, false, aniso::ApplyPrec::F32);
+    });
+}
+
+int aniso_forward_multi_f32_dev(aniso_handle h, int nrhs, const double* x, int64_t ldx, double* out, int64_t ldo,
+                                void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        auto& op = get(h);
+        if (!op.modeApplyCheck("aniso_forward_multi_f32_dev", 0, nrhs, x, ldx, out, ldo, true, true)) return;
+        op.modeApplyDev(0, nrhs, x, ldx, op.sigmaSTree(), true, out, ldo, (hipStream_t)stream, false,
+                        aniso::ApplyPrec::F32);
+    });
+}
+
+int aniso_forward_solve_multi_mixed_dev(aniso_handle h, int nrhs, const double* q, int64_t ldq, int rhs_is_source,
+                                        double* x, int64_t ldx, int restart, double tol, double inner_tol, int maxit,
+                                        int max_outer, int* iters, int* outer, double* relres, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        get(h).forwardSolveMultiMixedDev(nrhs, q, ldq, rhs_is_source != 0, x, ldx, restart, tol, inner_tol, maxit,
+                                         max_outer, iters, outer, relres, (hipStream_t)stream);
+    });
+}
+
+int aniso_forward_solve_multi_mixed(aniso_handle h, const double* Q, int k, int rhs_is_source, double* X, int restart,
+                                    double tol, double inner_tol, int maxit, int max_outer, int* iters, int* outer,
+                                    double* relres) {
+    ENTER(h);
+    return guarded([&] {
+        get(h).forwardSolveMultiMixedHost(Q, k, rhs_is_source != 0, X, restart, tol, inner_tol, maxit, max_outer, iters,
+                                          outer, relres);
+    });
+}
+
+int aniso_forward_solve_mixed_calls(aniso_handle h, int* calls, int cap, int* n) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(n);
+        const auto& c = get(h).forwardSolveMixedCalls();
+        *n = (int)c.size();
+        if (calls)
+            for (int i = 0; i < cap && i < (int)c.size(); ++i) {
+                calls[2 * i] = c[i].first;
+                calls[2 * i + 1] = c[i].second;
+            }
+    });
+}
+
 int aniso_block_op_multi_dev(aniso_handle h, int which, int nsrc, const double* x, int64_t ldx, double* out,
                              int64_t ldo, void* stream) {
     ENTER(h);

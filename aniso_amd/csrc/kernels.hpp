@@ -435,6 +435,20 @@ void launch_near_mode(int K, int id, int nl, int maxLeaf, const int4* leafInfo, 
 void launch_ho_m2l_mode(int np, int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
                         const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
                         const double* nry, const HoTables* T, const double* mult, double* local, hipStream_t s);
+// The reduced-precision operator of a high-order handle (mode_apply_f32.hip, DESIGN.md
+// §3.18.5): both E arrays rounded to float with the same indexing (one launch), and
+// launch_near_mode / launch_ho_m2l_mode on the mirrors with the factor, the products and the
+// accumulators in fp32 (ncx / ncy: the near field takes its points relative to the target
+// leaf's centre).  Charges, multipoles, locals and `out` stay double.
+void launch_cache_f32(int64_t na, const double* a, float* af, int64_t nb, const double* b, float* bf, hipStream_t s);
+void launch_near_mode_f32(int K, int id, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
+                          const int* nearPts, const int64_t* nearKOff, const float* E, const double* ncx,
+                          const double* ncy, const double* pxT, const double* pyT, const double* sigDiag,
+                          const double* fT, const int* operm, int64_t obase, int64_t ldo, double scale, double* out,
+                          hipStream_t s);
+void launch_ho_m2l_mode_f32(int np, int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
+                            const int* blk, const float* E, const double* ncx, const double* ncy, const double* nrx,
+                            const double* nry, const HoTables* T, const double* mult, double* local, hipStream_t s);
 // launch_m2l_hm for mode id on a rank-16 (np = 4) handle: mult [node][16][K] as the up tiers
 // leave it, local = the plain sums of every listed target (the down tiers read them as they
 // are); ntgt = 0 launches nothing.  A column's bits do not depend on K or on its slot.

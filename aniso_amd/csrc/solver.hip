@@ -1192,22 +1192,29 @@ static void checkColsSolveParams(const std::string& w, int restart, double tol, 
 
 // everything that can be refused before the device is touched (false: nothing to do)
 bool Operator::forwardSolveMultiCheck(const char* what, int nrhs, const void* q, int64_t ldq, const void* x,
-                                      int64_t ldx, const int* iters, int restart, double tol, int maxit) const {
+                                      int64_t ldx, const int* iters, int restart, double tol, int maxit,
+                                      const MixedParams* mixed) const {
     const std::string w(what);
     const int64_t N = geo.N;
     if (nrhs < 0) throw std::invalid_argument(w + ": nrhs must be >= 0, got " + std::to_string(nrhs));
     if (ldq < N) throw std::invalid_argument(w + ": ldq = " + std::to_string(ldq) + " is below N = " + std::to_string(N));
     if (ldx < N) throw std::invalid_argument(w + ": ldx = " + std::to_string(ldx) + " is below N = " + std::to_string(N));
     checkColsSolveParams(w, restart, tol, maxit);
+    if (mixed && !(mixed->innerTol > 0.0 && mixed->innerTol < 1.0))
+        throw std::invalid_argument(w + ": inner_tol must be in (0, 1)");
+    if (mixed && mixed->maxOuter < 1)
+        throw std::invalid_argument(w + ": max_outer must be >= 1, got " + std::to_string(mixed->maxOuter));
     if (nrhs > 0 && !q) throw std::invalid_argument(w + ": q is NULL");
     if (nrhs > 0 && !x) throw std::invalid_argument(w + ": x is NULL");
     if (nrhs > 0 && !iters) throw std::invalid_argument(w + ": iters is NULL");
+    if (nrhs > 0 && mixed && !mixed->outer) throw std::invalid_argument(w + ": outer is NULL");
     if (nrhs == 0) return false;
     const char* qb = static_cast<const char*>(q);
     const char* xb = static_cast<const char*>(x);
     const size_t qs = ((size_t)(nrhs - 1) * ldq + N) * sizeof(double), xs = ((size_t)(nrhs - 1) * ldx + N) * sizeof(double);
     if (qb < xb + xs && xb < qb + qs) throw std::invalid_argument(w + ": q and x overlap");
-    return modeApplyCheck(what, 0, nrhs, q, ldq, x, ldx, false);  // the handle's state, as aniso_forward_multi_dev
+    // the handle's state, as aniso_forward_multi_dev (mixed: as aniso_forward_multi_f32_dev)
+    return modeApplyCheck(what, 0, nrhs, q, ldq, x, ldx, false, mixed != nullptr);
 }
 
 int Operator::forwardSolveMultiDev(int nrhs, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx,
@@ -1479,6 +1486,201 @@ int Operator::forwardSolveMultiHost(const double* Q, int k, bool rhsIsSource, do
     HIP_CHECK(hipMemcpyAsync(dx.p, X, bytes, hipMemcpyHostToDevice, own));
     const int steps = forwardSolveMultiDev(k, dq.as<double>(), geo.N, rhsIsSource, dx.as<double>(), geo.N, restart, tol,
                                            maxit, iters, relres, nullptr, 0, own);
+    HIP_CHECK(hipMemcpyAsync(X, dx.p, bytes, hipMemcpyDeviceToHost, own));
+    HIP_CHECK(hipStreamSynchronize(own));
+    return steps;
+}
+
+// ---- the multi-source forward solve in mixed precision: high-order
+// handles.  Per group of arn::kMaxCols columns an fp64 refinement loop around colsSolveGroup
+// over the f32 operator: the Krylov vectors stay double, only the operator is inexact.
+//   r = b - A x (fp64; a zero guess costs no pass); until every column is done:
+//     a column is converged at |r| <= tol |b| (what confirms a column of the fp64 solve);
+//     d from A~ d = r / |r| (zero guess, innerTol, restart, maxit cycles; an inner solve
+//     that stops short still contributes its d); x += |r| d; one fp64 pass over exactly the
+//     active columns for the new residuals.
+// A column stops when it has converged, at maxOuter, or when a refinement does not reduce
+// its fp64 residual (the previous iterate is put back).
+int Operator::forwardSolveMultiMixedDev(int nrhs, const double* q, int64_t ldq, bool rhsIsSource, double* x,
+                                        int64_t ldx, int restart, double tol, double innerTol, int maxit,
+                                        int maxOuter, int* iters, int* outer, double* relres, hipStream_t s) {
+    const MixedParams mp{innerTol, maxOuter, outer};
+    if (!forwardSolveMultiCheck("aniso_forward_solve_multi_mixed_dev", nrhs, q, ldq, x, ldx, iters, restart, tol, maxit,
+                                &mp))
+        return 0;
+    ensureDevice();
+    checkDeviceErrors();
+    constexpr int G = arn::kMaxCols;
+    const int64_t N = geo.N;
+    const int m = restart, gmax = std::min(nrhs, G);
+    const std::string g = std::to_string(gmax);
+    const size_t row = (size_t)gmax * N * sizeof(double);
+    const unsigned nbp = std::min(nblk(N), 1024u);  // partial sums per norm
+    ColsWork cw;
+    DevBuf Bt, R, D, Xp, dPart, dNrm;  // the true right-hand sides, residuals, corrections, previous iterates
+    cw.alloc(N, gmax, m, false,
+             "mixed forward solve: the Krylov bases of (restart + 1) x " + g + " x N = " + std::to_string(m + 1) +
+                 " x " + g + " x " + std::to_string(N),
+             ("work buffers and 4 x " + std::to_string(row) + " bytes of refinement vectors").c_str(), [&] {
+                 Bt.alloc(row);
+                 R.alloc(row);
+                 D.alloc(row);
+                 Xp.alloc(row);
+                 dPart.alloc((size_t)nbp * sizeof(double));
+                 dNrm.alloc(G * sizeof(double));
+             });
+    cacheF32();  // the float mirrors, if this is their first use: before anything is launched
+    arn_small_kernel_attrs();
+    solveCalls.clear();
+    mixedCalls.clear();
+    const double* sigS = sigmaSTree();
+    double *bt = Bt.as<double>(), *r = R.as<double>(), *d = D.as<double>(), *xp = Xp.as<double>();
+    double *W = cw.W.as<double>(), *In = cw.In.as<double>(), *Bn = cw.B.as<double>(), *nrm = dNrm.as<double>();
+    const size_t rb = (size_t)N * sizeof(double);
+    const ColsSolve cs{N, "mixed forward solve", [&](int nrows, const double* in, double* w) {
+                           modeApplyDev(0, nrows, in, N, sigS, true, w, N, s, false, ApplyPrec::F32);
+                           mixedCalls.push_back({32, nrows});
+                       }};
+    // |v_a|^2 of n vectors (fixed-order sums) to the host
+    double hn[G];
+    auto norms2 = [&](int n, auto&& vec) {
+        for (int a = 0; a < n; ++a) {
+            const double* v = vec(a);
+            k_dot_partial<<<nbp, 256, 0, s>>>(N, v, v, dPart.as<double>());
+            k_dot_final<<<1, 256, 0, s>>>((int)nbp, dPart.as<double>(), nrm + a);
+        }
+        HIP_LAUNCH_CHECK();
+        HIP_CHECK(hipMemcpyAsync(hn, nrm, n * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    };
+    // W[a] = A x[cols[a]] in fp64: one pass over exactly these columns
+    auto pass64 = [&](const std::vector<int>& cols, double* xg, int64_t ld) {
+        for (size_t a = 0; a < cols.size(); ++a)
+            HIP_CHECK(hipMemcpyAsync(In + a * N, xg + (size_t)cols[a] * ld, rb, hipMemcpyDeviceToDevice, s));
+        modeApplyDev(0, (int)cols.size(), In, N, sigS, true, W, N, s);
+        mixedCalls.push_back({64, (int)cols.size()});
+    };
+    int steps = 0;
+    try {
+        for (int r0 = 0; r0 < nrhs; r0 += G) {
+            const int ng = std::min(G, nrhs - r0);
+            const double* qg = q + (size_t)r0 * ldq;
+            double* xg = x + (size_t)r0 * ldx;
+            if (rhsIsSource) {
+                modeApplyDev(0, ng, qg, ldq, nullptr, false, bt, N, s);
+                mixedCalls.push_back({64, ng});
+            } else {
+                HIP_CHECK(hipMemcpy2DAsync(bt, rb, qg, ldq * sizeof(double), rb, ng, hipMemcpyDeviceToDevice, s));
+            }
+            struct Col {
+                int total = 0, outer = 0;
+                bool done = false, conv = false;
+                double normb = 0.0, rel = 0.0, nr = 0.0;
+            } col[G];
+            norms2(ng, [&](int c) { return bt + (size_t)c * N; });
+            for (int c = 0; c < ng; ++c) col[c].normb = std::sqrt(hn[c]);
+            norms2(ng, [&](int c) { return xg + (size_t)c * ldx; });
+            std::vector<int> act, first;
+            for (int c = 0; c < ng; ++c) {
+                if (!(col[c].normb > 0.0)) {  // b = 0: x = 0
+                    HIP_CHECK(hipMemsetAsync(xg + (size_t)c * ldx, 0, rb, s));
+                    col[c].done = col[c].conv = true;
+                    continue;
+                }
+                act.push_back(c);
+                if (hn[c] != 0.0) first.push_back(c);  // A 0 = 0: a zero guess costs no pass
+                else HIP_CHECK(hipMemcpyAsync(r + (size_t)c * N, bt + (size_t)c * N, rb, hipMemcpyDeviceToDevice, s));
+            }
+            if (!first.empty()) {
+                pass64(first, xg, ldx);
+                for (size_t a = 0; a < first.size(); ++a)
+                    k_sub<<<nblk(N), 256, 0, s>>>(N, bt + (size_t)first[a] * N, W + a * N, r + (size_t)first[a] * N);
+                HIP_LAUNCH_CHECK();
+            }
+            norms2((int)act.size(), [&](int a) { return r + (size_t)act[a] * N; });
+            for (size_t a = 0; a < act.size(); ++a) {
+                Col& k = col[act[a]];
+                k.nr = std::sqrt(hn[a]);
+                k.rel = k.nr / k.normb;
+            }
+            for (;;) {
+                act.clear();
+                for (int c = 0; c < ng; ++c) {
+                    Col& k = col[c];
+                    if (k.done) continue;
+                    k.conv = k.rel <= tol;
+                    if (k.conv || k.outer >= maxOuter) k.done = true;
+                    else act.push_back(c);
+                }
+                if (act.empty()) break;
+                const int na = (int)act.size();
+                // the residuals at unit norm: the fp32 staging never sees their scale
+                for (int a = 0; a < na; ++a)
+                    k_scale<<<nblk(N), 256, 0, s>>>(N, 1.0 / col[act[a]].nr, r + (size_t)act[a] * N, Bn + (size_t)a * N);
+                HIP_LAUNCH_CHECK();
+                HIP_CHECK(hipMemsetAsync(d, 0, (size_t)na * rb, s));
+                int it[G];
+                colsSolveGroup(cs, cw, na, d, N, m, innerTol, maxit, it, nullptr, nullptr, 0, s);
+                for (int a = 0; a < na; ++a) {
+                    const int c = act[a];
+                    col[c].total += maxit == 0 ? 0 : std::abs(it[a]);
+                    ++col[c].outer;
+                    HIP_CHECK(hipMemcpyAsync(xp + (size_t)c * N, xg + (size_t)c * ldx, rb, hipMemcpyDeviceToDevice, s));
+                    k_axpby<<<nblk(N), 256, 0, s>>>(N, col[c].nr, d + (size_t)a * N, 1.0, xg + (size_t)c * ldx);
+                }
+                HIP_LAUNCH_CHECK();
+                pass64(act, xg, ldx);
+                for (int a = 0; a < na; ++a)
+                    k_sub<<<nblk(N), 256, 0, s>>>(N, bt + (size_t)act[a] * N, W + (size_t)a * N, d + (size_t)a * N);
+                HIP_LAUNCH_CHECK();
+                norms2(na, [&](int a) { return d + (size_t)a * N; });  // (the corrections are spent: d holds b - A x)
+                for (int a = 0; a < na; ++a) {
+                    const int c = act[a];
+                    Col& k = col[c];
+                    const double nr = std::sqrt(hn[a]);
+                    if (nr < k.nr) {
+                        k.nr = nr;
+                        k.rel = nr / k.normb;
+                        HIP_CHECK(hipMemcpyAsync(r + (size_t)c * N, d + (size_t)a * N, rb, hipMemcpyDeviceToDevice, s));
+                    } else {  // no reduction: the previous iterate is kept and the column stops
+                        HIP_CHECK(hipMemcpyAsync(xg + (size_t)c * ldx, xp + (size_t)c * N, rb, hipMemcpyDeviceToDevice, s));
+                        k.done = true;
+                    }
+                }
+            }
+            HIP_CHECK(hipStreamSynchronize(s));
+            checkDeviceErrors();
+            for (int c = 0; c < ng; ++c) {
+                const Col& k = col[c];
+                iters[r0 + c] = k.conv ? k.total : -std::max(k.total, 1);
+                outer[r0 + c] = k.outer;
+                if (relres) relres[r0 + c] = k.rel;
+                steps += k.total;
+            }
+        }
+    } catch (...) {
+        (void)hipStreamSynchronize(s);  // no kernel still writes the buffers freed here
+        throw;
+    }
+    return steps;
+}
+
+// N x k column-major host arrays: one staging copy each way
+int Operator::forwardSolveMultiMixedHost(const double* Q, int k, bool rhsIsSource, double* X, int restart, double tol,
+                                         double innerTol, int maxit, int maxOuter, int* iters, int* outer,
+                                         double* relres) {
+    const MixedParams mp{innerTol, maxOuter, outer};
+    if (!forwardSolveMultiCheck("aniso_forward_solve_multi_mixed", k, Q, geo.N, X, geo.N, iters, restart, tol, maxit, &mp))
+        return 0;
+    ensureDevice();
+    const size_t bytes = (size_t)k * geo.N * sizeof(double);
+    DevBuf dq, dx;
+    dq.alloc(bytes);
+    dx.alloc(bytes);
+    HIP_CHECK(hipMemcpyAsync(dq.p, Q, bytes, hipMemcpyHostToDevice, own));
+    HIP_CHECK(hipMemcpyAsync(dx.p, X, bytes, hipMemcpyHostToDevice, own));
+    const int steps = forwardSolveMultiMixedDev(k, dq.as<double>(), geo.N, rhsIsSource, dx.as<double>(), geo.N, restart,
+                                                tol, innerTol, maxit, maxOuter, iters, outer, relres, own);
     HIP_CHECK(hipMemcpyAsync(X, dx.p, bytes, hipMemcpyDeviceToHost, own));
     HIP_CHECK(hipStreamSynchronize(own));
     return steps;

@@ -161,6 +161,12 @@ int aniso_forward_solve_calls(aniso_handle h, int *counts, int cap, int *n);
  * kernels do not serve (ANISO_NEAR_HS_SYM=1) reports 8, the offset form's rows, once per
  * column.  Host only. */
 int aniso_mode_apply_calls(aniso_handle h, int *counts, int cap, int *n);
+/* ---- the mixed-precision forward solve ---- */
+/* every operator pass of the handle's last aniso_forward_solve_multi_mixed(_dev) call, in
+ * order: *n = their number, calls (cap >= 0 pairs, may be NULL) = {precision, columns} of
+ * each, precision 64 (the right-hand sides, the first residual, one residual pass per
+ * refinement over the columns still active) or 32 (the inner solves' passes).  Host only. */
+int aniso_forward_solve_mixed_calls(aniso_handle h, int *calls, int cap, int *n);
 
 #ifdef __cplusplus
 }
