@@ -85,6 +85,9 @@ def lib():
             "aniso_block_op_multi": [P, I, dp, I, dp],
             "aniso_block_solve_multi_dev": [P, I, P, I64, I, P, I64, I, D, I, ip, dp, dp, I, P],
             "aniso_block_solve_multi": [P, dp, I, I, dp, I, D, I, ip, dp],
+            "aniso_cache_mode": [P, I],
+            "aniso_cache_mode_bytes": [P, lp],
+            "aniso_cache_mode_free": [P, I],
             "aniso_cache_f32": [P],
             "aniso_cache_f32_bytes": [P, lp],
             "aniso_mapping_multi_f32_dev": [P, I, I, P, I64, P, I64, P],
@@ -450,6 +453,24 @@ class Aniso:
                                                float(tol), int(maxit),
                                                iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(relres)))
         return X, iters, relres
+
+    # ---- resident mode operators of a high-order handle (np = 6, 8)
+    def cache_mode(self, id_):
+        """Mode id_'s resident factor blocks (aniso_cache_mode): as large as the handle's E
+        blocks, built in one launch.  While they are resident, mapping_multi(_dev),
+        forward_multi_dev and forward_solve_multi(_dev) on that mode run the fp64 MFMA M2L on
+        them, up to 16 columns per chunk.  A second call for a resident mode does nothing."""
+        _check(lib().aniso_cache_mode(self.address, int(id_)))
+
+    def cache_mode_bytes(self):
+        """Device bytes of the resident mode blocks over all modes, 0 when there are none."""
+        b = ctypes.c_int64()
+        _check(lib().aniso_cache_mode_bytes(self.address, ctypes.byref(b)))
+        return int(b.value)
+
+    def cache_mode_free(self, id_=-1):
+        """Drop mode id_'s resident blocks; -1: every mode's."""
+        _check(lib().aniso_cache_mode_free(self.address, int(id_)))
 
     # ---- the reduced-precision route of a high-order handle (np = 6, 8)
     def cache_f32(self):

@@ -450,6 +450,7 @@ void Operator::uploadPlan() {
         HIP_CHECK(hipMemset(dTopSteals.p, 0, sizeof(unsigned)));
         attReady = false;
         dropCacheF32();
+        modeBlocks.clear();
     }
     up(dM2LCanonBase, plan.m2lCanonBase);
     up(dM2LInPtr, plan.m2lInPtr);
@@ -557,6 +558,7 @@ void Operator::setCoeff(const double* ss, const double* st) {
     for (auto& m : modes) m.tables = m.resident = false;
     attReady = false;
     dropCacheF32();    // the float mirrors are rounded from the shared caches of sigma_t
+    modeBlocks.clear();  // ... and the resident mode blocks are formed from them
     f32Ready = false;  // config 5's fp32 caches are rounded from the mode-0 operators of sigma_t
     m64.clear();       // ... and the fp64 16-RHS caches are the modes' operators
     coeffSet = true;
@@ -680,6 +682,59 @@ void Operator::cacheF32() {
     HIP_CHECK(hipStreamSynchronize(own));
 }
 
+// One mode's resident factor blocks: as many bytes as the E blocks, one
+// launch.  Everything that can be refused is refused before the device is touched.
+void Operator::cacheMode(int id) {
+    if (id < 0 || id >= kernelSize)
+        throw std::out_of_range("aniso_cache_mode: kernel id " + std::to_string(id) + " out of range [0, " +
+                                std::to_string(kernelSize) + ")");
+    if (!highOrder())
+        throw std::logic_error("aniso_cache_mode: the resident mode blocks are built for np = 6, 8; the resident route "
+                               "of an np = 4 handle is aniso_cache(h, id)");
+    refuseHoShard("aniso_cache_mode");
+    if (plan.nranks > 1) throw std::logic_error("aniso_cache_mode on a sharded handle (use an unsharded handle)");
+    if (!coeffSet || !attReady || !modes[id].tables)
+        throw std::runtime_error("aniso_cache_mode before aniso_set_coeff and aniso_cache(" + std::to_string(id) +
+                                 ") or aniso_cache_block");
+    if (modeBlocks.count(id)) return;
+    ensureDevice();
+    const size_t need = dAttM2L.bytes;
+    size_t freeB = 0, totalB = 0;
+    HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+    const std::string sizes = std::to_string(need) + " bytes for mode " + std::to_string(id) + ", " +
+                              std::to_string(freeB) + " bytes of HBM free";
+    if (need + (size_t)(1ull << 30) > freeB)  // keep a GiB of headroom
+        throw std::runtime_error("aniso_cache_mode: the resident blocks do not fit with a GiB to spare: " + sizes);
+    DevBuf F;
+    try {
+        F.alloc(need);
+    } catch (const std::exception& e) {
+        throw std::runtime_error("aniso_cache_mode: the resident blocks could not be allocated: " + sizes + ": " + e.what());
+    }
+    const size_t rank = (size_t)np * np;
+    launch_ho_mode_blocks(np, id, (int64_t)(need / (rank * rank * sizeof(double))), dAttOwner.as<int>(),
+                          dAttOther.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(),
+                          dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(), F.as<double>(), own);
+    HIP_CHECK(hipStreamSynchronize(own));
+    modeBlocks.emplace(id, std::move(F));
+}
+
+void Operator::cacheModeFree(int id) {
+    if (id < -1 || id >= kernelSize)
+        throw std::out_of_range("aniso_cache_mode_free: kernel id " + std::to_string(id) + " out of range [-1, " +
+                                std::to_string(kernelSize) + ")");
+    if (modeBlocks.empty() || (id >= 0 && !modeBlocks.count(id))) return;
+    HIP_CHECK(hipDeviceSynchronize());  // queued applies (on the caller's streams too) may still read them
+    if (id < 0) modeBlocks.clear();
+    else modeBlocks.erase(id);
+}
+
+int64_t Operator::cacheModeBytes() const {
+    int64_t b = 0;
+    for (const auto& m : modeBlocks) b += (int64_t)m.second.bytes;
+    return b;
+}
+
 void Operator::refuseHighOrder(const char* what) const {
     if (highOrder())
         throw std::logic_error(std::string(what) + ": a high-order handle (np = " + std::to_string(np) +
@@ -700,6 +755,7 @@ void Operator::needResident(int id, const char* what) const {
 // every point (the mode-0 diagonal).  Built once per setCoeff on a block handle.
 void Operator::buildAttCache() {
     dropCacheF32();
+    modeBlocks.clear();
     const Params* P = dParams.as<Params>();
     const int64_t npairs = (int64_t)(plan.attOwner.size() + plan.hmCopyOwner.size());  // stored blocks + copies
     const size_t rank = (size_t)np * np;
@@ -1109,15 +1165,18 @@ void Operator::corrections(int K, const CorrFold& cf, const double* fT, const do
                 dParams.as<Params>(), mask, kScale, o.tree, o.ld, o.out, s);
 }
 
-void Operator::hoReserve(int K, hipStream_t s) {
-    if (K > hoWorkK) {
-        dHoMult.alloc(hoDoubles(K) * sizeof(double));
-        dHoLocal.alloc(hoDoubles(K) * sizeof(double));
-        hoWorkK = K;
+void Operator::hoReserve(int K, hipStream_t s, bool second) {
+    DevBuf& mult = second ? dHoMult2 : dHoMult;
+    DevBuf& local = second ? dHoLocal2 : dHoLocal;
+    int& have = second ? hoWorkK2 : hoWorkK;
+    if (K > have) {
+        mult.alloc(hoDoubles(K) * sizeof(double));
+        local.alloc(hoDoubles(K) * sizeof(double));
+        have = K;
     }
     // nodes that are no M2L target (the root, empty nodes) keep zero locals; a smaller K
     // re-uses the buffers with its own strides
-    HIP_CHECK(hipMemsetAsync(dHoLocal.p, 0, hoDoubles(K) * sizeof(double), s));
+    HIP_CHECK(hipMemsetAsync(local.p, 0, hoDoubles(K) * sizeof(double), s));
 }
 
 void Operator::hoUpPass(int K, double* mult, bool allLeaves, hipStream_t s) {
@@ -1677,6 +1736,7 @@ bool Operator::modeApplyCheck(const char* what, int id, int nrhs, const void* x,
 // fold; o.minuend: x - K_id(...)).  The expansions live in the block path's dHoMult / dHoLocal.
 void Operator::modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, hipStream_t s, ApplyPrec prec) {
     const bool f32 = prec == ApplyPrec::F32;
+    const double* F = f32 ? nullptr : modeResident(id);  // (the f32 entries ignore the resident blocks)
     ensureWork(K);
     hoReserve(K, s);
     const CorrFold& cf = corrTable(K, 1, &id, identityMix(K).data());
@@ -1694,6 +1754,10 @@ void Operator::modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, 
                                dAttSrc.as<int>(), dAttBlk.as<int>(), dAttM2LF.as<float>(), dNcx.as<double>(),
                                dNcy.as<double>(), dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(),
                                dHoMult.as<double>(), dHoLocal.as<double>(), s);
+    else if (F)
+        launch_ho_m2l_resident(np, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
+                               dAttSrc.as<int>(), dAttBlk.as<int>(), F, dHoMult.as<double>(), K, nullptr, 0,
+                               dHoLocal.as<double>(), nullptr, s);
     else
         launch_ho_m2l_mode(np, K, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
                            dAttSrc.as<int>(), dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(),
@@ -1701,6 +1765,42 @@ void Operator::modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, 
                            dHoMult.as<double>(), dHoLocal.as<double>(), s);
     sp.end(2);
     hoDownPass(K, dHoLocal.as<double>(), o, s);
+    sp.end(5);
+    sp.total();
+}
+
+// A chunk of 9 .. 16 columns on a resident mode: each half runs modeApplyHigh's launches on
+// expansion buffers of its own (the charges dFT / dCT are re-used: the second half's are
+// formed after the first half's up pass has read them), around one M2L for all 16 columns.
+void Operator::modeApplyHigh16(int id, int K2, const InRows& inA, const OutRows& oA, const InRows& inB,
+                               const OutRows& oB, hipStream_t s) {
+    const double* F = modeResident(id);
+    if (!F) throw std::logic_error("a 16-column mode chunk without resident blocks");
+    const int KA = kMaxRhs;
+    ensureWork(KA);
+    hoReserve(KA, s);
+    hoReserve(K2, s, true);
+    StageSpans sp(*this, s);
+    for (int half = 0; half < 2; ++half) {
+        const int K = half ? K2 : KA;
+        const InRows& in = half ? inB : inA;
+        const OutRows& o = half ? oB : oA;
+        const CorrFold& cf = corrTable(K, 1, &id, identityMix(K).data());
+        prepareCharges(K, in, dFT.as<double>(), dCT.as<double>(), s);
+        nearMode(K, id, o, s);
+        sp.end(4);
+        corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
+        sp.end(6);
+        hoUpPass(K, (half ? dHoMult2 : dHoMult).as<double>(), false, s);
+        sp.end(1);
+    }
+    sp.startRoofline();
+    launch_ho_m2l_resident(np, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
+                           dAttSrc.as<int>(), dAttBlk.as<int>(), F, dHoMult.as<double>(), KA, dHoMult2.as<double>(), K2,
+                           dHoLocal.as<double>(), dHoLocal2.as<double>(), s);
+    sp.end(2);
+    hoDownPass(KA, dHoLocal.as<double>(), oA, s);
+    hoDownPass(K2, dHoLocal2.as<double>(), oB, s);
     sp.end(5);
     sp.total();
 }
@@ -1769,11 +1869,39 @@ void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, cons
             else modeApplyHigh(id, K, in, o, s, prec);
             modeCalls.push_back(K);
         };
-        for (int j0 = 0; j0 < nrhs; j0 += kMaxRhs) {
+        // a resident high-order mode: more than 8 remaining columns form one chunk of up to 16
+        const bool wide = highOrder() && prec == ApplyPrec::F64 && modeResident(id);
+        for (int j0 = 0; j0 < nrhs;) {
+            if (wide && nrhs - j0 > kMaxRhs) {
+                const int nb2 = std::min(kMaxRhs, nrhs - j0 - kMaxRhs);
+                const int K2 = nb2 == 1 ? 2 : rhs_padded(nb2);
+                const double* xa = x + (size_t)j0 * ldx;
+                double* oa = dst + (size_t)j0 * ldd;
+                const double* xb = xa + (size_t)kMaxRhs * ldx;
+                double* ob = oa + (size_t)kMaxRhs * ldd;
+                const InRows inA{xa, ldx, false, sigT};
+                const OutRows oA = outRows(oa, ldd, false, sub ? xa : nullptr, ldx);
+                if (K2 == nb2) {
+                    modeApplyHigh16(id, K2, inA, oA, InRows{xb, ldx, false, sigT},
+                                    outRows(ob, ldd, false, sub ? xb : nullptr, ldx), s);
+                } else {
+                    const size_t pb = (size_t)K2 * N * sizeof(double);
+                    if (dPadIn.bytes < pb) dPadIn.alloc(pb);
+                    if (dPadOut.bytes < pb) dPadOut.alloc(pb);
+                    padRowsIn(dPadIn, 1, nb2, K2, xb, ldx, s);
+                    modeApplyHigh16(id, K2, inA, oA, InRows{dPadIn.as<double>(), N, false, sigT},
+                                    outRows(dPadOut.as<double>(), N, false, sub ? dPadIn.as<double>() : nullptr, N), s);
+                    padRowsOut(dPadOut.as<double>(), nb2, N, ob, ldd, s);
+                }
+                modeCalls.push_back(2 * kMaxRhs);
+                j0 += kMaxRhs + nb2;
+                continue;
+            }
             const int nb = std::min(kMaxRhs, nrhs - j0);
             const int K = nb == 1 ? 2 : rhs_padded(nb);  // (the mode kernels start at 2 columns)
             const double* xc = x + (size_t)j0 * ldx;
             double* oc = dst + (size_t)j0 * ldd;
+            j0 += nb;
             if (K == nb) {
                 chunk(K, xc, ldx, oc, ldd);
                 continue;
@@ -1821,7 +1949,7 @@ void Operator::mappingMultiHost(const double* Q, int k, int id, double* Out) {
     if (!modeApplyCheck("aniso_mapping_multi", id, k, Q, geo.N, Out, geo.N, false)) return;
     ensureDevice();
     const int64_t N = geo.N;
-    const int kb = std::min(k, kMaxRhs);
+    const int kb = std::min(k, highOrder() && modeResident(id) ? 2 * kMaxRhs : kMaxRhs);  // (a resident mode's chunk)
     DevBuf dq, dout;
     dq.alloc((size_t)kb * N * sizeof(double));
     dout.alloc((size_t)kb * N * sizeof(double));

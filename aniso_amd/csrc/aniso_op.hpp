@@ -147,6 +147,15 @@ public:
     // build them on first use.  cacheF32Bytes: their device bytes, 0 when there are none.
     void cacheF32();
     int64_t cacheF32Bytes() const { return (int64_t)(dAttM2LF.bytes + dAttNearF.bytes); }
+    // one mode's resident factor blocks on a high-order handle (np = 6, 8; mode_resident.hip,
+    // DESIGN.md §3.18.6): F_id = (E / r) T_id(c) of every stored pair, indexed as the E blocks
+    // and as large as they are, built in one launch.  While mode id is resident the fp64 mode
+    // applies run the MFMA M2L on them, up to 16 columns per chunk.  Several modes may be
+    // resident; they live until cacheModeFree (id = -1: all), setCoeff, a rebuild of the shared
+    // caches or the handle's end.  cacheModeBytes: their device bytes over all modes.
+    void cacheMode(int id);
+    void cacheModeFree(int id);
+    int64_t cacheModeBytes() const;
     void mappingHost(const double* charge, int id, double* out);
     void mappingBatchedHost(const double* Q, int k, int id, double* Out);  // N x k column-major
     // One mode on nrhs vectors wherever the mode is ready: rows of N
@@ -155,7 +164,9 @@ public:
     //     out[k] = x[k] - K_id (sigT .* x[k])   (minuend; x and out must not overlap)
     // A high-order handle runs chunks of 8 columns (a remainder zero-padded to 2, 4 or 8)
     // through the mode kernels of mode_apply.hip on the mode-shared caches: the entry's
-    // factor is formed once per chunk.  np = 4: a resident mode runs applyBlock's identity
+    // factor is formed once per chunk.  A mode made resident by cacheMode (fp64 only) runs
+    // the MFMA M2L of mode_resident.hip in their place; more than 8 remaining columns then
+    // form one chunk of up to 16, two halves of the 8-column launches around one M2L.  np = 4: a resident mode runs applyBlock's identity
     // mix in chunks of 8; a lean mode runs the same chunks through modeApplyLean16 (the
     // near-field mode kernel and the rank-16 mode M2L between the up and down tiers), one
     // read of the shared caches per chunk.  (A handle whose harmonic near field keeps
@@ -170,7 +181,8 @@ public:
     void modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, const double* sigT, bool minuend, double* out,
                       int64_t ldo, hipStream_t s, bool keepCalls = false, ApplyPrec prec = ApplyPrec::F64);
     // the compiled column count K of every operator pass of the last modeApplyDev /
-    // mappingMultiHost call, in order: a mode-kernel chunk (2, 4, 5 or 8), a resident
+    // mappingMultiHost call, in order: a mode-kernel chunk (2, 4, 5 or 8), 16 for a resident
+    // high-order mode's chunk of more than 8 columns, a resident
     // np = 4 mode's applyBlock chunk (1, 2, 4, 5 or 8), 8 for a per-column leanMapping pass
     const std::vector<int>& modeApplyCalls() const { return modeCalls; }
     void mappingMultiHost(const double* Q, int k, int id, double* Out);  // N x k column-major
@@ -558,7 +570,9 @@ private:
     void nearMode(int K, int id, const OutRows& o, hipStream_t s, ApplyPrec prec = ApplyPrec::F64);
     void corrections(int K, const CorrFold& cf, const double* fT, const double* cT, int64_t begin, int64_t end,
                      int mask, const OutRows& o, hipStream_t s);
-    void hoReserve(int K, hipStream_t s);  // dHoMult / dHoLocal for K columns (grown, never shrunk), the locals zeroed
+    // dHoMult / dHoLocal for K columns (grown, never shrunk), the locals zeroed; second: the
+    // expansions of a 16-column chunk's second half (dHoMult2 / dHoLocal2)
+    void hoReserve(int K, hipStream_t s, bool second = false);
     size_t hoDoubles(int K) const { return (size_t)tree.nn * np * np * K; }  // one expansion buffer
     void hoUpPass(int K, double* mult, bool allLeaves, hipStream_t s);  // allLeaves: a shard's replicated P2M
     void hoDownPass(int K, double* local, const OutRows& o, hipStream_t s);
@@ -581,6 +595,17 @@ private:
     void leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask, const double* sigT = nullptr);
     // modeApplyDev's chunk of K = 2, 4, 5 or 8 columns on a high-order handle
     void modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, hipStream_t s, ApplyPrec prec);
+    // its chunk of more than 8 columns on a resident mode: the launches of an 8-column half
+    // and of a K2-column half (K2 = 2, 4, 5 or 8) around one resident M2L for all of them
+    void modeApplyHigh16(int id, int K2, const InRows& inA, const OutRows& oA, const InRows& inB, const OutRows& oB,
+                         hipStream_t s);
+    std::map<int, DevBuf> modeBlocks;  // cacheMode: resident factor blocks per mode id
+    const double* modeResident(int id) const {
+        const auto it = modeBlocks.find(id);
+        return it == modeBlocks.end() ? nullptr : it->second.as<double>();
+    }
+    DevBuf dHoMult2, dHoLocal2;
+    int hoWorkK2 = 0;
     // modeApplyDev's chunk of K = 2, 4, 5 or 8 columns on a lean mode of an np = 4 handle
     void modeApplyLean16(int id, int K, const InRows& in, const OutRows& o, hipStream_t s);
     // the modes of a batched apply are usable by it: tables for the harmonic launches,

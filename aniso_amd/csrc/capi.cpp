@@ -293,6 +293,24 @@ int aniso_cache_f32_bytes(aniso_handle h, int64_t* bytes) {
     });
 }
 
+int aniso_cache_mode(aniso_handle h, int id) {
+    ENTER(h);
+    return guarded([&] { get(h).cacheMode(id); });
+}
+
+int aniso_cache_mode_bytes(aniso_handle h, int64_t* bytes) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(bytes);
+        *bytes = get(h).cacheModeBytes();
+    });
+}
+
+int aniso_cache_mode_free(aniso_handle h, int id) {
+    ENTER(h);
+    return guarded([&] { get(h).cacheModeFree(id); });
+}
+
 int aniso_mapping_multi_f32_dev(aniso_handle h, int id, int nrhs, const double* x, int64_t ldx, double* out,
                                 int64_t ldo, void* stream) {
     ENTER(h);

@@ -435,6 +435,17 @@ void launch_near_mode(int K, int id, int nl, int maxLeaf, const int4* leafInfo, 
 void launch_ho_m2l_mode(int np, int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
                         const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
                         const double* nry, const HoTables* T, const double* mult, double* local, hipStream_t s);
+// The resident per-mode blocks of a high-order handle (mode_resident.hip):
+// F[pair] = (E / r) T_id(c) of every stored pair (owner / other: its target and source node),
+// R x R doubles per pair in 4 x 4 microtiles, and launch_ho_m2l_mode on them as an fp64 MFMA
+// product for 16 columns: columns 0 .. KA-1 from multA / to localA ([node][R][KA]), columns
+// 8 .. 8+KB-1 from multB / to localB (KB = 0: none), 1 <= KA <= 8, 0 <= KB <= 8.
+void launch_ho_mode_blocks(int np, int id, int64_t npairs, const int* owner, const int* other, const double* E,
+                           const double* ncx, const double* ncy, const double* nrx, const double* nry,
+                           const HoTables* T, double* F, hipStream_t s);
+void launch_ho_m2l_resident(int np, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
+                            const int* blk, const double* F, const double* multA, int KA, const double* multB,
+                            int KB, double* localA, double* localB, hipStream_t s);
 // The reduced-precision operator of a high-order handle (mode_apply_f32.hip, DESIGN.md
 // §3.18.5): both E arrays rounded to float with the same indexing (one launch), and
 // launch_near_mode / launch_ho_m2l_mode on the mirrors with the factor, the products and the
