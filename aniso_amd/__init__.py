@@ -88,6 +88,9 @@ def lib():
             "aniso_cache_mode": [P, I],
             "aniso_cache_mode_bytes": [P, lp],
             "aniso_cache_mode_free": [P, I],
+            "aniso_cache_mode_near": [P, I],
+            "aniso_cache_mode_near_bytes": [P, lp],
+            "aniso_cache_mode_near_free": [P, I],
             "aniso_cache_f32": [P],
             "aniso_cache_f32_bytes": [P, lp],
             "aniso_mapping_multi_f32_dev": [P, I, I, P, I64, P, I64, P],
@@ -97,6 +100,7 @@ def lib():
             "aniso_forward_solve_mixed_calls": [P, ip, I, ip],
             "aniso_forward_solve_calls": [P, ip, I, ip],
             "aniso_mode_apply_calls": [P, ip, I, ip],
+            "aniso_mode_near_calls": [P, ip, ip, I, ip],
             "aniso_mapping_stages_dev": [P, P, I, I, P, P],
             "aniso_set_shard": [P, I, I],
             "aniso_get_shard": [P, lp, lp],
@@ -472,6 +476,26 @@ class Aniso:
         """Drop mode id_'s resident blocks; -1: every mode's."""
         _check(lib().aniso_cache_mode_free(self.address, int(id_)))
 
+    # ---- the resident near field of a high-order handle (np = 6, 8)
+    def cache_mode_near(self, id_):
+        """Mode id_'s resident near-field factor blocks (aniso_cache_mode_near): the directed
+        near E blocks with every leaf's sources padded to 16, built in one launch.  While they
+        are resident, the fp64 mode applies on that mode run the fp64 MFMA near field on them
+        for a full 8-column chunk;
+        with cache_mode's blocks resident too, a 16-column chunk runs one near launch.  They are
+        independent of cache_mode's blocks.  A second call for a resident mode does nothing."""
+        _check(lib().aniso_cache_mode_near(self.address, int(id_)))
+
+    def cache_mode_near_bytes(self):
+        """Device bytes of the resident near blocks over all modes, 0 when there are none."""
+        b = ctypes.c_int64()
+        _check(lib().aniso_cache_mode_near_bytes(self.address, ctypes.byref(b)))
+        return int(b.value)
+
+    def cache_mode_near_free(self, id_=-1):
+        """Drop mode id_'s resident near blocks; -1: every mode's."""
+        _check(lib().aniso_cache_mode_near_free(self.address, int(id_)))
+
     # ---- the reduced-precision route of a high-order handle (np = 6, 8)
     def cache_f32(self):
         """Float mirrors of the mode-shared caches' M2L and near blocks (aniso_cache_f32): what
@@ -586,6 +610,19 @@ class Aniso:
         _check(lib().aniso_mode_apply_calls(self.address, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
                                             n.value, ctypes.byref(n)))
         return counts[: n.value]
+
+    def mode_near_calls(self):
+        """The near-field launches of the last mapping_multi(_dev) / forward_multi_dev call, in
+        order, as an (n, 2) int32 array of [columns, resident]: columns 2, 4, 5, 8, or 16 for
+        the wide launch; resident 1 if it ran on cache_mode_near's blocks, else 0."""
+        n = ctypes.c_int()
+        _check(lib().aniso_mode_near_calls(self.address, None, None, 0, ctypes.byref(n)))
+        cols = np.zeros(max(n.value, 1), dtype=np.int32)
+        res = np.zeros(max(n.value, 1), dtype=np.int32)
+        ipt = ctypes.POINTER(ctypes.c_int)
+        _check(lib().aniso_mode_near_calls(self.address, cols.ctypes.data_as(ipt), res.ctypes.data_as(ipt), n.value,
+                                           ctypes.byref(n)))
+        return np.stack([cols[: n.value], res[: n.value]], axis=1)
 
     def mapping_dev(self, charge, id_, out, stream=None, mask=STAGE_ALL):
         """charge/out: contiguous float64 torch tensors of N entries on the GPU."""

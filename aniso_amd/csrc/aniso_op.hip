@@ -416,6 +416,7 @@ void Operator::uploadPlan() {
     up(dNearPtr, plan.nearPtr);
     up(dNearSrc, plan.nearSrc);
     up(dNearKOff, plan.nearKOff);
+    up(dNearFOff, plan.nearFOff);
     up(dM2LTgt, plan.m2lTgt);
     up(dM2LPtr, plan.m2lPtr);
     up(dM2LSrc, plan.m2lSrc);
@@ -451,6 +452,7 @@ void Operator::uploadPlan() {
         attReady = false;
         dropCacheF32();
         modeBlocks.clear();
+        modeNearBlocks.clear();
     }
     up(dM2LCanonBase, plan.m2lCanonBase);
     up(dM2LInPtr, plan.m2lInPtr);
@@ -559,6 +561,7 @@ void Operator::setCoeff(const double* ss, const double* st) {
     attReady = false;
     dropCacheF32();    // the float mirrors are rounded from the shared caches of sigma_t
     modeBlocks.clear();  // ... and the resident mode blocks are formed from them
+    modeNearBlocks.clear();
     f32Ready = false;  // config 5's fp32 caches are rounded from the mode-0 operators of sigma_t
     m64.clear();       // ... and the fp64 16-RHS caches are the modes' operators
     coeffSet = true;
@@ -735,6 +738,61 @@ int64_t Operator::cacheModeBytes() const {
     return b;
 }
 
+// One mode's resident near blocks: the directed near E blocks with the
+// sources of every leaf padded to 16, one launch.  cacheMode's checks, order and memory policy.
+void Operator::cacheModeNear(int id) {
+    if (id < 0 || id >= kernelSize)
+        throw std::out_of_range("aniso_cache_mode_near: kernel id " + std::to_string(id) + " out of range [0, " +
+                                std::to_string(kernelSize) + ")");
+    if (!highOrder())
+        throw std::logic_error("aniso_cache_mode_near: the resident near blocks are built for np = 6, 8; the resident "
+                               "route of an np = 4 handle is aniso_cache(h, id)");
+    refuseHoShard("aniso_cache_mode_near");
+    if (plan.nranks > 1) throw std::logic_error("aniso_cache_mode_near on a sharded handle (use an unsharded handle)");
+    if (!coeffSet || !attReady || !modes[id].tables)
+        throw std::runtime_error("aniso_cache_mode_near before aniso_set_coeff and aniso_cache(" + std::to_string(id) +
+                                 ") or aniso_cache_block");
+    if (plan.nearSymHsOn || plan.nearPartTotal != 0)
+        throw std::logic_error("aniso_cache_mode_near: the near E blocks are not stored directed");
+    if (modeNearBlocks.count(id)) return;
+    ensureDevice();
+    const size_t need = (size_t)plan.nearFTotal * sizeof(double);
+    size_t freeB = 0, totalB = 0;
+    HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+    const std::string sizes = std::to_string(need) + " bytes for mode " + std::to_string(id) + ", " +
+                              std::to_string(freeB) + " bytes of HBM free";
+    if (need + (size_t)(1ull << 30) > freeB)  // keep a GiB of headroom
+        throw std::runtime_error("aniso_cache_mode_near: the resident near blocks do not fit with a GiB to spare: " + sizes);
+    DevBuf F;
+    try {
+        F.alloc(need);
+    } catch (const std::exception& e) {
+        throw std::runtime_error("aniso_cache_mode_near: the resident near blocks could not be allocated: " + sizes + ": " +
+                                 e.what());
+    }
+    launch_near_mode_blocks(id, (int)plan.leaves.size(), dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
+                            dNearPts.as<int>(), dNearKOff.as<int64_t>(), dNearFOff.as<int64_t>(), dAttNear.as<double>(),
+                            dPxT.as<double>(), dPyT.as<double>(), F.as<double>(), own);
+    HIP_CHECK(hipStreamSynchronize(own));
+    modeNearBlocks.emplace(id, std::move(F));
+}
+
+void Operator::cacheModeNearFree(int id) {
+    if (id < -1 || id >= kernelSize)
+        throw std::out_of_range("aniso_cache_mode_near_free: kernel id " + std::to_string(id) + " out of range [-1, " +
+                                std::to_string(kernelSize) + ")");
+    if (modeNearBlocks.empty() || (id >= 0 && !modeNearBlocks.count(id))) return;
+    HIP_CHECK(hipDeviceSynchronize());  // queued applies (on the caller's streams too) may still read them
+    if (id < 0) modeNearBlocks.clear();
+    else modeNearBlocks.erase(id);
+}
+
+int64_t Operator::cacheModeNearBytes() const {
+    int64_t b = 0;
+    for (const auto& m : modeNearBlocks) b += (int64_t)m.second.bytes;
+    return b;
+}
+
 void Operator::refuseHighOrder(const char* what) const {
     if (highOrder())
         throw std::logic_error(std::string(what) + ": a high-order handle (np = " + std::to_string(np) +
@@ -756,6 +814,7 @@ void Operator::needResident(int id, const char* what) const {
 void Operator::buildAttCache() {
     dropCacheF32();
     modeBlocks.clear();
+    modeNearBlocks.clear();
     const Params* P = dParams.as<Params>();
     const int64_t npairs = (int64_t)(plan.attOwner.size() + plan.hmCopyOwner.size());  // stored blocks + copies
     const size_t rank = (size_t)np * np;
@@ -1151,12 +1210,41 @@ void Operator::nearMode(int K, int id, const OutRows& o, hipStream_t s, ApplyPre
                              dAttNearF.as<float>(), dNcx.as<double>(), dNcy.as<double>(), dPxT.as<double>(),
                              dPyT.as<double>(), dSigDiag.as<double>(), dFT.as<double>(), o.perm, o.base, o.ld, kScale,
                              o.out, s);
+        nearCalls.emplace_back(K, 0);  // (the f32 entries ignore the resident near blocks)
+        return;
+    }
+    // the stored near blocks serve the full chunk only: at 2, 4 and 5 columns k_near_mode's span
+    // on mode 0 is as short or shorter at both orders (measured)
+    if (const double* F = K == kMaxRhs ? modeNearResident(id) : nullptr) {
+        launch_near_resident(id, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(),
+                             dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(), dNearFOff.as<int64_t>(), F,
+                             dSigDiag.as<double>(), dFT.as<double>(), K, nullptr, 0, o.perm, o.base, kScale, o.out, o.ld,
+                             nullptr, 0, s);
+        nearCalls.emplace_back(K, 1);
         return;
     }
     launch_near_mode(K, id, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
                      dNearPts.as<int>(), dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(),
                      dPyT.as<double>(), dSigDiag.as<double>(), dFT.as<double>(), o.perm, o.base, o.ld, kScale, o.out,
                      s);
+    nearCalls.emplace_back(K, 0);
+}
+
+void Operator::nearMode16(int id, int KA, int KB, const OutRows& oA, const OutRows& oB, hipStream_t s) {
+    const double* F = modeNearResident(id);
+    if (!F || oA.perm != oB.perm || oA.base != oB.base)
+        throw std::logic_error("a 16-column near launch without resident near blocks or with two output orders");
+    launch_near_resident(id, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
+                         dNearPts.as<int>(), dNearFOff.as<int64_t>(), F, dSigDiag.as<double>(), dFT.as<double>(), KA,
+                         dFT2.as<double>(), KB, oA.perm, oA.base, kScale, oA.out, oA.ld, oB.out, oB.ld, s);
+    nearCalls.emplace_back(2 * kMaxRhs, 1);
+}
+
+void Operator::reserveCharges2(int K) {
+    if (K <= workK2) return;
+    workK2 = K;
+    dFT2.alloc((size_t)geo.N * rhs_stride(K) * sizeof(double));
+    dCT2.alloc((size_t)geo.N * rhs_stride(K) * sizeof(double));
 }
 
 void Operator::corrections(int K, const CorrFold& cf, const double* fT, const double* cT, int64_t begin, int64_t end,
@@ -1179,10 +1267,10 @@ void Operator::hoReserve(int K, hipStream_t s, bool second) {
     HIP_CHECK(hipMemsetAsync(local.p, 0, hoDoubles(K) * sizeof(double), s));
 }
 
-void Operator::hoUpPass(int K, double* mult, bool allLeaves, hipStream_t s) {
+void Operator::hoUpPass(int K, const double* fT, double* mult, bool allLeaves, hipStream_t s) {
     const int nl = allLeaves ? hoLeafAll : (int)plan.leaves.size();
     launch_ho_p2m(np, K, nl, (allLeaves ? dHoLeafAll : dLeafInfo).as<int4>(), dNcx.as<double>(), dNcy.as<double>(),
-                  dNrx.as<double>(), dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), dFT.as<double>(),
+                  dNrx.as<double>(), dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), fT,
                   dHoTab.as<HoTables>(), mult, s);
     for (size_t l = 0; l + 1 < hoM2mPtr.size(); ++l)
         launch_ho_m2m(np, K, hoM2mPtr[l + 1] - hoM2mPtr[l], dHoM2m.as<int>() + hoM2mPtr[l], dHoChild.as<int4>(),
@@ -1684,7 +1772,7 @@ void Operator::applyBlockHigh(int K, const InRows& in, int nterm, const int* ids
     corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, mask, o, s);
     sp.end(6);
     // (a shard: the up pass over every leaf of the tree -- the M2L reads any node's multipole)
-    hoUpPass(K, dHoMult.as<double>(), hoShard, s);
+    hoUpPass(K, dFT.as<double>(), dHoMult.as<double>(), hoShard, s);
     sp.end(1);
     sp.startRoofline();
     launch_ho_m2l(np, K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
@@ -1746,7 +1834,7 @@ void Operator::modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, 
     sp.end(4);
     corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
     sp.end(6);
-    hoUpPass(K, dHoMult.as<double>(), false, s);
+    hoUpPass(K, dFT.as<double>(), dHoMult.as<double>(), false, s);
     sp.end(1);
     sp.startRoofline();
     if (f32)
@@ -1772,6 +1860,8 @@ void Operator::modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, 
 // A chunk of 9 .. 16 columns on a resident mode: each half runs modeApplyHigh's launches on
 // expansion buffers of its own (the charges dFT / dCT are re-used: the second half's are
 // formed after the first half's up pass has read them), around one M2L for all 16 columns.
+// With the mode's near blocks resident too (cacheModeNear) the near field is one launch for
+// all 16 columns as well, and the second half's charges live in dFT2 / dCT2.
 void Operator::modeApplyHigh16(int id, int K2, const InRows& inA, const OutRows& oA, const InRows& inB,
                                const OutRows& oB, hipStream_t s) {
     const double* F = modeResident(id);
@@ -1781,18 +1871,37 @@ void Operator::modeApplyHigh16(int id, int K2, const InRows& inA, const OutRows&
     hoReserve(KA, s);
     hoReserve(K2, s, true);
     StageSpans sp(*this, s);
-    for (int half = 0; half < 2; ++half) {
-        const int K = half ? K2 : KA;
-        const InRows& in = half ? inB : inA;
-        const OutRows& o = half ? oB : oA;
-        const CorrFold& cf = corrTable(K, 1, &id, identityMix(K).data());
-        prepareCharges(K, in, dFT.as<double>(), dCT.as<double>(), s);
-        nearMode(K, id, o, s);
+    if (modeNearResident(id)) {
+        // one near launch for all 16 columns: both halves' charges exist at once, the second
+        // half's in dFT2 / dCT2 (same stage ids, each stage once for both halves)
+        reserveCharges2(K2);
+        const CorrFold& cfA = corrTable(KA, 1, &id, identityMix(KA).data());
+        prepareCharges(KA, inA, dFT.as<double>(), dCT.as<double>(), s);
+        prepareCharges(K2, inB, dFT2.as<double>(), dCT2.as<double>(), s);
+        nearMode16(id, KA, K2, oA, oB, s);
         sp.end(4);
-        corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
+        corrections(KA, cfA, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, oA, s);
+        // (corrTable may drop its folds when it adds one: the second half's is taken after the first's launch)
+        const CorrFold& cfB = corrTable(K2, 1, &id, identityMix(K2).data());
+        corrections(K2, cfB, dFT2.as<double>(), dCT2.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, oB, s);
         sp.end(6);
-        hoUpPass(K, (half ? dHoMult2 : dHoMult).as<double>(), false, s);
+        hoUpPass(KA, dFT.as<double>(), dHoMult.as<double>(), false, s);
+        hoUpPass(K2, dFT2.as<double>(), dHoMult2.as<double>(), false, s);
         sp.end(1);
+    } else {
+        for (int half = 0; half < 2; ++half) {
+            const int K = half ? K2 : KA;
+            const InRows& in = half ? inB : inA;
+            const OutRows& o = half ? oB : oA;
+            const CorrFold& cf = corrTable(K, 1, &id, identityMix(K).data());
+            prepareCharges(K, in, dFT.as<double>(), dCT.as<double>(), s);
+            nearMode(K, id, o, s);
+            sp.end(4);
+            corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
+            sp.end(6);
+            hoUpPass(K, dFT.as<double>(), (half ? dHoMult2 : dHoMult).as<double>(), false, s);
+            sp.end(1);
+        }
     }
     sp.startRoofline();
     launch_ho_m2l_resident(np, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
@@ -1844,7 +1953,10 @@ void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, cons
     checkDeviceErrors();
     ensureDevice();
     if (prec == ApplyPrec::F32) cacheF32();  // (built on first use)
-    if (!keepCalls) modeCalls.clear();
+    if (!keepCalls) {
+        modeCalls.clear();
+        nearCalls.clear();
+    }
     const int64_t N = geo.N;
     // a lean mode of an np = 4 handle on the mode-shared caches (leanMapping's conditions;
     // the mode kernels read the directed near blocks)
@@ -1954,6 +2066,7 @@ void Operator::mappingMultiHost(const double* Q, int k, int id, double* Out) {
     dq.alloc((size_t)kb * N * sizeof(double));
     dout.alloc((size_t)kb * N * sizeof(double));
     modeCalls.clear();
+    nearCalls.clear();
     for (int j0 = 0; j0 < k; j0 += kb) {
         const int nb = std::min(kb, k - j0);
         HIP_CHECK(hipMemcpyAsync(dq.p, Q + (size_t)j0 * N, (size_t)nb * N * sizeof(double), hipMemcpyHostToDevice, own));
@@ -2311,7 +2424,7 @@ void Operator::blockMultiChunk(int which, int S, int nreal, const double* x, int
         sp.end(4);
         corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
         sp.end(6);
-        hoUpPass(K, dMsMult.as<double>() + (size_t)j * exp, false, s);
+        hoUpPass(K, dFT.as<double>(), dMsMult.as<double>() + (size_t)j * exp, false, s);
         sp.end(1);
     }
     sp.start();

@@ -156,6 +156,17 @@ public:
     void cacheMode(int id);
     void cacheModeFree(int id);
     int64_t cacheModeBytes() const;
+    // one mode's resident near-field factor blocks on a high-order handle (np = 6, 8;
+    // mode_near_resident.hip): F_id = (E / r) T_id(c) of every stored entry
+    // of the directed near E blocks, in 16-row tiles of 4 x 4 microtiles at Plan::nearFOff,
+    // built in one launch.  While mode id is near-resident the fp64 mode applies run the MFMA
+    // near field on them for a full 8-column chunk (2, 4 and 5 columns keep k_near_mode: no
+    // gain measured on mode 0), and a 16-column chunk (which exists only while the M2L blocks of
+    // cacheMode are resident too) runs one near launch for all its columns.  Independent of
+    // the M2L blocks; same lifetime rules.  cacheModeNearBytes: their device bytes over all modes.
+    void cacheModeNear(int id);
+    void cacheModeNearFree(int id);
+    int64_t cacheModeNearBytes() const;
     void mappingHost(const double* charge, int id, double* out);
     void mappingBatchedHost(const double* Q, int k, int id, double* Out);  // N x k column-major
     // One mode on nrhs vectors wherever the mode is ready: rows of N
@@ -185,6 +196,9 @@ public:
     // high-order mode's chunk of more than 8 columns, a resident
     // np = 4 mode's applyBlock chunk (1, 2, 4, 5 or 8), 8 for a per-column leanMapping pass
     const std::vector<int>& modeApplyCalls() const { return modeCalls; }
+    // the near-field launches of the same call, in order: (columns: 2, 4, 5, 8, or 16 for the
+    // wide launch; 1 if it ran on the resident near blocks, 0 if k_near_mode or its f32 form)
+    const std::vector<std::pair<int, int>>& modeNearCalls() const { return nearCalls; }
     void mappingMultiHost(const double* Q, int k, int id, double* Out);  // N x k column-major
     const double* sigmaSTree() const { return dSigmaT.as<double>(); }    // sigma_s in tree order (device)
     void mappingDev(const double* charge, int id, double* out, hipStream_t s, int stageMask = 0x3f);
@@ -568,13 +582,17 @@ private:
     void prepareCharges(int K, const InRows& in, double* fT, double* cT, hipStream_t s);
     void nearUnstaged(int K, const HarmWeights& hw, const HarmWindow* win, int mask, const OutRows& o, hipStream_t s);
     void nearMode(int K, int id, const OutRows& o, hipStream_t s, ApplyPrec prec = ApplyPrec::F64);
+    // a 16-column chunk's near field on the resident near blocks: columns 0 .. KA-1 from
+    // dFT to oA, 8 .. 8+KB-1 from dFT2 to oB, one launch
+    void nearMode16(int id, int KA, int KB, const OutRows& oA, const OutRows& oB, hipStream_t s);
     void corrections(int K, const CorrFold& cf, const double* fT, const double* cT, int64_t begin, int64_t end,
                      int mask, const OutRows& o, hipStream_t s);
     // dHoMult / dHoLocal for K columns (grown, never shrunk), the locals zeroed; second: the
     // expansions of a 16-column chunk's second half (dHoMult2 / dHoLocal2)
     void hoReserve(int K, hipStream_t s, bool second = false);
     size_t hoDoubles(int K) const { return (size_t)tree.nn * np * np * K; }  // one expansion buffer
-    void hoUpPass(int K, double* mult, bool allLeaves, hipStream_t s);  // allLeaves: a shard's replicated P2M
+    // fT: the charges the P2M reads; allLeaves: a shard's replicated P2M
+    void hoUpPass(int K, const double* fT, double* mult, bool allLeaves, hipStream_t s);
     void hoDownPass(int K, double* local, const OutRows& o, hipStream_t s);
     void upTier16(int K, int k, const int* list, int ntask, double* fT, double* cT, const double* recv, double* send,
                   unsigned* zeroCnt, const UpTail* tail, const InRows& in, hipStream_t s);
@@ -606,6 +624,16 @@ private:
     }
     DevBuf dHoMult2, dHoLocal2;
     int hoWorkK2 = 0;
+    std::map<int, DevBuf> modeNearBlocks;  // cacheModeNear: resident near factor blocks per mode id
+    const double* modeNearResident(int id) const {
+        const auto it = modeNearBlocks.find(id);
+        return it == modeNearBlocks.end() ? nullptr : it->second.as<double>();
+    }
+    // the charges of a 16-column chunk's second half while one near launch serves both
+    // (grown, never shrunk, as dHoMult2)
+    DevBuf dFT2, dCT2;
+    int workK2 = 0;
+    void reserveCharges2(int K);
     // modeApplyDev's chunk of K = 2, 4, 5 or 8 columns on a lean mode of an np = 4 handle
     void modeApplyLean16(int id, int K, const InRows& in, const OutRows& o, hipStream_t s);
     // the modes of a batched apply are usable by it: tables for the harmonic launches,
@@ -681,6 +709,7 @@ private:
     std::vector<int> solveCalls;
     std::vector<std::pair<int, int>> mixedCalls;  // forwardSolveMixedCalls()
     std::vector<int> modeCalls;  // modeApplyCalls()
+    std::vector<std::pair<int, int>> nearCalls;  // modeNearCalls()
     void arnoldiParts(int rows);  // dKryPart for sweeps of `rows` rows
     bool topTraceOn = false;
     int hmRing = 0;  // the cluster M2L's LDS ring depth (ANISO_HM_RING; 0: the one-block-in-flight form)
@@ -817,7 +846,7 @@ private:
     int maxNearS = 0;
     // geometry / tree on device
     DevBuf dPxT, dPyT, dPerm, dW, dNcx, dNcy, dNrx, dNry, dBegin, dCount, dParent, dSlot, dChild, dIsLeaf, dNodeGeo;
-    DevBuf dLeaves, dNearPtr, dNearSrc, dNearKOff, dM2LTgt, dM2LPtr, dM2LSrc, dM2LPairTgt;
+    DevBuf dLeaves, dNearPtr, dNearSrc, dNearKOff, dNearFOff, dM2LTgt, dM2LPtr, dM2LSrc, dM2LPairTgt;
     DevBuf dUpTaskPtr, dUpGrpPtr, dUpGrp, dUpNode, dUpCode, dUpDesc, dUpGrpFix, dUpGeom, dUpLeaf;                       // up-pass tiers
     DevBuf dDnTaskPtr, dDnGrpPtr, dDnGrp, dDnNode, dDnLeafPtr, dDnLeafSlot, dDnLeafIdx, dDnLeafPts, dDnPtsRange, dDnDesc, dDnGrpFix, dDnLeafGeom;  // down
     DevBuf dLeafInfo, dNearPtsPtr, dNearPts;

@@ -311,6 +311,24 @@ int aniso_cache_mode_free(aniso_handle h, int id) {
     return guarded([&] { get(h).cacheModeFree(id); });
 }
 
+int aniso_cache_mode_near(aniso_handle h, int id) {
+    ENTER(h);
+    return guarded([&] { get(h).cacheModeNear(id); });
+}
+
+int aniso_cache_mode_near_bytes(aniso_handle h, int64_t* bytes) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(bytes);
+        *bytes = get(h).cacheModeNearBytes();
+    });
+}
+
+int aniso_cache_mode_near_free(aniso_handle h, int id) {
+    ENTER(h);
+    return guarded([&] { get(h).cacheModeNearFree(id); });
+}
+
 int aniso_mapping_multi_f32_dev(aniso_handle h, int id, int nrhs, const double* x, int64_t ldx, double* out,
                                 int64_t ldo, void* stream) {
     ENTER(h);
@@ -418,6 +436,19 @@ int aniso_mode_apply_calls(aniso_handle h, int* counts, int cap, int* n) {
         *n = (int)c.size();
         if (counts)
             for (int i = 0; i < cap && i < (int)c.size(); ++i) counts[i] = c[i];
+    });
+}
+
+int aniso_mode_near_calls(aniso_handle h, int* cols, int* resident, int cap, int* n) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(n);
+        const auto& c = get(h).modeNearCalls();
+        *n = (int)c.size();
+        for (int i = 0; i < cap && i < (int)c.size(); ++i) {
+            if (cols) cols[i] = c[i].first;
+            if (resident) resident[i] = c[i].second;
+        }
     });
 }
 

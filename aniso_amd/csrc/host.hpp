@@ -68,6 +68,10 @@ struct Plan {
     std::vector<int64_t> nearPtr;              // CSR over leaves -> source nodes
     std::vector<int> nearSrc;
     std::vector<int64_t> nearKOff;             // per leaf: offset of its K block (doubles)
+    // per leaf: offset of its block of a mode's resident near factors (doubles; rows padded
+    // to a multiple of 4 as the K block's, sources to a multiple of 16), and their total
+    std::vector<int64_t> nearFOff;
+    int64_t nearFTotal = 0;
     std::vector<std::array<int, 4>> leafInfo;  // per leaf: node, begin, count, S (source points)
     // symmetric storage: M2L targets' stored sources are
     // [m2lNDir directed | canonical]; canonical pair c (= m2lCanonBase + j) sends

@@ -419,6 +419,8 @@ void Plan::build(const Tree& t, int np, int rank_, int nranks_) {
         }
         nearPtr.push_back((int64_t)nearSrc.size());
         nearKTotal += S * ((t.count[i] + 3) & ~(int64_t)3);  // rows padded to a multiple of 4: 32-B row quads
+        nearFOff.push_back(nearFTotal);  // the resident near blocks: sources padded to 16 as well
+        nearFTotal += ((S + 15) & ~(int64_t)15) * ((t.count[i] + 3) & ~(int64_t)3);
         storedNear += S * t.count[i];
         if (S > (int64_t)1 << 30 || partTotal > ((int64_t)1 << 31) - 1)
             throw std::invalid_argument("leaf neighbourhood too large");

@@ -446,6 +446,19 @@ void launch_ho_mode_blocks(int np, int id, int64_t npairs, const int* owner, con
 void launch_ho_m2l_resident(int np, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
                             const int* blk, const double* F, const double* multA, int KA, const double* multB,
                             int KB, double* localA, double* localB, hipStream_t s);
+// The resident near blocks of one mode (mode_near_resident.hip):
+// F = mode_factor<true> of every stored entry of the directed near E blocks, per leaf at
+// nearFOff in 16-row tiles of 4 x 4 microtiles (rows padded to 4, sources to 16, the padding
+// zero), and launch_near_mode on them as an fp64 MFMA product for 16 columns: columns
+// 0 .. KA-1 from fTA ([tree position][kStride<KA>]) to outA, columns 8 .. 8+KB-1 from fTB to
+// outB (KB = 0: none), KA and KB in {2, 4, 5, 8}.  out (stored) as launch_near_mode's.
+void launch_near_mode_blocks(int id, int nl, const int4* leafInfo, const int64_t* nearPtsPtr, const int* nearPts,
+                             const int64_t* nearKOff, const int64_t* nearFOff, const double* E, const double* pxT,
+                             const double* pyT, double* F, hipStream_t s);
+void launch_near_resident(int id, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
+                          const int* nearPts, const int64_t* nearFOff, const double* F, const double* sigDiag,
+                          const double* fTA, int KA, const double* fTB, int KB, const int* operm, int64_t obase,
+                          double scale, double* outA, int64_t ldoA, double* outB, int64_t ldoB, hipStream_t s);
 // The reduced-precision operator of a high-order handle (mode_apply_f32.hip, DESIGN.md
 // §3.18.5): both E arrays rounded to float with the same indexing (one launch), and
 // launch_near_mode / launch_ho_m2l_mode on the mirrors with the factor, the products and the

@@ -161,6 +161,12 @@ int aniso_forward_solve_calls(aniso_handle h, int *counts, int cap, int *n);
  * kernels do not serve (ANISO_NEAR_HS_SYM=1) reports 8, the offset form's rows, once per
  * column.  Host only. */
 int aniso_mode_apply_calls(aniso_handle h, int *counts, int cap, int *n);
+/* the near-field launches of the handle's last aniso_mapping_multi(_dev) / aniso_forward_multi_dev
+ * call, in order: *n = their number, cols[i] (cap >= 0 entries, may be NULL) = the columns of
+ * launch i (2, 4, 5, 8, or 16 for the wide launch), resident[i] (likewise) = 1 if it ran on
+ * the stored near blocks of aniso_cache_mode_near, 0 if k_near_mode (or its f32 form).
+ * Host only. */
+int aniso_mode_near_calls(aniso_handle h, int *cols, int *resident, int cap, int *n);
 /* ---- the mixed-precision forward solve ---- */
 /* every operator pass of the handle's last aniso_forward_solve_multi_mixed(_dev) call, in
  * order: *n = their number, calls (cap >= 0 pairs, may be NULL) = {precision, columns} of
