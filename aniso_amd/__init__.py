@@ -121,6 +121,10 @@ def lib():
             "aniso_gmres": [P, dp, dp, I, I, D, dp, I, ip, dp],
             "aniso_block_solve": [P, dp, dp, I, D, I, dp, I, ip, dp],
             "aniso_block_solve_dev": [P, P, P, I, D, I, dp, I, ip, dp, P],
+            "aniso_block_op_f32_dev": [P, I, P, I64, P, I64, I, P],
+            "aniso_block_solve_relaxed": [P, dp, dp, I, D, I, D, dp, I, ip, dp],
+            "aniso_block_solve_relaxed_dev": [P, P, P, I, D, I, D, dp, I, ip, dp, P],
+            "aniso_block_solve_relaxed_calls": [P, ip, I, ip],
             "aniso_solve16_mixed_dev": [P, P, I64, P, I64, I, D, D, I, I, ip, ip, dp, P],
             "aniso_solve_mixed_dev": [P, I, P, I64, P, I64, I, D, D, I, I, ip, ip, ip, dp, P],
             "aniso_apply_block_dev": [P, I, P, I64, I, I, ip, dp, P, I64, I, P],
@@ -1030,6 +1034,59 @@ class Aniso:
         _check(lib().aniso_block_solve_dev(self.address, pr, px, int(restart), float(tol), int(maxit), _dp(hist),
                                            len(hist), ctypes.byref(it), ctypes.byref(rr), ctypes.c_void_p(s)))
         return it.value, hist[: min(abs(it.value), len(hist))], rr.value
+
+    # ---- the relaxed-precision block solve of a high-order handle (np = 6, 8, ks <= 8)
+    def block_op_f32_dev(self, which, x, out, tree=False, stream=None):
+        """block_op_dev with the M2L and the near field in fp32 on the float mirrors
+        (aniso_block_op_f32_dev): float64 tensors in and out, about 1e-7 .. 1e-6 from
+        block_op_dev; the inexact operator of block_solve_relaxed."""
+        import torch
+
+        _dev_rows(x, self.ks, self.N, "x")
+        _dev_rows(out, self.ks, self.n_owned() if tree else self.N, "out")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _check(lib().aniso_block_op_f32_dev(self.address, int(which), ctypes.c_void_p(x.data_ptr()), int(x.stride(0)),
+                                            ctypes.c_void_p(out.data_ptr()), int(out.stride(0)), int(bool(tree)),
+                                            ctypes.c_void_p(s)))
+        return out
+
+    def block_solve_relaxed(self, rhs, restart=400, tol=1e-11, maxit=400, relax=None, x0=None):
+        """block_solve as inexact GMRES (aniso_block_solve_relaxed): the Arnoldi matvecs run on
+        the f32 block operator once the relative residual estimate is <= relax (None: the
+        library default 1e6 x tol; 0: block_solve's bits); every cycle-boundary residual is
+        fp64.  Returns what block_solve returns."""
+        rhs = _f64(rhs, self.ks * self.N, "rhs")
+        x = np.zeros(self.ks * self.N) if x0 is None else _f64(x0, self.ks * self.N, "x0").copy()
+        hist = np.zeros(restart * maxit if restart * maxit < 100000 else 100000)
+        it, rr = ctypes.c_int(), ctypes.c_double()
+        _check(lib().aniso_block_solve_relaxed(self.address, _dp(rhs), _dp(x), int(restart), float(tol), int(maxit),
+                                               -1.0 if relax is None else float(relax), _dp(hist), len(hist),
+                                               ctypes.byref(it), ctypes.byref(rr)))
+        return it.value, x.reshape(self.ks, self.N), hist[: min(abs(it.value), len(hist))], rr.value
+
+    def block_solve_relaxed_dev(self, rhs, x, restart=400, tol=1e-11, maxit=400, relax=None, stream=None):
+        """The same on (ks, N) float64 CUDA tensors (original order); x: guess in, solution out.
+        Returns what block_solve_dev returns."""
+        import torch
+
+        pr, px = _dev_vec(rhs, self.ks * self.N, "rhs"), _dev_vec(x, self.ks * self.N, "x")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        hist = np.zeros(min(restart * maxit, 100000))
+        it, rr = ctypes.c_int(), ctypes.c_double()
+        _check(lib().aniso_block_solve_relaxed_dev(self.address, pr, px, int(restart), float(tol), int(maxit),
+                                                   -1.0 if relax is None else float(relax), _dp(hist), len(hist),
+                                                   ctypes.byref(it), ctypes.byref(rr), ctypes.c_void_p(s)))
+        return it.value, hist[: min(abs(it.value), len(hist))], rr.value
+
+    def block_solve_relaxed_calls(self):
+        """The precision (64 / 32) of every operator pass of the last block_solve_relaxed(_dev),
+        in order."""
+        n = ctypes.c_int()
+        _check(lib().aniso_block_solve_relaxed_calls(self.address, None, 0, ctypes.byref(n)))
+        calls = np.zeros(max(n.value, 1), dtype=np.int32)
+        _check(lib().aniso_block_solve_relaxed_calls(self.address, calls.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                     n.value, ctypes.byref(n)))
+        return calls[: n.value]
 
     def solve16_mixed_dev(self, B, X, m=40, tol=1e-12, inner_tol=1e-6, max_outer=30, max_cycles=20, stream=None):
         """Config 5's solve A X = B (aniso_solve16_mixed_dev): 16 right-hand sides, the

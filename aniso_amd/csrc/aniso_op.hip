@@ -669,7 +669,8 @@ void Operator::cacheF32() {
     refuseHoShard("aniso_cache_f32");
     if (!coeffSet || !attReady || !modes[0].tables)
         throw std::runtime_error("aniso_cache_f32 before aniso_set_coeff and aniso_cache(0) or aniso_cache_block");
-    if (dAttM2LF.p && dAttNearF.p) return;
+    // (an array without entries -- a tree without M2L pairs -- has no mirror to build)
+    if ((dAttM2LF.p || !dAttM2L.bytes) && (dAttNearF.p || !dAttNear.bytes)) return;
     ensureDevice();
     const size_t na = dAttM2L.bytes / sizeof(double), nb = dAttNear.bytes / sizeof(double);
     try {
@@ -1201,6 +1202,13 @@ void Operator::nearUnstaged(int K, const HarmWeights& hw, const HarmWindow* win,
                    dNearPts.as<int>(), dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(),
                    dPyT.as<double>(), dSigDiag.as<double>(), hw, dFT.as<double>(), o.perm, o.base, o.ld, mask, kScale,
                    o.out, nullptr, nullptr, nullptr, 0, nullptr, nearWpe, s, nullptr, win);
+}
+
+void Operator::nearUnstagedF32(int K, const HarmWeights& hw, const OutRows& o, hipStream_t s) {
+    launch_near_hm_f32(K, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
+                       dNearPts.as<int>(), dNearKOff.as<int64_t>(), dAttNearF.as<float>(), dNcx.as<double>(),
+                       dNcy.as<double>(), dPxT.as<double>(), dPyT.as<double>(), dSigDiag.as<double>(), hw,
+                       dFT.as<double>(), o.perm, o.base, o.ld, kScale, o.out, s);
 }
 
 void Operator::nearMode(int K, int id, const OutRows& o, hipStream_t s, ApplyPrec prec) {
@@ -1763,11 +1771,17 @@ void Operator::applyBlockHigh(int K, const InRows& in, int nterm, const int* ids
     if (win) hw = call.hw;
     else if (!harmonicWeights(K, nterm, ids, mixes, hw))
         refuseHighOrder("a block apply whose mixes are not aniso.m's forward / mforward");
+    // the relaxed-precision operator (block_f32.hip): the whole operator on an unsharded
+    // handle whose mirrors the caller has built
+    const bool f32 = call.prec == ApplyPrec::F32;
+    if (f32 && (win || hoShard || (dAttM2L.bytes && !dAttM2LF.p) || (dAttNear.bytes && !dAttNearF.p)))
+        throw std::logic_error("the f32 block operator: a pass, a shard, or no float mirrors");
     hoReserve(K, s);
     const CorrFold& cf = corrTable(K, nterm, ids, mixes);
     StageSpans sp(*this, s);
     prepareCharges(K, in, dFT.as<double>(), dCT.as<double>(), s);
-    nearUnstaged(K, hw, win, mask, o, s);
+    if (f32) nearUnstagedF32(K, hw, o, s);
+    else nearUnstaged(K, hw, win, mask, o, s);
     sp.end(4);
     corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, mask, o, s);
     sp.end(6);
@@ -1775,9 +1789,16 @@ void Operator::applyBlockHigh(int K, const InRows& in, int nterm, const int* ids
     hoUpPass(K, dFT.as<double>(), dHoMult.as<double>(), hoShard, s);
     sp.end(1);
     sp.startRoofline();
-    launch_ho_m2l(np, K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
-                  dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                  dNry.as<double>(), dHoTab.as<HoTables>(), hw, win, dHoMult.as<double>(), dHoLocal.as<double>(), s);
+    if (f32)
+        launch_ho_m2l_f32(np, K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
+                          dAttBlk.as<int>(), dAttM2LF.as<float>(), dNcx.as<double>(), dNcy.as<double>(),
+                          dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(), hw, dHoMult.as<double>(),
+                          dHoLocal.as<double>(), s);
+    else
+        launch_ho_m2l(np, K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
+                      dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(),
+                      dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(), hw, win, dHoMult.as<double>(),
+                      dHoLocal.as<double>(), s);
     sp.end(2);
     hoDownPass(K, dHoLocal.as<double>(), o, s);
     sp.end(5);
@@ -2125,8 +2146,9 @@ std::vector<double> Operator::blockMixes(int nb, double g, bool chi) {
 
 void Operator::blockOpDev(int which, const double* x, int64_t ldx, double* out, int64_t ldo, bool treeIo,
                           hipStream_t s, double gval, const double* sigT, int phase, double* rootsSend,
-                          const double* rootsRecv) {
+                          const double* rootsRecv, ApplyPrec prec) {
     if (which < 0 || which > 2) throw std::invalid_argument("block operator: which must be 0, 1 or 2");
+    if (prec == ApplyPrec::F32) blockOpF32Refuse("the f32 block operator");
     if (phase != 0) refuseHighOrder("the two-phase block operator");
     // a sharded high-order handle: the matvec of blockOpShardedHigh for a caller who gathered
     // the input -- the whole vector in tree order in, the owned slice out
@@ -2142,8 +2164,42 @@ void Operator::blockOpDev(int which, const double* x, int64_t ldx, double* out, 
     ApplyCall call;
     call.phased(phase, rootsSend, rootsRecv);
     call.hoShard = hoShard;
+    call.prec = prec;
     if (hoShard && plan.ownEnd == plan.ownBegin) return;  // a rank that owns nothing
     blockOp(which, x, ldx, out, ldo, treeIo, s, gval, sigT, call);
+}
+
+// ---- the relaxed-precision block operator ----
+
+void Operator::blockOpF32Refuse(const char* what) const {
+    const std::string w(what);
+    if (!highOrder())
+        throw std::logic_error(w + ": the f32 block operator is built for np = 6, 8; the reduced-precision route of an "
+                                   "np = 4 handle is aniso_solve_mixed_dev");
+    refuseHoShard(what);
+    if (plan.nranks > 1) throw std::logic_error(w + " on a sharded handle (use an unsharded handle)");
+    if (ks > kMaxRhs)
+        throw std::logic_error(w + ": ks = " + std::to_string(ks) + " blocks run as passes of " +
+                               std::to_string(kMaxRhs) + ", and the passes have no f32 form");
+}
+
+void Operator::blockOpF32Ready(const char* what) const {
+    bool ready = coeffSet && attReady;
+    for (int m = 0; ready && m < kernelSize; ++m) ready = modes[m].tables;
+    if (!ready)
+        throw std::runtime_error(std::string(what) + " before aniso_set_coeff and aniso_cache_block (or aniso_cache of "
+                                                     "every mode)");
+}
+
+void Operator::blockOpF32Dev(int which, const double* x, int64_t ldx, double* out, int64_t ldo, bool treeIo,
+                             hipStream_t s) {
+    const char* const what = "aniso_block_op_f32_dev";
+    if (which < 0 || which > 2) throw std::invalid_argument("block operator: which must be 0, 1 or 2");
+    blockOpF32Refuse(what);
+    blockOpF32Ready(what);
+    if (ldx < geo.N || ldo < geo.N) throw std::invalid_argument("block apply: leading dimension too small");
+    cacheF32();  // the float mirrors, if this is their first use: before anything is launched
+    blockOpDev(which, x, ldx, out, ldo, treeIo, s, NAN, nullptr, 0, nullptr, nullptr, ApplyPrec::F32);
 }
 
 void Operator::blockOp(int which, const double* x, int64_t ldx, double* out, int64_t ldo, bool treeIo, hipStream_t s,

@@ -76,6 +76,11 @@ struct ExchangeForm {
     bool issued = false;
 };
 
+// The precision of an apply's M2L and near field on a high-order handle (an argument of
+// modeApplyDev and a member of ApplyCall, not Operator state): F32 runs mode_apply_f32.hip
+// (one mode) or block_f32.hip (the block operator) on the float mirrors.
+enum class ApplyPrec { F64, F32 };
+
 // Everything about one applyBlock call that is not the operator's state (default: a
 // whole apply, no pass, no exchange).
 struct ApplyCall {
@@ -99,6 +104,9 @@ struct ApplyCall {
     // the apply of a sharded high-order matvec (blockOpShardedHigh, blockOpDev in tree order):
     // the only applies a handle made by createSharded at np = 6, 8 runs
     bool hoShard = false;
+    // F32: the M2L and the unstaged near field of a high-order handle on the float mirrors
+    // (blockOpF32Dev and the relaxed block solve; the caller has built the mirrors)
+    ApplyPrec prec = ApplyPrec::F64;
     ExchangeForm exch;
 };
 
@@ -111,9 +119,6 @@ struct InRows {
     bool tree;
     const double* sigT;
 };
-// The precision of a mode apply's M2L and near field on a high-order handle (an argument of
-// modeApplyDev, not Operator state): F32 runs mode_apply_f32.hip on the float mirrors.
-enum class ApplyPrec { F64, F32 };
 struct OutRows {
     double* out;
     const double* minuend;
@@ -231,7 +236,17 @@ public:
     // sigma_s when given (NaN / nullptr: the handle's).
     void blockOpDev(int which, const double* x, int64_t ldx, double* out, int64_t ldo, bool tree, hipStream_t s,
                     double gval = NAN, const double* sigT = nullptr, int phase = 0, double* rootsSend = nullptr,
-                    const double* rootsRecv = nullptr);
+                    const double* rootsRecv = nullptr, ApplyPrec prec = ApplyPrec::F64);
+    // The relaxed-precision block operator of a high-order handle (np = 6, 8, ks <= 8;
+    // block_f32.hip): blockOpDev with the M2L and the unstaged near field in
+    // fp32 on the float mirrors (built on first use), doubles in and out; everything around
+    // the two kernels, the minuend of which = 2 included, is the fp64 code.
+    // blockOpF32Refuse raises (ANISO_ERR_STATE) what the handle itself rules out -- np = 4, a
+    // sharded handle, ks > 8 -- and blockOpF32Ready a call before the coefficients and the
+    // caches; neither touches the device.
+    void blockOpF32Refuse(const char* what) const;
+    void blockOpF32Ready(const char* what) const;
+    void blockOpF32Dev(int which, const double* x, int64_t ldx, double* out, int64_t ldo, bool tree, hipStream_t s);
     // host-pointer block operator (aniso.m:121-157): u and out hold nb = ks blocks of
     // N points each (block b at b * N, original order); sigmaS (N, or nullptr: the
     // handle's sigma_s) and gval (NaN: the handle's g) as aniso.m's mforward reads them
@@ -292,6 +307,21 @@ public:
     // ks stacked blocks (original order, block b at b * N); device / host pointers
     int blockSolveDev(const double* rhs, double* x, int restart, double tol, int maxit, double* hist, int maxhist,
                       double* relres, hipStream_t s);
+    // blockSolveDev as inexact (relaxed) GMRES: the matvec of V[j] runs on
+    // the f32 block operator iff the latest relative residual estimate the host holds when it
+    // enqueues that matvec is <= relax (a cycle's start: its explicit relres; a look-ahead
+    // matvec: the estimate of the step before).  Every cycle-boundary residual is fp64, so
+    // convergence is blockSolveDev's.  relax = 0: blockSolveDev's launches and bits, no
+    // mirrors; relax < 0: the default kRelaxFactor x tol.  Arguments are checked before the
+    // handle's state, and every buffer (the mirrors included) is allocated before the first
+    // launch.  blockSolveRelaxedCalls: the precision (64 / 32) of every operator pass of the
+    // last relaxed solve, in order.
+    static constexpr double kRelaxFactor = 1e6;
+    int blockSolveRelaxedDev(const double* rhs, double* x, int restart, double tol, int maxit, double relax,
+                             double* hist, int maxhist, double* relres, hipStream_t s);
+    int blockSolveRelaxedHost(const double* rhs, double* x, int restart, double tol, int maxit, double relax,
+                              double* hist, int maxhist, double* relres);
+    const std::vector<int>& blockSolveRelaxedCalls() const { return relaxedCalls; }
     int solve16Mixed(const double* B, int64_t ldb, double* X, int64_t ldx, int m, double tol, double innerTol,
                      int maxOuter, int maxCycles, int* outer, double* rel, hipStream_t s);
     // the same for nrhs >= 1 rows in groups of 16 and a restart up to 400 (main.cpp:141's
@@ -581,6 +611,7 @@ private:
     }
     void prepareCharges(int K, const InRows& in, double* fT, double* cT, hipStream_t s);
     void nearUnstaged(int K, const HarmWeights& hw, const HarmWindow* win, int mask, const OutRows& o, hipStream_t s);
+    void nearUnstagedF32(int K, const HarmWeights& hw, const OutRows& o, hipStream_t s);
     void nearMode(int K, int id, const OutRows& o, hipStream_t s, ApplyPrec prec = ApplyPrec::F64);
     // a 16-column chunk's near field on the resident near blocks: columns 0 .. KA-1 from
     // dFT to oA, 8 .. 8+KB-1 from dFT2 to oB, one launch
@@ -709,6 +740,10 @@ private:
     std::vector<int> solveCalls;
     std::vector<std::pair<int, int>> mixedCalls;  // forwardSolveMixedCalls()
     std::vector<int> modeCalls;  // modeApplyCalls()
+    std::vector<int> relaxedCalls;  // blockSolveRelaxedCalls()
+    // blockSolveDev's body; relax > 0: the relaxed rule, rec: where every pass is recorded
+    int blockSolveRun(const double* rhs, double* x, int restart, double tol, int maxit, double relax,
+                      std::vector<int>* rec, double* hist, int maxhist, double* relres, hipStream_t s);
     std::vector<std::pair<int, int>> nearCalls;  // modeNearCalls()
     void arnoldiParts(int rows);  // dKryPart for sweeps of `rows` rows
     bool topTraceOn = false;

@@ -566,6 +566,16 @@ int aniso_block_op_dev(aniso_handle h, int which, const double* x, int64_t ldx, 
     });
 }
 
+int aniso_block_op_f32_dev(aniso_handle h, int which, const double* x, int64_t ldx, double* out, int64_t ldo, int tree,
+                           void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(x);
+        CHECK_PTR(out);
+        get(h).blockOpF32Dev(which, x, ldx, out, ldo, tree != 0, (hipStream_t)stream);
+    });
+}
+
 int aniso_block_op_begin_dev(aniso_handle h, int which, const double* x, int64_t ldx, double* out, int64_t ldo,
                              double* roots_send, void* stream) {
     ENTER(h);
@@ -688,6 +698,41 @@ int aniso_block_solve_dev(aniso_handle h, const double* rhs, double* x, int rest
         hipStream_t s = (hipStream_t)stream;
         const int it = op.blockSolveDev(rhs, x, restart, tol, maxit, hist, hist ? maxhist : 0, relres, s);
         if (iters) *iters = it;
+    });
+}
+
+int aniso_block_solve_relaxed(aniso_handle h, const double* rhs, double* x, int restart, double tol, int maxit,
+                              double relax, double* hist, int maxhist, int* iters, double* relres) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(rhs);
+        CHECK_PTR(x);
+        const int it =
+            get(h).blockSolveRelaxedHost(rhs, x, restart, tol, maxit, relax, hist, hist ? maxhist : 0, relres);
+        if (iters) *iters = it;
+    });
+}
+
+int aniso_block_solve_relaxed_dev(aniso_handle h, const double* rhs, double* x, int restart, double tol, int maxit,
+                                  double relax, double* hist, int maxhist, int* iters, double* relres, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(rhs);
+        CHECK_PTR(x);
+        const int it = get(h).blockSolveRelaxedDev(rhs, x, restart, tol, maxit, relax, hist, hist ? maxhist : 0, relres,
+                                                   (hipStream_t)stream);
+        if (iters) *iters = it;
+    });
+}
+
+int aniso_block_solve_relaxed_calls(aniso_handle h, int* calls, int cap, int* n) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(n);
+        const auto& c = get(h).blockSolveRelaxedCalls();
+        *n = (int)c.size();
+        if (calls)
+            for (int i = 0; i < cap && i < (int)c.size(); ++i) calls[i] = c[i];
     });
 }
 

@@ -92,6 +92,11 @@ struct GmresSystem {
     // after the host has waited for the status.  true: what it waited for ran on an invalid
     // fused launch and was recovered (recoverTopTimeout); a solve that cannot recover throws
     std::function<bool()> spoiled;
+    // the relaxed solve: w = A~ v on the reduced-precision operator, taken
+    // for the Arnoldi matvec of V[j] iff the latest relative residual estimate the host holds
+    // when it enqueues it is <= relax.  None (the sharded and the plain solves): matvec always.
+    std::function<void(const double*)> matvecLow = nullptr;
+    double relax = 0.0;
 };
 
 // One group's buffers of the lockstep multi-column solves (colsSolveGroup) at row length L,

@@ -156,4 +156,36 @@ __device__ __forceinline__ void hm_rows_src(double e, double dx, double dy2, con
     }
 }
 
+// ---- the fp32 entry of the relaxed-precision block operator (block_f32.hip)
+
+// 1/sqrt(x) in fp32: v_rsq_f32 (1 ulp) and one Newton step
+__device__ __forceinline__ float rsqrt_nr_f32(float x) {
+    const float y = __builtin_amdgcn_rsqf(x);
+    return y * __builtin_fmaf(-0.5f * x * y, y, 1.5f);
+}
+
+// hm_rows_win at i0 = b0 = 0 with one row, operation by operation, in fp32: the whole
+// operator of at most kMaxRhs blocks.  guard0: r = 0 is the point itself, where E = 0; the
+// floor keeps 1 / r finite in fp32's range (1e-30 is a separation of 1e-15, below any two
+// points).
+template <int K, bool guard0>
+__device__ __forceinline__ void hm_entry_f32(float e, float dx, float dy2, const float (&xw)[K], float (&o)[K]) {
+    static_assert(K >= 2, "at least T_0 and T_1");
+    float r2 = __builtin_fmaf(dx, dx, dy2);
+    if constexpr (guard0) r2 = __builtin_fmaxf(r2, 1e-30f);
+    const float ri = rsqrt_nr_f32(r2);
+    const float c = dx * ri, c2 = c + c, er = e * ri;
+    float T[K];
+    T[0] = 1.0f;
+    T[1] = c;
+#pragma unroll
+    for (int i = 2; i < K; ++i) T[i] = __builtin_fmaf(c2, T[i - 1], -T[i - 2]);
+    float v = __builtin_fmaf(T[1], xw[1], xw[0]);
+#pragma unroll
+    for (int b = 2; b < K; ++b) v = __builtin_fmaf(T[b], xw[b], v);
+    v *= er;  // (E / r) V
+#pragma unroll
+    for (int i = 0; i < K; ++i) o[i] = __builtin_fmaf(T[i], v, o[i]);
+}
+
 }  // namespace aniso

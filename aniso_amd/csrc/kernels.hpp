@@ -473,6 +473,17 @@ void launch_near_mode_f32(int K, int id, int nl, int maxLeaf, const int4* leafIn
 void launch_ho_m2l_mode_f32(int np, int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
                             const int* blk, const float* E, const double* ncx, const double* ncy, const double* nrx,
                             const double* nry, const HoTables* T, const double* mult, double* local, hipStream_t s);
+// The relaxed-precision block operator of a high-order handle (block_f32.hip, DESIGN.md
+// §3.18.8): launch_near_hm's unstaged kernel (whole operator, near field on) and
+// launch_ho_m2l (no window) on the same mirrors, the entry of all K modes in fp32.
+void launch_near_hm_f32(int K, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
+                        const int* nearPts, const int64_t* nearKOff, const float* E, const double* ncx,
+                        const double* ncy, const double* pxT, const double* pyT, const double* sigDiag,
+                        const HarmWeights& hw, const double* fT, const int* operm, int64_t obase, int64_t ldo,
+                        double scale, double* out, hipStream_t s);
+void launch_ho_m2l_f32(int np, int K, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk,
+                       const float* E, const double* ncx, const double* ncy, const double* nrx, const double* nry,
+                       const HoTables* T, const HarmWeights& hw, const double* mult, double* local, hipStream_t s);
 // launch_m2l_hm for mode id on a rank-16 (np = 4) handle: mult [node][16][K] as the up tiers
 // leave it, local = the plain sums of every listed target (the down tiers read them as they
 // are); ntgt = 0 launches nothing.  A column's bits do not depend on K or on its slot.

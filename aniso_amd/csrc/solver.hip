@@ -612,20 +612,27 @@ int Operator::gmresRestarted(const GmresSystem& g, StatusBlock& hs, double tol, 
     double relres = residual();
     bool conv = relres <= tol;
     LookAhead la;
+    // the relaxed rule: `est` is the latest estimate the host holds (a residual is never relaxed)
+    double est = relres;
+    auto arnoldiMatvec = [&](const double* v) {
+        if (g.matvecLow && g.relax > 0.0 && est <= g.relax) g.matvecLow(v);
+        else g.matvec(v);
+    };
     for (int cyc = 0; cyc < maxit && !conv; ++cyc) {
         if (hs.p[1] == 0.0) break;  // |r| = 0 in floating point
         int used = 0;
         bool ahead = false;  // the matvec of V[j] is already enqueued
         la.clear();
+        est = relres;  // the cycle's explicit relres
         for (int j = 0; j < m; ++j) {
-            if (!ahead) g.matvec(V + (size_t)j * L);
+            if (!ahead) arnoldiMatvec(V + (size_t)j * L);
             g.step(j);
             hs.post(s);
             // the next step's matvec before the host reads the status, unless this step is
             // predicted to converge (LookAhead); sharded, every rank holds the same
             // estimates: all ranks enqueue it, or none
             ahead = j + 1 < m && !la.near(tol);
-            if (ahead) g.matvec(V + (size_t)(j + 1) * L);
+            if (ahead) arnoldiMatvec(V + (size_t)(j + 1) * L);
             hs.wait();
             if (g.spoiled()) {
                 // this step's matvec (or the look-ahead one) ran on an invalid fused launch:
@@ -640,6 +647,7 @@ int Operator::gmresRestarted(const GmresSystem& g, StatusBlock& hs, double tol, 
             ++total;
             used = j + 1;
             relres = rel;
+            est = rel;
             la.push(rel);
             if (hist && nh < maxhist) hist[nh++] = rel;
             if (rel <= tol || rnext == 0.0) break;  // converged (estimate) or lucky breakdown
@@ -666,6 +674,48 @@ int Operator::gmresRestarted(const GmresSystem& g, StatusBlock& hs, double tol, 
 // hist gets the relative residual estimate after every step.
 int Operator::blockSolveDev(const double* rhs, double* x, int restart, double tol, int maxit, double* hist,
                             int maxhist, double* relresOut, hipStream_t s) {
+    return blockSolveRun(rhs, x, restart, tol, maxit, 0.0, nullptr, hist, maxhist, relresOut, s);
+}
+
+// The relaxed solve.  What the handle rules out first (np = 4, a shard,
+// ks > 8), then the arguments, then the state: nothing of this touches the device.
+int Operator::blockSolveRelaxedDev(const double* rhs, double* x, int restart, double tol, int maxit, double relax,
+                                   double* hist, int maxhist, double* relresOut, hipStream_t s) {
+    const char* const what = "aniso_block_solve_relaxed_dev";
+    blockOpF32Refuse(what);
+    if (restart < 1 || maxit < 1 || !(tol > 0.0))
+        throw std::invalid_argument(std::string(what) + " needs restart >= 1, maxit >= 1, tol > 0");
+    if (std::isnan(relax)) throw std::invalid_argument(std::string(what) + ": relax is NaN");
+    blockOpF32Ready(what);
+    if (relax < 0.0) relax = kRelaxFactor * tol;
+    relaxedCalls.clear();
+    return blockSolveRun(rhs, x, restart, tol, maxit, relax, &relaxedCalls, hist, maxhist, relresOut, s);
+}
+
+int Operator::blockSolveRelaxedHost(const double* rhs, double* x, int restart, double tol, int maxit, double relax,
+                                    double* hist, int maxhist, double* relres) {
+    const char* const what = "aniso_block_solve_relaxed";
+    blockOpF32Refuse(what);
+    if (restart < 1 || maxit < 1 || !(tol > 0.0))
+        throw std::invalid_argument(std::string(what) + " needs restart >= 1, maxit >= 1, tol > 0");
+    if (std::isnan(relax)) throw std::invalid_argument(std::string(what) + ": relax is NaN");
+    blockOpF32Ready(what);
+    ensureDevice();
+    const size_t bytes = (size_t)ks * geo.N * sizeof(double);
+    DevBuf db, dx;
+    db.alloc(bytes);
+    dx.alloc(bytes);
+    HIP_CHECK(hipMemcpyAsync(db.p, rhs, bytes, hipMemcpyHostToDevice, own));
+    HIP_CHECK(hipMemcpyAsync(dx.p, x, bytes, hipMemcpyHostToDevice, own));
+    const int it = blockSolveRelaxedDev(db.as<double>(), dx.as<double>(), restart, tol, maxit, relax, hist, maxhist,
+                                        relres, own);
+    HIP_CHECK(hipMemcpyAsync(x, dx.p, bytes, hipMemcpyDeviceToHost, own));
+    HIP_CHECK(hipStreamSynchronize(own));
+    return it;
+}
+
+int Operator::blockSolveRun(const double* rhs, double* x, int restart, double tol, int maxit, double relax,
+                            std::vector<int>* rec, double* hist, int maxhist, double* relresOut, hipStream_t s) {
     refuseHoShard("aniso_block_solve");
     checkBlockLimit(false);
     if (plan.nranks != 1) throw std::logic_error("block solve on a sharded handle");
@@ -681,12 +731,30 @@ int Operator::blockSolveDev(const double* rhs, double* x, int restart, double to
     const int m = restart;
     const arn::Layout lay(m);
     DevBuf bB, bX, bW, bV, bSt;
-    bB.alloc(L * sizeof(double));
-    bX.alloc(L * sizeof(double));
-    bW.alloc(L * sizeof(double));
-    bV.alloc((size_t)(m + 1) * L * sizeof(double));
-    bSt.alloc((size_t)lay.total * sizeof(double));
-    arnoldiParts(m + 2);
+    auto allocAll = [&] {
+        bB.alloc(L * sizeof(double));
+        bX.alloc(L * sizeof(double));
+        bW.alloc(L * sizeof(double));
+        bV.alloc((size_t)(m + 1) * L * sizeof(double));
+        bSt.alloc((size_t)lay.total * sizeof(double));
+        arnoldiParts(m + 2);
+    };
+    if (relax > 0.0) {
+        // the relaxed solve: every buffer, then the float mirrors (their own message), before
+        // the first launch
+        try {
+            allocAll();
+        } catch (const std::exception& e) {
+            throw std::runtime_error("relaxed block solve: the Krylov basis of (restart + 1) x ks x N = " +
+                                     std::to_string(m + 1) + " x " + std::to_string(ks) + " x " + std::to_string(N) +
+                                     " doubles (" + std::to_string((size_t)(m + 1) * L * sizeof(double)) +
+                                     " bytes) and 3 x " + std::to_string(L * sizeof(double)) +
+                                     " bytes of work vectors could not be allocated: " + e.what());
+        }
+        cacheF32();
+    } else {
+        allocAll();
+    }
     double *b = bB.as<double>(), *xt = bX.as<double>(), *w = bW.as<double>();
     double* V = bV.as<double>();
     double* st = bSt.as<double>();
@@ -713,7 +781,17 @@ int Operator::blockSolveDev(const double* rhs, double* x, int restart, double to
     g.normb = std::sqrt(sumsq(b));
     // A 0 = 0: a zero initial guess needs no matvec for its residual
     g.xZero = g.normb > 0.0 && sumsq(xt) == 0.0;
-    g.matvec = [&](const double* v) { blockOpDev(2, v, N, w, N, true, s); };
+    g.matvec = [&](const double* v) {
+        blockOpDev(2, v, N, w, N, true, s);
+        if (rec) rec->push_back(64);
+    };
+    if (relax > 0.0) {
+        g.relax = relax;
+        g.matvecLow = [&](const double* v) {
+            blockOpDev(2, v, N, w, N, true, s, NAN, nullptr, 0, nullptr, nullptr, ApplyPrec::F32);
+            if (rec) rec->push_back(32);
+        };
+    }
     g.startCycle = [&] { arnoldiBegin(L, m, V, L, st, nullptr, g.normb, stat, s); };
     g.step = [&](int j) { arnoldiStep(L, m, j, V, L, w, st, stat, s); };
     g.spoiled = [&] { return recoverTopTimeout(s); };

@@ -173,6 +173,11 @@ int aniso_mode_near_calls(aniso_handle h, int *cols, int *resident, int cap, int
  * each, precision 64 (the right-hand sides, the first residual, one residual pass per
  * refinement over the columns still active) or 32 (the inner solves' passes).  Host only. */
 int aniso_forward_solve_mixed_calls(aniso_handle h, int *calls, int cap, int *n);
+/* ---- the relaxed block solve ---- */
+/* every operator pass of the handle's last aniso_block_solve_relaxed(_dev) call, in order:
+ * *n = their number, calls (cap >= 0 entries, may be NULL) = the precision of each, 64 (the
+ * cycle-boundary residuals and the Arnoldi matvecs before the switch) or 32.  Host only. */
+int aniso_block_solve_relaxed_calls(aniso_handle h, int *calls, int cap, int *n);
 
 #ifdef __cplusplus
 }
