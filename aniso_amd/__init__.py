@@ -91,6 +91,8 @@ def lib():
             "aniso_cache_mode_near": [P, I],
             "aniso_cache_mode_near_bytes": [P, lp],
             "aniso_cache_mode_near_free": [P, I],
+            "aniso_set_wide": [P, I],
+            "aniso_get_wide": [P, ip],
             "aniso_cache_f32": [P],
             "aniso_cache_f32_bytes": [P, lp],
             "aniso_mapping_multi_f32_dev": [P, I, I, P, I64, P, I64, P],
@@ -420,7 +422,7 @@ class Aniso:
     def forward_solve_multi_dev(self, Q, X, restart=80, tol=1e-12, maxit=5, rhs_is_source=True, stream=None):
         """main.cpp:121-141 for several sources (aniso_forward_solve_multi_dev): solves
         u_k - K_0(sigma_s .* u_k) = b_k, b_k = K_0 Q[k] (rhs_is_source) or Q[k], every column a
-        restarted GMRES(restart) of its own, 8 columns per operator pass, on any handle
+        restarted GMRES(restart) of its own, 8 columns per operator pass (16 after set_wide), on any handle
         forward_multi_dev accepts.  Q and X are (nrhs, >= N) float64 CUDA tensors as
         mapping_multi_dev takes them; X holds the guess on entry and the solution on return.
         Returns (iters, relres, hist): the steps per column (negative: not converged), the
@@ -499,6 +501,22 @@ class Aniso:
     def cache_mode_near_free(self, id_=-1):
         """Drop mode id_'s resident near blocks; -1: every mode's."""
         _check(lib().aniso_cache_mode_near_free(self.address, int(id_)))
+
+    # ---- 16 columns per pass on a high-order handle (np = 6, 8)
+    def set_wide(self, on=True):
+        """The wide setting (aniso_set_wide), off by default.  On: mapping_multi(_dev) and
+        forward_multi_dev form one chunk of up to 16 columns whenever more than 8 remain, on
+        every mode, resident or not, and forward_solve_multi(_dev) runs lockstep groups of 16
+        (twice the Krylov bases of a group of 8).  Every column's result is what the setting
+        off gives it while nothing is resident.  Refused on np = 4 and on shards."""
+        _check(lib().aniso_set_wide(self.address, int(bool(on))))
+
+    @property
+    def wide(self):
+        """Whether the wide setting is on (aniso_get_wide)."""
+        v = ctypes.c_int()
+        _check(lib().aniso_get_wide(self.address, ctypes.byref(v)))
+        return bool(v.value)
 
     # ---- the reduced-precision route of a high-order handle (np = 6, 8)
     def cache_f32(self):
@@ -606,7 +624,8 @@ class Aniso:
         """The compiled column count K of every operator pass of the last mapping_multi(_dev) /
         forward_multi_dev call (after a forward_solve_multi(_dev): of its last operator call).
         The mode kernels (np = 6, 8, or a lean np = 4 mode) run chunks of up to 8 columns padded
-        to 2, 4, 5 or 8: 11 columns give [8, 4].  A resident np = 4 mode gives one entry per
+        to 2, 4, 5 or 8: 11 columns give [8, 4]; on np = 6, 8 after cache_mode or set_wide more than
+        8 remaining columns form one chunk reported as 16.  A resident np = 4 mode gives one entry per
         chunk of the block apply's batched branch (1, 2, 4, 5 or 8)."""
         n = ctypes.c_int()
         _check(lib().aniso_mode_apply_calls(self.address, None, 0, ctypes.byref(n)))

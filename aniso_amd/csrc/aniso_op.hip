@@ -688,6 +688,18 @@ void Operator::cacheF32() {
 
 // One mode's resident factor blocks: as many bytes as the E blocks, one
 // launch.  Everything that can be refused is refused before the device is touched.
+void Operator::setWide(int on) {
+    if (on != 0 && on != 1) throw std::invalid_argument("aniso_set_wide: on must be 0 or 1, got " + std::to_string(on));
+    if (on) {
+        if (!highOrder())
+            throw std::logic_error("aniso_set_wide: the 16-column chunks and solve groups are built for np = 6, 8; an "
+                                   "np = 4 handle keeps chunks and groups of 8");
+        refuseHoShard("aniso_set_wide");
+        if (plan.nranks > 1) throw std::logic_error("aniso_set_wide on a sharded handle (use an unsharded handle)");
+    }
+    wideOn = on != 0;
+}
+
 void Operator::cacheMode(int id) {
     if (id < 0 || id >= kernelSize)
         throw std::out_of_range("aniso_cache_mode: kernel id " + std::to_string(id) + " out of range [0, " +
@@ -1878,15 +1890,18 @@ void Operator::modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, 
     sp.total();
 }
 
-// A chunk of 9 .. 16 columns on a resident mode: each half runs modeApplyHigh's launches on
-// expansion buffers of its own (the charges dFT / dCT are re-used: the second half's are
-// formed after the first half's up pass has read them), around one M2L for all 16 columns.
-// With the mode's near blocks resident too (cacheModeNear) the near field is one launch for
-// all 16 columns as well, and the second half's charges live in dFT2 / dCT2.
+// A chunk of 9 .. 16 columns on a resident mode or with the wide setting on: each half runs
+// modeApplyHigh's launches on expansion buffers of its own (the charges dFT / dCT are re-used:
+// the second half's are formed after the first half's up pass has read them), around one M2L
+// for all 16 columns: the resident launch on the mode's stored blocks, otherwise the wide mode
+// kernel on the E blocks (one factor formation per entry).
+// With the mode's near blocks resident (cacheModeNear) the near field is one launch for all
+// 16 columns as well, whichever M2L runs, and the second half's charges live in dFT2 / dCT2.
 void Operator::modeApplyHigh16(int id, int K2, const InRows& inA, const OutRows& oA, const InRows& inB,
                                const OutRows& oB, hipStream_t s) {
     const double* F = modeResident(id);
-    if (!F) throw std::logic_error("a 16-column mode chunk without resident blocks");
+    if (!F && !wideOn)
+        throw std::logic_error("a 16-column mode chunk without resident blocks or the wide setting");
     const int KA = kMaxRhs;
     ensureWork(KA);
     hoReserve(KA, s);
@@ -1925,9 +1940,16 @@ void Operator::modeApplyHigh16(int id, int K2, const InRows& inA, const OutRows&
         }
     }
     sp.startRoofline();
-    launch_ho_m2l_resident(np, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
-                           dAttSrc.as<int>(), dAttBlk.as<int>(), F, dHoMult.as<double>(), KA, dHoMult2.as<double>(), K2,
-                           dHoLocal.as<double>(), dHoLocal2.as<double>(), s);
+    if (F)
+        launch_ho_m2l_resident(np, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
+                               dAttSrc.as<int>(), dAttBlk.as<int>(), F, dHoMult.as<double>(), KA, dHoMult2.as<double>(),
+                               K2, dHoLocal.as<double>(), dHoLocal2.as<double>(), s);
+    else
+        launch_ho_m2l_mode_wide(np, K2, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
+                                dAttSrc.as<int>(), dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(),
+                                dNcy.as<double>(), dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(),
+                                dHoMult.as<double>(), dHoMult2.as<double>(), dHoLocal.as<double>(),
+                                dHoLocal2.as<double>(), s);
     sp.end(2);
     hoDownPass(KA, dHoLocal.as<double>(), oA, s);
     hoDownPass(K2, dHoLocal2.as<double>(), oB, s);
@@ -2002,8 +2024,9 @@ void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, cons
             else modeApplyHigh(id, K, in, o, s, prec);
             modeCalls.push_back(K);
         };
-        // a resident high-order mode: more than 8 remaining columns form one chunk of up to 16
-        const bool wide = highOrder() && prec == ApplyPrec::F64 && modeResident(id);
+        // a resident high-order mode, or any with the wide setting on: more than 8 remaining
+        // columns form one chunk of up to 16
+        const bool wide = highOrder() && prec == ApplyPrec::F64 && (modeResident(id) || wideOn);
         for (int j0 = 0; j0 < nrhs;) {
             if (wide && nrhs - j0 > kMaxRhs) {
                 const int nb2 = std::min(kMaxRhs, nrhs - j0 - kMaxRhs);
@@ -2082,7 +2105,8 @@ void Operator::mappingMultiHost(const double* Q, int k, int id, double* Out) {
     if (!modeApplyCheck("aniso_mapping_multi", id, k, Q, geo.N, Out, geo.N, false)) return;
     ensureDevice();
     const int64_t N = geo.N;
-    const int kb = std::min(k, highOrder() && modeResident(id) ? 2 * kMaxRhs : kMaxRhs);  // (a resident mode's chunk)
+    // (a resident mode's chunk, or the wide setting's)
+    const int kb = std::min(k, highOrder() && (modeResident(id) || wideOn) ? 2 * kMaxRhs : kMaxRhs);
     DevBuf dq, dout;
     dq.alloc((size_t)kb * N * sizeof(double));
     dout.alloc((size_t)kb * N * sizeof(double));

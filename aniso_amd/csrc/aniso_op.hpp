@@ -166,12 +166,22 @@ public:
     // of the directed near E blocks, in 16-row tiles of 4 x 4 microtiles at Plan::nearFOff,
     // built in one launch.  While mode id is near-resident the fp64 mode applies run the MFMA
     // near field on them for a full 8-column chunk (2, 4 and 5 columns keep k_near_mode: no
-    // gain measured on mode 0), and a 16-column chunk (which exists only while the M2L blocks of
-    // cacheMode are resident too) runs one near launch for all its columns.  Independent of
+    // gain measured on mode 0), and a 16-column chunk (which exists while the M2L blocks of
+    // cacheMode are resident too, or with setWide(1)) runs one near launch for all its columns.  Independent of
     // the M2L blocks; same lifetime rules.  cacheModeNearBytes: their device bytes over all modes.
     void cacheModeNear(int id);
     void cacheModeNearFree(int id);
     int64_t cacheModeNearBytes() const;
+    // 16 columns per pass on an unsharded high-order handle, off by
+    // default.  On: the fp64 mode applies form one chunk of up to 16 columns whenever more
+    // than 8 remain, on every mode -- a mode without resident M2L blocks runs the wide mode
+    // kernel, one factor formation per entry for all 16 columns -- and the forward solve runs
+    // lockstep groups of 16.  The f32 entries, the mixed solve, the block operator and its
+    // solves are not affected.  A setting, not a cache: it survives setCoeff, cache rebuilds
+    // and the cacheMode*Free calls.  on = 1 is refused (logic_error) on np = 4 and on shards
+    // before the device is touched; on = 0 is accepted everywhere.
+    void setWide(int on);
+    bool wide() const { return wideOn; }
     void mappingHost(const double* charge, int id, double* out);
     void mappingBatchedHost(const double* Q, int k, int id, double* Out);  // N x k column-major
     // One mode on nrhs vectors wherever the mode is ready: rows of N
@@ -182,7 +192,9 @@ public:
     // through the mode kernels of mode_apply.hip on the mode-shared caches: the entry's
     // factor is formed once per chunk.  A mode made resident by cacheMode (fp64 only) runs
     // the MFMA M2L of mode_resident.hip in their place; more than 8 remaining columns then
-    // form one chunk of up to 16, two halves of the 8-column launches around one M2L.  np = 4: a resident mode runs applyBlock's identity
+    // form one chunk of up to 16, two halves of the 8-column launches around one M2L; with
+    // setWide(1) every mode forms such chunks, a mode without stored blocks around the wide mode
+    // M2L.  np = 4: a resident mode runs applyBlock's identity
     // mix in chunks of 8; a lean mode runs the same chunks through modeApplyLean16 (the
     // near-field mode kernel and the rank-16 mode M2L between the up and down tiers), one
     // read of the shared caches per chunk.  (A handle whose harmonic near field keeps
@@ -197,8 +209,8 @@ public:
     void modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, const double* sigT, bool minuend, double* out,
                       int64_t ldo, hipStream_t s, bool keepCalls = false, ApplyPrec prec = ApplyPrec::F64);
     // the compiled column count K of every operator pass of the last modeApplyDev /
-    // mappingMultiHost call, in order: a mode-kernel chunk (2, 4, 5 or 8), 16 for a resident
-    // high-order mode's chunk of more than 8 columns, a resident
+    // mappingMultiHost call, in order: a mode-kernel chunk (2, 4, 5 or 8), 16 for a high-order
+    // chunk of more than 8 columns (a resident mode's, or any mode's with setWide(1)), a resident
     // np = 4 mode's applyBlock chunk (1, 2, 4, 5 or 8), 8 for a per-column leanMapping pass
     const std::vector<int>& modeApplyCalls() const { return modeCalls; }
     // the near-field launches of the same call, in order: (columns: 2, 4, 5, 8, or 16 for the
@@ -343,8 +355,8 @@ public:
     // the multi-source forward solve (main.cpp:121-141 for nrhs sources):
     // u_k - K_0(sigma_s u_k) = b_k with b_k = K_0 q_k (rhsIsSource) or q_k, every column a
     // restarted GMRES of its own (blockSolveDev's semantics per column) over modeApplyDev,
-    // in groups of 8 columns that share one operator call per step on the rows still
-    // active.  q / x: device rows of N doubles in original order at strides ldq, ldx >= N;
+    // in groups of 8 columns (16 with the wide setting on) that share one operator call per
+    // step on the rows still active.  q / x: device rows of N doubles in original order at strides ldq, ldx >= N;
     // x: guess in, solution out.  iters / relres (nrhs entries) and hist (row k at k *
     // maxhist) are host arrays.  Every unsharded handle whose mode 0 is ready.  Returns the
     // steps of all columns.  forwardSolveMultiCheck raises everything that can be refused
@@ -655,6 +667,9 @@ private:
     }
     DevBuf dHoMult2, dHoLocal2;
     int hoWorkK2 = 0;
+    // setWide: every mode forms 16-column chunks, resident or not (the wide mode M2L measured
+    // shorter than two narrow launches at both orders)
+    bool wideOn = false;
     std::map<int, DevBuf> modeNearBlocks;  // cacheModeNear: resident near factor blocks per mode id
     const double* modeNearResident(int id) const {
         const auto it = modeNearBlocks.find(id);
@@ -723,7 +738,7 @@ private:
     int mixedGroupRun(const double* B, int64_t ldb, double* X, int64_t ldx, int nrows, int m, double tol,
                       double innerTol, int maxOuter, int maxCycles, int* outer, int* longest, double* rel,
                       hipStream_t s);
-    // One group of ng <= arn::kMaxCols independent columns of row length L in lockstep, the loop
+    // One group of ng <= cw.G (8 or 16) independent columns of row length L in lockstep, the loop
     // the forward solve and the multi-source block solve share: B holds the right-hand sides
     // (compact rows of L), x the guesses / solutions (rows at stride ldx), A(nrows, In, W) is one
     // operator call on nrows compact rows.  `what` names the solve in its error messages.

@@ -12,7 +12,8 @@
 namespace aniso {
 namespace arn {
 
-constexpr int kMaxCols = 8;  // slots per launch: one group of the solve
+constexpr int kMaxCols = 16;    // slots per launch: the widest group of a solve (the wide forward solve)
+constexpr int kNarrowCols = 8;  // a group of every other solve
 
 struct ColSlot {
     double* V;        // the column's basis (rows at the table's ldv)

@@ -329,6 +329,19 @@ int aniso_cache_mode_near_free(aniso_handle h, int id) {
     return guarded([&] { get(h).cacheModeNearFree(id); });
 }
 
+int aniso_set_wide(aniso_handle h, int on) {
+    ENTER(h);
+    return guarded([&] { get(h).setWide(on); });
+}
+
+int aniso_get_wide(aniso_handle h, int* on) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(on);
+        *on = get(h).wide() ? 1 : 0;
+    });
+}
+
 int aniso_mapping_multi_f32_dev(aniso_handle h, int id, int nrhs, const double* x, int64_t ldx, double* out,
                                 int64_t ldo, void* stream) {
     ENTER(h);

@@ -101,14 +101,16 @@ struct GmresSystem {
 
 // One group's buffers of the lockstep multi-column solves (colsSolveGroup) at row length L,
 // gmax columns and restart m; X (ownX): the guesses / solutions as compact rows where the
-// caller's are not.  hs: per column {estimate, r', steps, -}, then |b|^2 and |x|^2 per column.
+// caller's are not.  hs: per column {estimate, r', steps, -}, then |b|^2 and |x|^2 per column,
+// for G columns: the solve's group size (arn::kNarrowCols or arn::kMaxCols), gmax <= G.
 struct ColsWork {
     DevBuf V, B, In, W, X, st, part, dNb;
     StatusBlock hs;
+    int G = 0;
     // everything before anything is launched; a failure, of `more` (the caller's further
     // allocations) too, is raised as
     //   <head> doubles (<basis> bytes) and <rest> bytes of <tail> could not be allocated: <why>
-    void alloc(int64_t L, int gmax, int m, bool ownX, const std::string& head, const char* tail,
+    void alloc(int64_t L, int group, int gmax, int m, bool ownX, const std::string& head, const char* tail,
                const std::function<void()>& more = nullptr);
 };
 

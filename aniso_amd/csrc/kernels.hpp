@@ -435,6 +435,13 @@ void launch_near_mode(int K, int id, int nl, int maxLeaf, const int4* leafInfo, 
 void launch_ho_m2l_mode(int np, int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
                         const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
                         const double* nry, const HoTables* T, const double* mult, double* local, hipStream_t s);
+// the same for 8 + KB columns with one factor formation per entry:
+// columns 0 .. 7 from multA / to localA ([node][R][8]), 8 .. 8+KB-1 from multB / to localB
+// ([node][R][KB]), KB = 2, 4, 5 or 8; a column's bits are launch_ho_m2l_mode's
+void launch_ho_m2l_mode_wide(int np, int KB, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
+                             const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
+                             const double* nry, const HoTables* T, const double* multA, const double* multB,
+                             double* localA, double* localB, hipStream_t s);
 // The resident per-mode blocks of a high-order handle (mode_resident.hip):
 // F[pair] = (E / r) T_id(c) of every stored pair (owner / other: its target and source node),
 // R x R doubles per pair in 4 x 4 microtiles, and launch_ho_m2l_mode on them as an fp64 MFMA

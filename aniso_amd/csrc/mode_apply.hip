@@ -9,6 +9,7 @@
 // id -- is formed once and applied to the K columns with one FMA each.  There are no
 // harmonic weights: the staged multipole is the P2M's own and the stored local is the
 // plain sum, so P2M, M2M, L2L and L2P of high_order.hip run unchanged around the M2L.
+// k_ho_m2l_mode_wide forms it once for 16 columns in two expansion buffers.
 // A lean np = 4 handle runs the same near field and the rank-16 M2L k_m2l_mode16 between
 // the up and down tiers of apply.hip.
 // Every sum runs in a fixed order and there are no atomics: repeats are bitwise equal.
@@ -97,6 +98,102 @@ __global__ void __launch_bounds__(256) k_ho_m2l_mode(const int* __restrict__ tgt
 #pragma unroll
         for (int p = 1; p < NPH; ++p) v += TL[p * RK + i];
         local[(size_t)n * RK + i] = v;
+    }
+}
+
+// k_ho_m2l_mode for 8 + KB columns in two expansion buffers (the column convention of
+// k_ho_m2l_resident: columns 0 .. 7 in multA / localA as [node][R][8], columns 8 .. 8+KB-1
+// in multB / localB as [node][R][KB]).  The factor of an entry is
+// formed once and applied to all 8 + KB columns.  Thread shape, entry order (s = ph +
+// NPH g ascending within a pair, pairs in list order) and the phase-order sum are
+// k_ho_m2l_mode's, so a column's bits are what k_ho_m2l_mode<NP, 8> / <NP, KB> gives it.
+// The phases' partial rows go through the tile in two rounds, the first half's and then the
+// second's: the tile keeps its 8-column size.
+template <int NP, int KB>
+__global__ void __launch_bounds__(256) k_ho_m2l_mode_wide(const int* __restrict__ tgt, const int64_t* __restrict__ ptr,
+                                                          const int* __restrict__ src, const int* __restrict__ blk,
+                                                          const double* __restrict__ E, const double* __restrict__ ncx,
+                                                          const double* __restrict__ ncy, const double* __restrict__ nrx,
+                                                          const double* __restrict__ nry, const HoTables* __restrict__ T,
+                                                          int id, const double* __restrict__ multA,
+                                                          const double* __restrict__ multB, double* __restrict__ localA,
+                                                          double* __restrict__ localB) {
+    constexpr int KA = 8, R = NP * NP, RA = R * KA, RB = R * KB, NPH = 256 / R, NC = (R + NPH - 1) / NPH, LD = R + 1;
+    constexpr int G = NP == 8 ? 4 : 3;  // NC = 16 / 6
+    static_assert(NC % G == 0, "whole column groups");
+    static_assert(KB >= 1 && KB <= KA, "the second half is no wider than the first");
+    constexpr int TILE = R * LD > NPH * RA ? R * LD : NPH * RA;
+    __shared__ double XA[RA], XB[RB], SX[R], SY[R], TL[TILE];
+    const int tid = threadIdx.x, t = tid % R, ph = tid / R;
+    const bool active = ph < NPH;
+    const int n = tgt[blockIdx.x];
+    const double bx = ncx[n] + nrx[n] * T->cheb[t % NP];
+    const double by = ncy[n] + nry[n] * T->cheb[t / NP];
+    double accA[KA], accB[KB];
+#pragma unroll
+    for (int k = 0; k < KA; ++k) accA[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < KB; ++k) accB[k] = 0.0;
+    const int64_t p0 = ptr[blockIdx.x], p1 = ptr[blockIdx.x + 1];
+    for (int64_t e = p0; e < p1; ++e) {
+        const int B = src[e], b = blk[e];
+        const bool tr = b < 0;
+        const double* Eb = E + (size_t)(tr ? ~b : b) * (R * R);
+        __syncthreads();  // the previous pair's LDS reads are done
+        for (int i = tid; i < RA; i += 256) XA[i] = multA[(size_t)B * RA + i];
+        for (int i = tid; i < RB; i += 256) XB[i] = multB[(size_t)B * RB + i];
+        if (tid < R) {
+            SX[tid] = ncx[B] + nrx[B] * T->cheb[tid % NP];
+            SY[tid] = ncy[B] + nry[B] * T->cheb[tid / NP];
+        }
+        if (tr)
+            for (int i = tid; i < R * R; i += 256) TL[(i / R) * LD + (i % R)] = Eb[i];
+        __syncthreads();
+#pragma unroll 1
+        for (int g = 0; g < NC; g += G) {
+            double ev[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const int s = min(ph + NPH * (g + i), R - 1);  // clamped: a valid address, skipped below
+                ev[i] = tr ? TL[t * LD + s] : Eb[s * R + t];
+            }
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const int s = ph + NPH * (g + i);
+                if (active && s < R) {
+                    const double dy = SY[s] - by;
+                    const double f = mode_factor<false>(ev[i], SX[s] - bx, dy * dy, id);
+#pragma unroll
+                    for (int k = 0; k < KA; ++k) accA[k] = __builtin_fma(f, XA[s * KA + k], accA[k]);
+#pragma unroll
+                    for (int k = 0; k < KB; ++k) accB[k] = __builtin_fma(f, XB[s * KB + k], accB[k]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < KA; ++k) TL[(ph * R + t) * KA + k] = accA[k];
+    }
+    __syncthreads();
+    for (int i = tid; i < RA; i += 256) {
+        double v = TL[i];
+#pragma unroll
+        for (int p = 1; p < NPH; ++p) v += TL[p * RA + i];
+        localA[(size_t)n * RA + i] = v;
+    }
+    __syncthreads();  // the first half's partials are read
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < KB; ++k) TL[(ph * R + t) * KB + k] = accB[k];
+    }
+    __syncthreads();
+    for (int i = tid; i < RB; i += 256) {
+        double v = TL[i];
+#pragma unroll
+        for (int p = 1; p < NPH; ++p) v += TL[p * RB + i];
+        localB[(size_t)n * RB + i] = v;
     }
 }
 
@@ -384,6 +481,25 @@ void launch_ho_m2l_mode(int np, int K, int id, int ntgt, const int* tgt, const i
     } else if (np == 8) {
         ANISO_MODE_DISPATCH_K(K, (k_ho_m2l_mode<8, KK><<<ntgt, 256, 0, s>>>(tgt, ptr, src, blk, E, ncx, ncy, nrx, nry, T,
                                                                            id, mult, local)));
+    } else {
+        throw std::invalid_argument("mode apply: np must be 6 or 8");
+    }
+    HIP_LAUNCH_CHECK();
+}
+
+void launch_ho_m2l_mode_wide(int np, int KB, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
+                             const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
+                             const double* nry, const HoTables* T, const double* multA, const double* multB,
+                             double* localA, double* localB, hipStream_t s) {
+    if (ntgt <= 0) return;
+    if (id < 0) throw std::invalid_argument("mode apply: negative mode");
+    if (!multA || !multB || !localA || !localB) throw std::invalid_argument("wide mode apply: a NULL expansion buffer");
+    if (np == 6) {
+        ANISO_MODE_DISPATCH_K(KB, (k_ho_m2l_mode_wide<6, KK><<<ntgt, 256, 0, s>>>(
+                                      tgt, ptr, src, blk, E, ncx, ncy, nrx, nry, T, id, multA, multB, localA, localB)));
+    } else if (np == 8) {
+        ANISO_MODE_DISPATCH_K(KB, (k_ho_m2l_mode_wide<8, KK><<<ntgt, 256, 0, s>>>(
+                                      tgt, ptr, src, blk, E, ncx, ncy, nrx, nry, T, id, multA, multB, localA, localB)));
     } else {
         throw std::invalid_argument("mode apply: np must be 6 or 8");
     }

@@ -1257,8 +1257,8 @@ int Operator::mixedGroupRun(const double* B, int64_t ldb, double* X, int64_t ldx
 // whose mode 0 is ready -- np = 6, 8 and np = 4 lean or resident -- through modeApplyDev.
 // Each column is blockSolveDev's restarted GMRES (DCGS2 Arnoldi, arnoldi.hpp) with a
 // basis, a state block and a convergence of its own; the columns of a group of
-// arn::kMaxCols run in lockstep and share one operator call per step, on exactly the
-// rows still active.
+// arn::kNarrowCols (arn::kMaxCols with the wide setting on) run in
+// lockstep and share one operator call per step, on exactly the rows still active.
 
 // the GMRES parameters of the lockstep multi-column solves (w: the entry's name)
 static void checkColsSolveParams(const std::string& w, int restart, double tol, int maxit) {
@@ -1302,15 +1302,19 @@ int Operator::forwardSolveMultiDev(int nrhs, const double* q, int64_t ldq, bool 
         return 0;
     ensureDevice();
     checkDeviceErrors();
-    constexpr int G = arn::kMaxCols;
+    // the group size: 16 with the wide setting on (a step's live columns are one operator
+    // call: one wide chunk while more than 8 are live)
+    const int G = wideOn ? arn::kMaxCols : arn::kNarrowCols;
     const int64_t N = geo.N;
     const int m = restart, gmax = std::min(nrhs, G);
     const std::string g = std::to_string(gmax);
+    const std::string tail =
+        gmax > arn::kNarrowCols ? "work buffers (aniso_set_wide(h, 0) halves both: groups of 8)" : "work buffers";
     ColsWork cw;
-    cw.alloc(N, gmax, m, false,
+    cw.alloc(N, G, gmax, m, false,
              "forward solve: the Krylov bases of (restart + 1) x " + g + " x N = " + std::to_string(m + 1) + " x " + g +
                  " x " + std::to_string(N),
-             "work buffers");
+             tail.c_str());
     arn_small_kernel_attrs();
     solveCalls.clear();
     const double* sigS = sigmaSTree();
@@ -1339,8 +1343,10 @@ int Operator::forwardSolveMultiDev(int nrhs, const double* q, int64_t ldq, bool 
 }
 
 // one group's buffers at row length L (ColsWork, gmres_driver.hpp)
-void ColsWork::alloc(int64_t L, int gmax, int m, bool ownX, const std::string& head, const char* tail,
+void ColsWork::alloc(int64_t L, int group, int gmax, int m, bool ownX, const std::string& head, const char* tail,
                      const std::function<void()>& more) {
+    if (group < 1 || group > arn::kMaxCols || gmax > group)
+        throw std::logic_error("a solve group of " + std::to_string(gmax) + " of " + std::to_string(group) + " columns");
     const int64_t sts = arn::Layout(m).total, pc = (int64_t)(m + 2) * arn::kParts;
     const size_t row = (size_t)gmax * L * sizeof(double), basis = (size_t)(m + 1) * row;
     const size_t rest = (size_t)((ownX ? 4 : 3) * L + sts + pc + 1) * gmax * sizeof(double);
@@ -1358,14 +1364,18 @@ void ColsWork::alloc(int64_t L, int gmax, int m, bool ownX, const std::string& h
         throw std::runtime_error(head + " doubles (" + std::to_string(basis) + " bytes) and " + std::to_string(rest) +
                                  " bytes of " + tail + " could not be allocated: " + e.what());
     }
-    hs.alloc(6 * arn::kMaxCols);
+    hs.alloc(6 * group);
+    G = group;
 }
 
 // The lockstep loop of one group (ColsSolve) on the buffers cw: every column a restarted
 // GMRES of its own on vectors of cs.L doubles; cw.B holds the right-hand sides.
 int Operator::colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* x, int64_t ldx, int m, double tol,
                              int maxit, int* iters, double* relres, double* hist, int maxhist, hipStream_t s) {
-    constexpr int G = arn::kMaxCols;
+    const int G = cw.G;  // the group size: the status block's stride
+    if (ng > G)
+        throw std::logic_error(std::string(cs.what) + ": " + std::to_string(ng) + " columns in a group of " +
+                               std::to_string(G));
     const int64_t N = cs.L;  // the row length
     const std::string what(cs.what);
     const arn::Layout lay(m);
@@ -1379,7 +1389,7 @@ int Operator::colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* 
         int total = 0, used = 0, nh = 0;
         bool done = false, conv = false, frozen = false, xzero = false;
         double normb = 0.0, rel = 0.0, r = 0.0;
-    } col[G];
+    } col[arn::kMaxCols];
     auto slot = [&](int c) {
         arn::ColSlot sl{};
         sl.V = V + (size_t)c * vc;
@@ -1423,7 +1433,7 @@ int Operator::colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* 
         HIP_LAUNCH_CHECK();
         cw.hs.sync(s);
     }
-    double normbs[G] = {};
+    double normbs[arn::kMaxCols] = {};
     for (int c = 0; c < ng; ++c) {
         Col& k = col[c];
         k.normb = std::sqrt(hstat[4 * G + c]);
@@ -1570,7 +1580,7 @@ int Operator::forwardSolveMultiHost(const double* Q, int k, bool rhsIsSource, do
 }
 
 // ---- the multi-source forward solve in mixed precision: high-order
-// handles.  Per group of arn::kMaxCols columns an fp64 refinement loop around colsSolveGroup
+// handles.  Per group of arn::kNarrowCols columns an fp64 refinement loop around colsSolveGroup
 // over the f32 operator: the Krylov vectors stay double, only the operator is inexact.
 //   r = b - A x (fp64; a zero guess costs no pass); until every column is done:
 //     a column is converged at |r| <= tol |b| (what confirms a column of the fp64 solve);
@@ -1588,7 +1598,7 @@ int Operator::forwardSolveMultiMixedDev(int nrhs, const double* q, int64_t ldq, 
         return 0;
     ensureDevice();
     checkDeviceErrors();
-    constexpr int G = arn::kMaxCols;
+    constexpr int G = arn::kNarrowCols;  // (the f32 operator has no wide chunk: groups of 8 whatever the setting)
     const int64_t N = geo.N;
     const int m = restart, gmax = std::min(nrhs, G);
     const std::string g = std::to_string(gmax);
@@ -1596,7 +1606,7 @@ int Operator::forwardSolveMultiMixedDev(int nrhs, const double* q, int64_t ldq, 
     const unsigned nbp = std::min(nblk(N), 1024u);  // partial sums per norm
     ColsWork cw;
     DevBuf Bt, R, D, Xp, dPart, dNrm;  // the true right-hand sides, residuals, corrections, previous iterates
-    cw.alloc(N, gmax, m, false,
+    cw.alloc(N, G, gmax, m, false,
              "mixed forward solve: the Krylov bases of (restart + 1) x " + g + " x N = " + std::to_string(m + 1) +
                  " x " + g + " x " + std::to_string(N),
              ("work buffers and 4 x " + std::to_string(row) + " bytes of refinement vectors").c_str(), [&] {
@@ -1783,13 +1793,13 @@ int Operator::blockSolveMultiDev(int nsrc, const double* q, int64_t ldq, bool rh
     if (!blockSolveMultiCheck("aniso_block_solve_multi_dev", nsrc, q, ldq, x, ldx, iters, restart, tol, maxit)) return 0;
     ensureDevice();
     checkDeviceErrors();
-    constexpr int G = arn::kMaxCols;
+    constexpr int G = arn::kNarrowCols;
     static_assert(kBlockGroup <= G, "a group fits the column tables");
     const int64_t N = geo.N, L = (int64_t)ks * N;
     const int m = restart, gmax = std::min(nsrc, kBlockGroup);
     const std::string g = std::to_string(gmax);
     ColsWork cw;  // X: the group's guesses as compact vectors
-    cw.alloc(L, gmax, m, true,
+    cw.alloc(L, G, gmax, m, true,
              "multi-source block solve: the Krylov bases of (restart + 1) x " + g + " x ks x N = " +
                  std::to_string(m + 1) + " x " + g + " x " + std::to_string(ks) + " x " + std::to_string(N),
              "work rows", [&] {
