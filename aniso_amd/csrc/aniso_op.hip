@@ -451,8 +451,8 @@ void Operator::uploadPlan() {
         HIP_CHECK(hipMemset(dTopSteals.p, 0, sizeof(unsigned)));
         attReady = false;
         dropCacheF32();
-        modeBlocks.clear();
-        modeNearBlocks.clear();
+        modeBlocks.blocks.clear();
+        modeNearBlocks.blocks.clear();
     }
     up(dM2LCanonBase, plan.m2lCanonBase);
     up(dM2LInPtr, plan.m2lInPtr);
@@ -560,8 +560,8 @@ void Operator::setCoeff(const double* ss, const double* st) {
     for (auto& m : modes) m.tables = m.resident = false;
     attReady = false;
     dropCacheF32();    // the float mirrors are rounded from the shared caches of sigma_t
-    modeBlocks.clear();  // ... and the resident mode blocks are formed from them
-    modeNearBlocks.clear();
+    modeBlocks.blocks.clear();  // ... and the resident mode blocks are formed from them
+    modeNearBlocks.blocks.clear();
     f32Ready = false;  // config 5's fp32 caches are rounded from the mode-0 operators of sigma_t
     m64.clear();       // ... and the fp64 16-RHS caches are the modes' operators
     coeffSet = true;
@@ -597,11 +597,11 @@ void Operator::cache(int id) {
     int maxSrc = 1;
     for (size_t li = 0; li < plan.leaves.size(); ++li)
         maxSrc = std::max<int>(maxSrc, (int)(plan.nearPtr[li + 1] - plan.nearPtr[li]));
-    launch_cache_m2l(plan.storedM2L,dM2LPairTgt.as<int>(), dM2LSrc.as<int>(), dNcx.as<double>(), dNcy.as<double>(),
-                     dNrx.as<double>(), dNry.as<double>(), dStCoef.as<double>(), P, id, mc.Km2l.as<double>(), own);
+    launch_cache_m2l(plan.storedM2L, dM2LPairTgt.as<int>(), dM2LSrc.as<int>(), nodeBoxes(), dStCoef.as<double>(), P, id,
+                     mc.Km2l.as<double>(), own);
     launch_cache_near((int)plan.leaves.size(), dLeaves.as<int>(), dNearPtr.as<int64_t>(), dNearSrc.as<int>(),
-                      dNearKOff.as<int64_t>(), dBegin.as<int64_t>(), dCount.as<int64_t>(), dPxT.as<double>(),
-                      dPyT.as<double>(), dStCoef.as<double>(), P, id, maxSrc, mc.Knear.as<double>(), own);
+                      dNearKOff.as<int64_t>(), dBegin.as<int64_t>(), dCount.as<int64_t>(), treePoints(),
+                      dStCoef.as<double>(), P, id, maxSrc, mc.Knear.as<double>(), own);
     if (useAtt && !attReady) buildAttCache();
     CorrTables ct;
     ct.build(geo, id);
@@ -686,8 +686,6 @@ void Operator::cacheF32() {
     HIP_CHECK(hipStreamSynchronize(own));
 }
 
-// One mode's resident factor blocks: as many bytes as the E blocks, one
-// launch.  Everything that can be refused is refused before the device is touched.
 void Operator::setWide(int on) {
     if (on != 0 && on != 1) throw std::invalid_argument("aniso_set_wide: on must be 0 or 1, got " + std::to_string(on));
     if (on) {
@@ -700,111 +698,94 @@ void Operator::setWide(int on) {
     wideOn = on != 0;
 }
 
-void Operator::cacheMode(int id) {
+// One mode's resident factor blocks of either kind: one launch.
+// Everything that can be refused is refused before the device is touched.
+void ResidentBlocks::free(int id) {
+    if (blocks.empty() || (id >= 0 && !blocks.count(id))) return;
+    HIP_CHECK(hipDeviceSynchronize());  // queued applies (on the caller's streams too) may still read them
+    if (id < 0) blocks.clear();
+    else blocks.erase(id);
+}
+
+int64_t ResidentBlocks::bytes() const {
+    int64_t b = 0;
+    for (const auto& m : blocks) b += (int64_t)m.second.bytes;
+    return b;
+}
+
+void Operator::cacheResident(const char* api, const char* built, const char* noun, bool needDirected, int id,
+                             ResidentBlocks& rb, size_t need, const std::function<void(double*)>& build) {
+    const std::string a(api), what = a + ": the " + noun;
     if (id < 0 || id >= kernelSize)
-        throw std::out_of_range("aniso_cache_mode: kernel id " + std::to_string(id) + " out of range [0, " +
+        throw std::out_of_range(a + ": kernel id " + std::to_string(id) + " out of range [0, " +
                                 std::to_string(kernelSize) + ")");
     if (!highOrder())
-        throw std::logic_error("aniso_cache_mode: the resident mode blocks are built for np = 6, 8; the resident route "
-                               "of an np = 4 handle is aniso_cache(h, id)");
-    refuseHoShard("aniso_cache_mode");
-    if (plan.nranks > 1) throw std::logic_error("aniso_cache_mode on a sharded handle (use an unsharded handle)");
+        throw std::logic_error(a + ": the " + built + " are built for np = 6, 8; the resident route of an np = 4 handle "
+                                   "is aniso_cache(h, id)");
+    refuseHoShard(api);
+    if (plan.nranks > 1) throw std::logic_error(a + " on a sharded handle (use an unsharded handle)");
     if (!coeffSet || !attReady || !modes[id].tables)
-        throw std::runtime_error("aniso_cache_mode before aniso_set_coeff and aniso_cache(" + std::to_string(id) +
+        throw std::runtime_error(a + " before aniso_set_coeff and aniso_cache(" + std::to_string(id) +
                                  ") or aniso_cache_block");
-    if (modeBlocks.count(id)) return;
+    if (needDirected && (plan.nearSymHsOn || plan.nearPartTotal != 0))
+        throw std::logic_error(a + ": the near E blocks are not stored directed");
+    if (rb.blocks.count(id)) return;
     ensureDevice();
-    const size_t need = dAttM2L.bytes;
     size_t freeB = 0, totalB = 0;
     HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
     const std::string sizes = std::to_string(need) + " bytes for mode " + std::to_string(id) + ", " +
                               std::to_string(freeB) + " bytes of HBM free";
     if (need + (size_t)(1ull << 30) > freeB)  // keep a GiB of headroom
-        throw std::runtime_error("aniso_cache_mode: the resident blocks do not fit with a GiB to spare: " + sizes);
+        throw std::runtime_error(what + " do not fit with a GiB to spare: " + sizes);
     DevBuf F;
     try {
         F.alloc(need);
     } catch (const std::exception& e) {
-        throw std::runtime_error("aniso_cache_mode: the resident blocks could not be allocated: " + sizes + ": " + e.what());
+        throw std::runtime_error(what + " could not be allocated: " + sizes + ": " + e.what());
     }
-    const size_t rank = (size_t)np * np;
-    launch_ho_mode_blocks(np, id, (int64_t)(need / (rank * rank * sizeof(double))), dAttOwner.as<int>(),
-                          dAttOther.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(),
-                          dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(), F.as<double>(), own);
+    build(F.as<double>());
     HIP_CHECK(hipStreamSynchronize(own));
-    modeBlocks.emplace(id, std::move(F));
+    rb.blocks.emplace(id, std::move(F));
+}
+
+// (as many bytes as the E blocks: F_id of every stored pair)
+void Operator::cacheMode(int id) {
+    const size_t need = dAttM2L.bytes, rank = (size_t)np * np;
+    cacheResident("aniso_cache_mode", "resident mode blocks", "resident blocks", false, id, modeBlocks, need,
+                  [&](double* F) {
+                      launch_ho_mode_blocks(np, id, (int64_t)(need / (rank * rank * sizeof(double))), dAttOwner.as<int>(),
+                                            dAttOther.as<int>(), dAttM2L.as<double>(), nodeBoxes(),
+                                            dHoTab.as<HoTables>(), F, own);
+                  });
 }
 
 void Operator::cacheModeFree(int id) {
     if (id < -1 || id >= kernelSize)
         throw std::out_of_range("aniso_cache_mode_free: kernel id " + std::to_string(id) + " out of range [-1, " +
                                 std::to_string(kernelSize) + ")");
-    if (modeBlocks.empty() || (id >= 0 && !modeBlocks.count(id))) return;
-    HIP_CHECK(hipDeviceSynchronize());  // queued applies (on the caller's streams too) may still read them
-    if (id < 0) modeBlocks.clear();
-    else modeBlocks.erase(id);
+    modeBlocks.free(id);
 }
 
-int64_t Operator::cacheModeBytes() const {
-    int64_t b = 0;
-    for (const auto& m : modeBlocks) b += (int64_t)m.second.bytes;
-    return b;
-}
+int64_t Operator::cacheModeBytes() const { return modeBlocks.bytes(); }
 
 // One mode's resident near blocks: the directed near E blocks with the
-// sources of every leaf padded to 16, one launch.  cacheMode's checks, order and memory policy.
+// sources of every leaf padded to 16, one launch.
 void Operator::cacheModeNear(int id) {
-    if (id < 0 || id >= kernelSize)
-        throw std::out_of_range("aniso_cache_mode_near: kernel id " + std::to_string(id) + " out of range [0, " +
-                                std::to_string(kernelSize) + ")");
-    if (!highOrder())
-        throw std::logic_error("aniso_cache_mode_near: the resident near blocks are built for np = 6, 8; the resident "
-                               "route of an np = 4 handle is aniso_cache(h, id)");
-    refuseHoShard("aniso_cache_mode_near");
-    if (plan.nranks > 1) throw std::logic_error("aniso_cache_mode_near on a sharded handle (use an unsharded handle)");
-    if (!coeffSet || !attReady || !modes[id].tables)
-        throw std::runtime_error("aniso_cache_mode_near before aniso_set_coeff and aniso_cache(" + std::to_string(id) +
-                                 ") or aniso_cache_block");
-    if (plan.nearSymHsOn || plan.nearPartTotal != 0)
-        throw std::logic_error("aniso_cache_mode_near: the near E blocks are not stored directed");
-    if (modeNearBlocks.count(id)) return;
-    ensureDevice();
-    const size_t need = (size_t)plan.nearFTotal * sizeof(double);
-    size_t freeB = 0, totalB = 0;
-    HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
-    const std::string sizes = std::to_string(need) + " bytes for mode " + std::to_string(id) + ", " +
-                              std::to_string(freeB) + " bytes of HBM free";
-    if (need + (size_t)(1ull << 30) > freeB)  // keep a GiB of headroom
-        throw std::runtime_error("aniso_cache_mode_near: the resident near blocks do not fit with a GiB to spare: " + sizes);
-    DevBuf F;
-    try {
-        F.alloc(need);
-    } catch (const std::exception& e) {
-        throw std::runtime_error("aniso_cache_mode_near: the resident near blocks could not be allocated: " + sizes + ": " +
-                                 e.what());
-    }
-    launch_near_mode_blocks(id, (int)plan.leaves.size(), dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
-                            dNearPts.as<int>(), dNearKOff.as<int64_t>(), dNearFOff.as<int64_t>(), dAttNear.as<double>(),
-                            dPxT.as<double>(), dPyT.as<double>(), F.as<double>(), own);
-    HIP_CHECK(hipStreamSynchronize(own));
-    modeNearBlocks.emplace(id, std::move(F));
+    cacheResident("aniso_cache_mode_near", "resident near blocks", "resident near blocks", true, id, modeNearBlocks,
+                  (size_t)plan.nearFTotal * sizeof(double), [&](double* F) {
+                      launch_near_mode_blocks(id, nearList(), dNearFOff.as<int64_t>(), dAttNear.as<double>(),
+                                              treePoints(), F, own);
+                  });
 }
 
 void Operator::cacheModeNearFree(int id) {
     if (id < -1 || id >= kernelSize)
         throw std::out_of_range("aniso_cache_mode_near_free: kernel id " + std::to_string(id) + " out of range [-1, " +
                                 std::to_string(kernelSize) + ")");
-    if (modeNearBlocks.empty() || (id >= 0 && !modeNearBlocks.count(id))) return;
-    HIP_CHECK(hipDeviceSynchronize());  // queued applies (on the caller's streams too) may still read them
-    if (id < 0) modeNearBlocks.clear();
-    else modeNearBlocks.erase(id);
+    modeNearBlocks.free(id);
 }
 
-int64_t Operator::cacheModeNearBytes() const {
-    int64_t b = 0;
-    for (const auto& m : modeNearBlocks) b += (int64_t)m.second.bytes;
-    return b;
-}
+int64_t Operator::cacheModeNearBytes() const { return modeNearBlocks.bytes(); }
 
 void Operator::refuseHighOrder(const char* what) const {
     if (highOrder())
@@ -826,8 +807,8 @@ void Operator::needResident(int id, const char* what) const {
 // every point (the mode-0 diagonal).  Built once per setCoeff on a block handle.
 void Operator::buildAttCache() {
     dropCacheF32();
-    modeBlocks.clear();
-    modeNearBlocks.clear();
+    modeBlocks.blocks.clear();
+    modeNearBlocks.blocks.clear();
     const Params* P = dParams.as<Params>();
     const int64_t npairs = (int64_t)(plan.attOwner.size() + plan.hmCopyOwner.size());  // stored blocks + copies
     const size_t rank = (size_t)np * np;
@@ -841,16 +822,15 @@ void Operator::buildAttCache() {
     int maxSrc = 1;
     for (size_t li = 0; li < plan.leaves.size(); ++li) maxSrc = std::max<int>(maxSrc, (int)(nptr[li + 1] - nptr[li]));
     if (highOrder())
-        launch_ho_cache_att(np, npairs, dAttOwner.as<int>(), dAttOther.as<int>(), dNcx.as<double>(), dNcy.as<double>(),
-                            dNrx.as<double>(), dNry.as<double>(), dStCoef.as<double>(), P, dHoTab.as<HoTables>(),
-                            dAttM2L.as<double>(), own);
+        launch_ho_cache_att(np, npairs, dAttOwner.as<int>(), dAttOther.as<int>(), nodeBoxes(), dStCoef.as<double>(), P,
+                            dHoTab.as<HoTables>(), dAttM2L.as<double>(), own);
     else
-        launch_cache_att_m2l(npairs, dAttOwner.as<int>(), dAttOther.as<int>(), dNcx.as<double>(), dNcy.as<double>(),
-                             dNrx.as<double>(), dNry.as<double>(), dStCoef.as<double>(), P, dAttM2L.as<double>(), own);
+        launch_cache_att_m2l(npairs, dAttOwner.as<int>(), dAttOther.as<int>(), nodeBoxes(), dStCoef.as<double>(), P,
+                             dAttM2L.as<double>(), own);
     launch_cache_near((int)plan.leaves.size(), dLeaves.as<int>(), (hs ? dHsSrcPtr : dNearPtr).as<int64_t>(),
                       (hs ? dHsSrc : dNearSrc).as<int>(), (hs ? dHsKOff : dNearKOff).as<int64_t>(),
-                      dBegin.as<int64_t>(), dCount.as<int64_t>(), dPxT.as<double>(), dPyT.as<double>(),
-                      dStCoef.as<double>(), P, kAttMode, maxSrc, dAttNear.as<double>(), own);
+                      dBegin.as<int64_t>(), dCount.as<int64_t>(), treePoints(), dStCoef.as<double>(), P, kAttMode,
+                      maxSrc, dAttNear.as<double>(), own);
     launch_sigma_diag(geo.N, dPxT.as<double>(), dPyT.as<double>(), dStCoef.as<double>(), P, dSigDiag.as<double>(),
                       own);
     if (!highOrder()) {  // the deterministic sums' bound: rank 16 only
@@ -1210,53 +1190,41 @@ void Operator::prepareCharges(int K, const InRows& in, double* fT, double* cT, h
 
 void Operator::nearUnstaged(int K, const HarmWeights& hw, const HarmWindow* win, int mask, const OutRows& o,
                             hipStream_t s) {
-    launch_near_hm(K, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
-                   dNearPts.as<int>(), dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(),
-                   dPyT.as<double>(), dSigDiag.as<double>(), hw, dFT.as<double>(), o.perm, o.base, o.ld, mask, kScale,
-                   o.out, nullptr, nullptr, nullptr, 0, nullptr, nearWpe, s, nullptr, win);
+    launch_near_hm(K, nearList(), dAttNear.as<double>(), treePoints(), dSigDiag.as<double>(), hw, dFT.as<double>(), mask,
+                   kScale, o, nullptr, nullptr, nullptr, 0, nullptr, nearWpe, s, nullptr, win);
 }
 
 void Operator::nearUnstagedF32(int K, const HarmWeights& hw, const OutRows& o, hipStream_t s) {
-    launch_near_hm_f32(K, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
-                       dNearPts.as<int>(), dNearKOff.as<int64_t>(), dAttNearF.as<float>(), dNcx.as<double>(),
-                       dNcy.as<double>(), dPxT.as<double>(), dPyT.as<double>(), dSigDiag.as<double>(), hw,
-                       dFT.as<double>(), o.perm, o.base, o.ld, kScale, o.out, s);
+    launch_near_hm_f32(K, nearList(), dAttNearF.as<float>(), nodeBoxes(), treePoints(), dSigDiag.as<double>(), hw,
+                       dFT.as<double>(), kScale, o, s);
 }
 
 void Operator::nearMode(int K, int id, const OutRows& o, hipStream_t s, ApplyPrec prec) {
     if (prec == ApplyPrec::F32) {
-        launch_near_mode_f32(K, id, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(),
-                             dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(), dNearKOff.as<int64_t>(),
-                             dAttNearF.as<float>(), dNcx.as<double>(), dNcy.as<double>(), dPxT.as<double>(),
-                             dPyT.as<double>(), dSigDiag.as<double>(), dFT.as<double>(), o.perm, o.base, o.ld, kScale,
-                             o.out, s);
+        launch_near_mode_f32(K, id, nearList(), dAttNearF.as<float>(), nodeBoxes(), treePoints(), dSigDiag.as<double>(),
+                             dFT.as<double>(), kScale, o, s);
         nearCalls.emplace_back(K, 0);  // (the f32 entries ignore the resident near blocks)
         return;
     }
     // the stored near blocks serve the full chunk only: at 2, 4 and 5 columns k_near_mode's span
     // on mode 0 is as short or shorter at both orders (measured)
-    if (const double* F = K == kMaxRhs ? modeNearResident(id) : nullptr) {
-        launch_near_resident(id, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(),
-                             dNearPtsPtr.as<int64_t>(), dNearPts.as<int>(), dNearFOff.as<int64_t>(), F,
-                             dSigDiag.as<double>(), dFT.as<double>(), K, nullptr, 0, o.perm, o.base, kScale, o.out, o.ld,
-                             nullptr, 0, s);
+    if (const double* F = K == kMaxRhs ? modeNearBlocks.find(id) : nullptr) {
+        launch_near_resident(id, nearList(true), F, dSigDiag.as<double>(), dFT.as<double>(), K, nullptr, 0, kScale, o,
+                             OutRows{}, s);
         nearCalls.emplace_back(K, 1);
         return;
     }
-    launch_near_mode(K, id, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
-                     dNearPts.as<int>(), dNearKOff.as<int64_t>(), dAttNear.as<double>(), dPxT.as<double>(),
-                     dPyT.as<double>(), dSigDiag.as<double>(), dFT.as<double>(), o.perm, o.base, o.ld, kScale, o.out,
-                     s);
+    launch_near_mode(K, id, nearList(), dAttNear.as<double>(), treePoints(), dSigDiag.as<double>(), dFT.as<double>(),
+                     kScale, o, s);
     nearCalls.emplace_back(K, 0);
 }
 
-void Operator::nearMode16(int id, int KA, int KB, const OutRows& oA, const OutRows& oB, hipStream_t s) {
-    const double* F = modeNearResident(id);
-    if (!F || oA.perm != oB.perm || oA.base != oB.base)
+void Operator::nearMode16(int id, const ModeHalf& a, const ModeHalf& b, hipStream_t s) {
+    const double* F = modeNearBlocks.find(id);
+    if (!F || a.o.perm != b.o.perm || a.o.base != b.o.base)
         throw std::logic_error("a 16-column near launch without resident near blocks or with two output orders");
-    launch_near_resident(id, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
-                         dNearPts.as<int>(), dNearFOff.as<int64_t>(), F, dSigDiag.as<double>(), dFT.as<double>(), KA,
-                         dFT2.as<double>(), KB, oA.perm, oA.base, kScale, oA.out, oA.ld, oB.out, oB.ld, s);
+    launch_near_resident(id, nearList(true), F, dSigDiag.as<double>(), dFT.as<double>(), a.K, dFT2.as<double>(), b.K,
+                         kScale, a.o, b.o, s);
     nearCalls.emplace_back(2 * kMaxRhs, 1);
 }
 
@@ -1289,8 +1257,7 @@ void Operator::hoReserve(int K, hipStream_t s, bool second) {
 
 void Operator::hoUpPass(int K, const double* fT, double* mult, bool allLeaves, hipStream_t s) {
     const int nl = allLeaves ? hoLeafAll : (int)plan.leaves.size();
-    launch_ho_p2m(np, K, nl, (allLeaves ? dHoLeafAll : dLeafInfo).as<int4>(), dNcx.as<double>(), dNcy.as<double>(),
-                  dNrx.as<double>(), dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), fT,
+    launch_ho_p2m(np, K, nl, (allLeaves ? dHoLeafAll : dLeafInfo).as<int4>(), nodeBoxes(), treePoints(), fT,
                   dHoTab.as<HoTables>(), mult, s);
     for (size_t l = 0; l + 1 < hoM2mPtr.size(); ++l)
         launch_ho_m2m(np, K, hoM2mPtr[l + 1] - hoM2mPtr[l], dHoM2m.as<int>() + hoM2mPtr[l], dHoChild.as<int4>(),
@@ -1302,9 +1269,7 @@ void Operator::hoDownPass(int K, double* local, const OutRows& o, hipStream_t s)
     for (size_t l = 0; l + 1 < hoL2lPtr.size(); ++l)
         launch_ho_l2l(np, K, hoL2lPtr[l + 1] - hoL2lPtr[l], dHoL2l.as<int>() + hoL2lPtr[l], dParent.as<int>(),
                       dSlot.as<int>(), T, local, s);
-    launch_ho_l2p(np, K, (int)plan.leaves.size(), dLeafInfo.as<int4>(), dNcx.as<double>(), dNcy.as<double>(),
-                  dNrx.as<double>(), dNry.as<double>(), dPxT.as<double>(), dPyT.as<double>(), T, local, o.perm, o.base,
-                  o.ld, kScale, o.out, o.minuend, o.minuendLd, s);
+    launch_ho_l2p(np, K, (int)plan.leaves.size(), dLeafInfo.as<int4>(), nodeBoxes(), treePoints(), T, local, kScale, o, s);
 }
 
 // tier k: `list` (nullptr: every task of the tier) names ntask tasks; fT / cT (nullptr: none)
@@ -1515,6 +1480,9 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     const int64_t* const hmPtsPtr = (hsSym ? dHsPtsPtr : dNearPtsPtr).as<int64_t>();
     const int64_t* const hmKOff = (hsSym ? dHsKOff : dNearKOff).as<int64_t>();
     const uint16_t* const hmLoc = (hsSym ? dHsLoc : dNearLoc).as<uint16_t>();
+    NearList hmList = nearList();  // (symmetric U storage: its own column lists)
+    hmList.ptsPtr = hmPtsPtr;
+    hmList.off = hmKOff;
     // near field + corrections (they need only fT / cT, or with nearIn the input)
     auto nearStage = [&] {
         if (fork) HIP_CHECK(hipStreamWaitEvent(side, evFork, 0));
@@ -1523,11 +1491,9 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         if (harmonic) {
             // the corrections ride in the staged near kernel (d = 1, its table holds
             // every stencil neighbour; Plan::nearCorrRow)
-            corrFused = launch_near_hm(K, (int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), hmPtsPtr,
-                           dNearPts.as<int>(), hmKOff, dAttNear.as<double>(), dPxT.as<double>(), dPyT.as<double>(),
-                           dSigDiag.as<double>(), hw, dFT.as<double>(), o.perm, o.base, ldo, mask, kScale, out, hmLoc,
-                           dNsPtr.as<int64_t>(), dNsPts.as<int>(), plan.nsMax, plan.nearCorrOk ? &nc : nullptr,
-                           nearWpe, sn, &nin, win);
+            corrFused = launch_near_hm(K, hmList, dAttNear.as<double>(), treePoints(), dSigDiag.as<double>(), hw,
+                                       dFT.as<double>(), mask, kScale, o, hmLoc, dNsPtr.as<int64_t>(), dNsPts.as<int>(),
+                                       plan.nsMax, plan.nearCorrOk ? &nc : nullptr, nearWpe, sn, &nin, win);
         } else if (plan.nearPartTotal > 0) {
             // symmetric U storage (K = 1 handles): one launch per term; the transposed
             // products go to partials summed over the terms
@@ -1740,10 +1706,8 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         } else if (clustered) {
             m2lClusters(0, ncl, s);
         } else if (harmonic) {
-            launch_m2l_hm(K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
-                          dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(),
-                          dNrx.as<double>(), dNry.as<double>(), P, hw, dMult.as<double>(), dLocal.as<double>(), s,
-                          win);
+            launch_m2l_hm(K, pairList(), dAttM2L.as<double>(), nodeBoxes(), P, hw, dMult.as<double>(), dLocal.as<double>(),
+                          s, win);
         } else {
             launch_m2l(K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dM2LPtr.as<int64_t>(), dM2LNDir.as<int>(),
                        dM2LCanonBase.as<int>(), dM2LOutSlot.as<int>(), dM2LSrc.as<int>(), tab, nterm,
@@ -1802,15 +1766,11 @@ void Operator::applyBlockHigh(int K, const InRows& in, int nterm, const int* ids
     sp.end(1);
     sp.startRoofline();
     if (f32)
-        launch_ho_m2l_f32(np, K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
-                          dAttBlk.as<int>(), dAttM2LF.as<float>(), dNcx.as<double>(), dNcy.as<double>(),
-                          dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(), hw, dHoMult.as<double>(),
-                          dHoLocal.as<double>(), s);
+        launch_ho_m2l_f32(np, K, pairList(), dAttM2LF.as<float>(), nodeBoxes(), dHoTab.as<HoTables>(), hw,
+                          dHoMult.as<double>(), dHoLocal.as<double>(), s);
     else
-        launch_ho_m2l(np, K, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
-                      dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(),
-                      dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(), hw, win, dHoMult.as<double>(),
-                      dHoLocal.as<double>(), s);
+        launch_ho_m2l(np, K, pairList(), dAttM2L.as<double>(), nodeBoxes(), dHoTab.as<HoTables>(), hw, win,
+                      dHoMult.as<double>(), dHoLocal.as<double>(), s);
     sp.end(2);
     hoDownPass(K, dHoLocal.as<double>(), o, s);
     sp.end(5);
@@ -1852,107 +1812,67 @@ bool Operator::modeApplyCheck(const char* what, int id, int nrhs, const void* x,
     return true;
 }
 
-// One chunk on a high-order handle: applyBlockHigh's sequence with the mode kernels in
-// place of launch_near_hm and launch_ho_m2l, and the corrections of mode id (identity
-// fold; o.minuend: x - K_id(...)).  The expansions live in the block path's dHoMult / dHoLocal.
-void Operator::modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, hipStream_t s, ApplyPrec prec) {
-    const bool f32 = prec == ApplyPrec::F32;
-    const double* F = f32 ? nullptr : modeResident(id);  // (the f32 entries ignore the resident blocks)
-    ensureWork(K);
-    hoReserve(K, s);
-    const CorrFold& cf = corrTable(K, 1, &id, identityMix(K).data());
-    StageSpans sp(*this, s);
-    prepareCharges(K, in, dFT.as<double>(), dCT.as<double>(), s);
-    nearMode(K, id, o, s, prec);
-    sp.end(4);
-    corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
-    sp.end(6);
-    hoUpPass(K, dFT.as<double>(), dHoMult.as<double>(), false, s);
-    sp.end(1);
-    sp.startRoofline();
-    if (f32)
-        launch_ho_m2l_mode_f32(np, K, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
-                               dAttSrc.as<int>(), dAttBlk.as<int>(), dAttM2LF.as<float>(), dNcx.as<double>(),
-                               dNcy.as<double>(), dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(),
-                               dHoMult.as<double>(), dHoLocal.as<double>(), s);
-    else if (F)
-        launch_ho_m2l_resident(np, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
-                               dAttSrc.as<int>(), dAttBlk.as<int>(), F, dHoMult.as<double>(), K, nullptr, 0,
-                               dHoLocal.as<double>(), nullptr, s);
-    else
-        launch_ho_m2l_mode(np, K, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
-                           dAttSrc.as<int>(), dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(),
-                           dNcy.as<double>(), dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(),
-                           dHoMult.as<double>(), dHoLocal.as<double>(), s);
-    sp.end(2);
-    hoDownPass(K, dHoLocal.as<double>(), o, s);
-    sp.end(5);
-    sp.total();
-}
-
-// A chunk of 9 .. 16 columns on a resident mode or with the wide setting on: each half runs
-// modeApplyHigh's launches on expansion buffers of its own (the charges dFT / dCT are re-used:
-// the second half's are formed after the first half's up pass has read them), around one M2L
-// for all 16 columns: the resident launch on the mode's stored blocks, otherwise the wide mode
-// kernel on the E blocks (one factor formation per entry).
-// With the mode's near blocks resident (cacheModeNear) the near field is one launch for all
-// 16 columns as well, whichever M2L runs, and the second half's charges live in dFT2 / dCT2.
-void Operator::modeApplyHigh16(int id, int K2, const InRows& inA, const OutRows& oA, const InRows& inB,
-                               const OutRows& oB, hipStream_t s) {
-    const double* F = modeResident(id);
-    if (!F && !wideOn)
+// One chunk on a high-order handle: applyBlockHigh's sequence with the mode kernels in place of
+// launch_near_hm and launch_ho_m2l, and the corrections of mode id (identity fold; o.minuend:
+// x - K_id(...)), on one half of 2, 4, 5 or 8 columns or on an 8-column half and a second one
+// (a resident mode, or the wide setting) around ONE M2L for all their columns.  Half i has
+// expansion buffers of its own, the block path's dHoMult / dHoLocal and dHoMult2 / dHoLocal2.
+// The variation points:
+//   near field -- f32: launch_near_mode_f32 per half; two halves with the mode's near blocks
+//     resident: one launch for all 16 columns; otherwise nearMode per half;
+//   M2L -- f32: the f32 mode kernel (one half only); the mode's M2L blocks resident: the MFMA
+//     launch on them; two halves without them: the wide mode kernel on the E blocks (one factor
+//     formation per entry, §3.18.9); otherwise the mode kernel;
+//   order -- per half (charges, near field, corrections, up pass, then the next half: they share
+//     dFT / dCT, the second half's charges are formed after the first's up pass has read them), or
+//     per stage where the near launch is joint (the second half's charges live in dFT2 / dCT2;
+//     same stage ids, each stage once for both halves).
+void Operator::modeChunkHigh(int id, int nh, const ModeHalf* h, hipStream_t s, ApplyPrec prec) {
+    const bool f32 = prec == ApplyPrec::F32, two = nh == 2;
+    const double* F = f32 ? nullptr : modeBlocks.find(id);  // (the f32 entries ignore the resident blocks)
+    if (two && (f32 || (!F && !wideOn)))
         throw std::logic_error("a 16-column mode chunk without resident blocks or the wide setting");
-    const int KA = kMaxRhs;
-    ensureWork(KA);
-    hoReserve(KA, s);
-    hoReserve(K2, s, true);
+    const bool joint = two && modeNearBlocks.find(id);
+    ensureWork(h[0].K);
+    for (int i = 0; i < nh; ++i) hoReserve(h[i].K, s, i == 1);
+    if (joint) reserveCharges2(h[1].K);
+    double* const fT[2] = {dFT.as<double>(), (joint ? dFT2 : dFT).as<double>()};
+    double* const cT[2] = {dCT.as<double>(), (joint ? dCT2 : dCT).as<double>()};
+    double* const mult[2] = {dHoMult.as<double>(), dHoMult2.as<double>()};
+    double* const local[2] = {dHoLocal.as<double>(), dHoLocal2.as<double>()};
     StageSpans sp(*this, s);
-    if (modeNearResident(id)) {
-        // one near launch for all 16 columns: both halves' charges exist at once, the second
-        // half's in dFT2 / dCT2 (same stage ids, each stage once for both halves)
-        reserveCharges2(K2);
-        const CorrFold& cfA = corrTable(KA, 1, &id, identityMix(KA).data());
-        prepareCharges(KA, inA, dFT.as<double>(), dCT.as<double>(), s);
-        prepareCharges(K2, inB, dFT2.as<double>(), dCT2.as<double>(), s);
-        nearMode16(id, KA, K2, oA, oB, s);
+    // one round of the stages before the M2L per half, or one for both halves around the joint near launch
+    const int step = joint ? 2 : 1;
+    for (int i0 = 0; i0 < nh; i0 += step) {
+        const int i1 = i0 + step;
+        for (int i = i0; i < i1; ++i) prepareCharges(h[i].K, h[i].in, fT[i], cT[i], s);
+        if (joint) nearMode16(id, h[0], h[1], s);
+        else nearMode(h[i0].K, id, h[i0].o, s, prec);
         sp.end(4);
-        corrections(KA, cfA, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, oA, s);
-        // (corrTable may drop its folds when it adds one: the second half's is taken after the first's launch)
-        const CorrFold& cfB = corrTable(K2, 1, &id, identityMix(K2).data());
-        corrections(K2, cfB, dFT2.as<double>(), dCT2.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, oB, s);
-        sp.end(6);
-        hoUpPass(KA, dFT.as<double>(), dHoMult.as<double>(), false, s);
-        hoUpPass(K2, dFT2.as<double>(), dHoMult2.as<double>(), false, s);
-        sp.end(1);
-    } else {
-        for (int half = 0; half < 2; ++half) {
-            const int K = half ? K2 : KA;
-            const InRows& in = half ? inB : inA;
-            const OutRows& o = half ? oB : oA;
-            const CorrFold& cf = corrTable(K, 1, &id, identityMix(K).data());
-            prepareCharges(K, in, dFT.as<double>(), dCT.as<double>(), s);
-            nearMode(K, id, o, s);
-            sp.end(4);
-            corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
-            sp.end(6);
-            hoUpPass(K, dFT.as<double>(), (half ? dHoMult2 : dHoMult).as<double>(), false, s);
-            sp.end(1);
+        for (int i = i0; i < i1; ++i) {
+            // (corrTable may drop its folds when it adds one: the second half's is taken after the first's launch)
+            const CorrFold& cf = corrTable(h[i].K, 1, &id, identityMix(h[i].K).data());
+            corrections(h[i].K, cf, fT[i], cT[i], plan.ownBegin, plan.ownEnd, kStageAll, h[i].o, s);
         }
+        sp.end(6);
+        for (int i = i0; i < i1; ++i) hoUpPass(h[i].K, fT[i], mult[i], false, s);
+        sp.end(1);
     }
     sp.startRoofline();
-    if (F)
-        launch_ho_m2l_resident(np, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
-                               dAttSrc.as<int>(), dAttBlk.as<int>(), F, dHoMult.as<double>(), KA, dHoMult2.as<double>(),
-                               K2, dHoLocal.as<double>(), dHoLocal2.as<double>(), s);
+    if (f32)
+        launch_ho_m2l_mode_f32(np, h[0].K, id, pairList(), dAttM2LF.as<float>(), nodeBoxes(), dHoTab.as<HoTables>(),
+                               mult[0], local[0], s);
+    else if (F)
+        launch_ho_m2l_resident(np, id, pairList(), F, mult[0], h[0].K, two ? mult[1] : nullptr, two ? h[1].K : 0,
+                               local[0], two ? local[1] : nullptr, s);
+    else if (two)
+        launch_ho_m2l_mode_wide(np, h[1].K, id, pairList(), dAttM2L.as<double>(), nodeBoxes(), dHoTab.as<HoTables>(),
+                                mult[0], mult[1], local[0], local[1], s);
     else
-        launch_ho_m2l_mode_wide(np, K2, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(),
-                                dAttSrc.as<int>(), dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(),
-                                dNcy.as<double>(), dNrx.as<double>(), dNry.as<double>(), dHoTab.as<HoTables>(),
-                                dHoMult.as<double>(), dHoMult2.as<double>(), dHoLocal.as<double>(),
-                                dHoLocal2.as<double>(), s);
+        launch_ho_m2l_mode(np, h[0].K, id, pairList(), dAttM2L.as<double>(), nodeBoxes(), dHoTab.as<HoTables>(), mult[0],
+                           local[0], s);
     sp.end(2);
-    hoDownPass(KA, dHoLocal.as<double>(), oA, s);
-    hoDownPass(K2, dHoLocal2.as<double>(), oB, s);
+    for (int i = 0; i < nh; ++i) hoDownPass(h[i].K, local[i], h[i].o, s);
     sp.end(5);
     sp.total();
 }
@@ -1981,13 +1901,27 @@ void Operator::modeApplyLean16(int id, int K, const InRows& in, const OutRows& o
                  nullptr, nullptr, in, s);
     sp.end(1);
     sp.startRoofline();
-    launch_m2l_mode16(K, id, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
-                      dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                      dNry.as<double>(), dParams.as<Params>(), dMult.as<double>(), dLocal.as<double>(), s);
+    launch_m2l_mode16(K, id, pairList(), dAttM2L.as<double>(), nodeBoxes(), dParams.as<Params>(), dMult.as<double>(),
+                      dLocal.as<double>(), s);
     sp.end(2);
     downPass16(K, kStageAll, nullptr, nullptr, o, s);
     sp.end(5);
     sp.total();
+}
+
+// zero rows pad the half to its compiled count, as applyBlock pads (the buffers grow and never
+// shrink: a solve's active columns change the count)
+ModeHalf Operator::stageHalf(int nb, int K, const double* x, int64_t ldx, const double* sigT, bool sub, double* out,
+                             int64_t ldo, bool* padded, hipStream_t s) {
+    *padded = K != nb;
+    if (!*padded) return {K, InRows{x, ldx, false, sigT}, outRows(out, ldo, false, sub ? x : nullptr, ldx)};
+    const int64_t N = geo.N;
+    const size_t pb = (size_t)K * N * sizeof(double);
+    if (dPadIn.bytes < pb) dPadIn.alloc(pb);
+    if (dPadOut.bytes < pb) dPadOut.alloc(pb);
+    padRowsIn(dPadIn, 1, nb, K, x, ldx, s);
+    return {K, InRows{dPadIn.as<double>(), N, false, sigT},
+            outRows(dPadOut.as<double>(), N, false, sub ? dPadIn.as<double>() : nullptr, N)};
 }
 
 void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, const double* sigT, bool minuend,
@@ -2017,59 +1951,27 @@ void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, cons
             ldd = N;
         }
         const bool sub = minuend && !viaBuffer;
-        auto chunk = [&](int K, const double* xc, int64_t ldc, double* oc, int64_t ldoc) {
-            const InRows in{xc, ldc, false, sigT};
-            const OutRows o = outRows(oc, ldoc, false, sub ? xc : nullptr, ldc);
-            if (lean16) modeApplyLean16(id, K, in, o, s);
-            else modeApplyHigh(id, K, in, o, s, prec);
-            modeCalls.push_back(K);
-        };
-        // a resident high-order mode, or any with the wide setting on: more than 8 remaining
-        // columns form one chunk of up to 16
-        const bool wide = highOrder() && prec == ApplyPrec::F64 && (modeResident(id) || wideOn);
+        // a chunk: up to 8 columns as one half, or (a width of 16) 9 .. 16 as an 8-column half
+        // and a second one; a half of no compiled count is zero-padded to the next one
+        const int width = modeChunkWidth(id, prec);
         for (int j0 = 0; j0 < nrhs;) {
-            if (wide && nrhs - j0 > kMaxRhs) {
-                const int nb2 = std::min(kMaxRhs, nrhs - j0 - kMaxRhs);
-                const int K2 = nb2 == 1 ? 2 : rhs_padded(nb2);
-                const double* xa = x + (size_t)j0 * ldx;
-                double* oa = dst + (size_t)j0 * ldd;
-                const double* xb = xa + (size_t)kMaxRhs * ldx;
-                double* ob = oa + (size_t)kMaxRhs * ldd;
-                const InRows inA{xa, ldx, false, sigT};
-                const OutRows oA = outRows(oa, ldd, false, sub ? xa : nullptr, ldx);
-                if (K2 == nb2) {
-                    modeApplyHigh16(id, K2, inA, oA, InRows{xb, ldx, false, sigT},
-                                    outRows(ob, ldd, false, sub ? xb : nullptr, ldx), s);
-                } else {
-                    const size_t pb = (size_t)K2 * N * sizeof(double);
-                    if (dPadIn.bytes < pb) dPadIn.alloc(pb);
-                    if (dPadOut.bytes < pb) dPadOut.alloc(pb);
-                    padRowsIn(dPadIn, 1, nb2, K2, xb, ldx, s);
-                    modeApplyHigh16(id, K2, inA, oA, InRows{dPadIn.as<double>(), N, false, sigT},
-                                    outRows(dPadOut.as<double>(), N, false, sub ? dPadIn.as<double>() : nullptr, N), s);
-                    padRowsOut(dPadOut.as<double>(), nb2, N, ob, ldd, s);
-                }
-                modeCalls.push_back(2 * kMaxRhs);
-                j0 += kMaxRhs + nb2;
-                continue;
+            const int nc = std::min(width, nrhs - j0), nh = nc > kMaxRhs ? 2 : 1;
+            ModeHalf h[2];
+            int nb[2], padHalf = -1;
+            for (int i = 0; i < nh; ++i) {
+                const size_t r = (size_t)j0 + i * kMaxRhs;
+                nb[i] = std::min(kMaxRhs, nc - i * kMaxRhs);
+                const int K = nb[i] == 1 ? 2 : rhs_padded(nb[i]);  // (the mode kernels start at 2 columns)
+                bool padded = false;
+                h[i] = stageHalf(nb[i], K, x + r * ldx, ldx, sigT, sub, dst + r * ldd, ldd, &padded, s);
+                if (padded) padHalf = i;  // (at most one: the first of two halves is full)
             }
-            const int nb = std::min(kMaxRhs, nrhs - j0);
-            const int K = nb == 1 ? 2 : rhs_padded(nb);  // (the mode kernels start at 2 columns)
-            const double* xc = x + (size_t)j0 * ldx;
-            double* oc = dst + (size_t)j0 * ldd;
-            j0 += nb;
-            if (K == nb) {
-                chunk(K, xc, ldx, oc, ldd);
-                continue;
-            }
-            // zero columns pad the chunk to the next compiled count, as applyBlock pads
-            // (the buffers grow and never shrink: a solve's active columns change the count)
-            const size_t pb = (size_t)K * N * sizeof(double);
-            if (dPadIn.bytes < pb) dPadIn.alloc(pb);
-            if (dPadOut.bytes < pb) dPadOut.alloc(pb);
-            padRowsIn(dPadIn, 1, nb, K, xc, ldx, s);
-            chunk(K, dPadIn.as<double>(), N, dPadOut.as<double>(), N);
-            padRowsOut(dPadOut.as<double>(), nb, N, oc, ldd, s);
+            if (lean16) modeApplyLean16(id, h[0].K, h[0].in, h[0].o, s);
+            else modeChunkHigh(id, nh, h, s, prec);
+            if (padHalf >= 0)
+                padRowsOut(dPadOut.as<double>(), nb[padHalf], N, dst + ((size_t)j0 + padHalf * kMaxRhs) * ldd, ldd, s);
+            modeCalls.push_back(nh == 2 ? 2 * kMaxRhs : h[0].K);
+            j0 += nc;
         }
         if (viaBuffer) launch_sub_slice(N, nrhs, x, ldx, dBlk.as<double>(), N, out, ldo, s);
         return;
@@ -2105,8 +2007,7 @@ void Operator::mappingMultiHost(const double* Q, int k, int id, double* Out) {
     if (!modeApplyCheck("aniso_mapping_multi", id, k, Q, geo.N, Out, geo.N, false)) return;
     ensureDevice();
     const int64_t N = geo.N;
-    // (a resident mode's chunk, or the wide setting's)
-    const int kb = std::min(k, highOrder() && (modeResident(id) || wideOn) ? 2 * kMaxRhs : kMaxRhs);
+    const int kb = std::min(k, modeChunkWidth(id, ApplyPrec::F64));
     DevBuf dq, dout;
     dq.alloc((size_t)kb * N * sizeof(double));
     dout.alloc((size_t)kb * N * sizeof(double));
@@ -2508,10 +2409,8 @@ void Operator::blockMultiChunk(int which, int S, int nreal, const double* x, int
         sp.end(1);
     }
     sp.start();
-    launch_ho_m2l_src(np, K, S, (int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(),
-                      dAttBlk.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(),
-                      dNry.as<double>(), dHoTab.as<HoTables>(), hw, dMsMult.as<double>(), (int64_t)exp,
-                      dMsLocal.as<double>(), (int64_t)exp, s);
+    launch_ho_m2l_src(np, K, S, pairList(), dAttM2L.as<double>(), nodeBoxes(), dHoTab.as<HoTables>(), hw,
+                      dMsMult.as<double>(), (int64_t)exp, dMsLocal.as<double>(), (int64_t)exp, s);
     sp.end(2);
     for (int j = 0; j < nreal; ++j) {
         const OutRows o = rowsOut(j);
@@ -2955,8 +2854,8 @@ void Operator::buildF32() {
         DevBuf tmp;
         tmp.alloc((size_t)std::max<int64_t>(np_, 1) * 256 * sizeof(double));
         d32Km2l.alloc((size_t)std::max<int64_t>(np_, 1) * 256 * sizeof(float));
-        launch_cache_m2l(np_, d32PairTgt.as<int>(), d32Src.as<int>(), dNcx.as<double>(), dNcy.as<double>(),
-                         dNrx.as<double>(), dNry.as<double>(), dStCoef.as<double>(), P, 0, tmp.as<double>(), own);
+        launch_cache_m2l(np_, d32PairTgt.as<int>(), d32Src.as<int>(), nodeBoxes(), dStCoef.as<double>(), P, 0,
+                         tmp.as<double>(), own);
         launch32_conv_m2l(np_, tmp.as<double>(), d32Km2l.p, own);
         HIP_CHECK(hipStreamSynchronize(own));
     }
@@ -2965,8 +2864,8 @@ void Operator::buildF32() {
         tmp.alloc((size_t)std::max<int64_t>(f.nearD, 1) * sizeof(double));
         d32Knear.alloc((size_t)std::max<int64_t>(f.nearTiles, 1) * 4 * sizeof(float));
         launch_cache_near((int)f.leaves.size(), d32Leaves.as<int>(), d32SrcPtr.as<int64_t>(), d32SrcNodes.as<int>(),
-                          d32KoffD.as<int64_t>(), dBegin.as<int64_t>(), dCount.as<int64_t>(), dPxT.as<double>(),
-                          dPyT.as<double>(), dStCoef.as<double>(), P, 0, f.maxSrc, tmp.as<double>(), own);
+                          d32KoffD.as<int64_t>(), dBegin.as<int64_t>(), dCount.as<int64_t>(), treePoints(),
+                          dStCoef.as<double>(), P, 0, f.maxSrc, tmp.as<double>(), own);
         launch32_conv_near((int)f.leaves.size(), d32LeafInfo.as<int4>(), d32KoffD.as<int64_t>(),
                            d32Koff.as<int64_t>(), d32SrcCount.as<int>(), tmp.as<double>(), d32Knear.p, own);
         HIP_CHECK(hipStreamSynchronize(own));
@@ -3001,16 +2900,16 @@ void Operator::buildMrhs64(int id) {
     Mrhs64Cache c;
     const int64_t np_ = (int64_t)f.m2lSrc.size();
     c.Km2l.alloc((size_t)std::max<int64_t>(np_, 1) * 256 * sizeof(double));
-    launch_cache_m2l(np_, d32PairTgt.as<int>(), d32Src.as<int>(), dNcx.as<double>(), dNcy.as<double>(),
-                     dNrx.as<double>(), dNry.as<double>(), dStCoef.as<double>(), P, id, c.Km2l.as<double>(), own);
+    launch_cache_m2l(np_, d32PairTgt.as<int>(), d32Src.as<int>(), nodeBoxes(), dStCoef.as<double>(), P, id,
+                     c.Km2l.as<double>(), own);
     launch64_lane_major(np_, c.Km2l.as<double>(), own);
     {
         DevBuf tmp;
         tmp.alloc((size_t)std::max<int64_t>(f.nearD, 1) * sizeof(double));
         c.Knear.alloc((size_t)std::max<int64_t>(f.nearTiles, 1) * 4 * sizeof(double));
         launch_cache_near((int)f.leaves.size(), d32Leaves.as<int>(), d32SrcPtr.as<int64_t>(), d32SrcNodes.as<int>(),
-                          d32KoffD.as<int64_t>(), dBegin.as<int64_t>(), dCount.as<int64_t>(), dPxT.as<double>(),
-                          dPyT.as<double>(), dStCoef.as<double>(), P, id, f.maxSrc, tmp.as<double>(), own);
+                          d32KoffD.as<int64_t>(), dBegin.as<int64_t>(), dCount.as<int64_t>(), treePoints(),
+                          dStCoef.as<double>(), P, id, f.maxSrc, tmp.as<double>(), own);
         launch64_conv_near((int)f.leaves.size(), d32LeafInfo.as<int4>(), d32KoffD.as<int64_t>(),
                            d32Koff.as<int64_t>(), d32SrcCount.as<int>(), tmp.as<double>(), c.Knear.p, own);
         HIP_CHECK(hipStreamSynchronize(own));

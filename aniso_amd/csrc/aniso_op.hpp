@@ -111,20 +111,29 @@ struct ApplyCall {
 };
 
 // The K input rows of an apply (tree: in tree order; sigT: sigma_s in tree order, multiplied
-// into the charges, or nullptr) and its output rows (Operator::outRows: perm / base place a
-// tree position in `out`; the last writer stores minuend - (...) where minuend is set).
+// into the charges, or nullptr); its output rows are kernels.hpp's OutRows (Operator::outRows).
 struct InRows {
     const double* x;
     int64_t ld;
     bool tree;
     const double* sigT;
 };
-struct OutRows {
-    double* out;
-    const double* minuend;
-    const int* perm;
-    int64_t ld, base, minuendLd;
-    bool tree;
+// One half of a mode chunk on a high-order handle (Operator::modeChunkHigh): K compiled columns
+struct ModeHalf {
+    int K;
+    InRows in;
+    OutRows o;
+};
+
+// The resident factor blocks of one kind per mode id (Operator::cacheMode / cacheModeNear)
+struct ResidentBlocks {
+    std::map<int, DevBuf> blocks;
+    const double* find(int id) const {  // nullptr: mode id has none
+        const auto it = blocks.find(id);
+        return it == blocks.end() ? nullptr : it->second.as<double>();
+    }
+    void free(int id);  // id = -1: all
+    int64_t bytes() const;
 };
 
 class Operator {
@@ -621,13 +630,23 @@ private:
     OutRows outRows(double* out, int64_t ld, bool tree, const double* minuend = nullptr, int64_t minuendLd = 0) const {
         return {out, minuend, tree ? nullptr : dPerm.as<int>(), ld, tree ? plan.ownBegin : 0, minuendLd, tree};
     }
+    // the plan views of kernels.hpp: the only place these buffers are cast for the launchers that take views
+    PairList pairList() const {
+        return {(int)plan.m2lTgt.size(), dM2LTgt.as<int>(), dAttPtr.as<int64_t>(), dAttSrc.as<int>(), dAttBlk.as<int>()};
+    }
+    NodeBoxes nodeBoxes() const { return {dNcx.as<double>(), dNcy.as<double>(), dNrx.as<double>(), dNry.as<double>()}; }
+    TreePoints treePoints() const { return {dPxT.as<double>(), dPyT.as<double>()}; }
+    NearList nearList(bool residentOff = false) const {  // residentOff: off = nearFOff, else nearKOff
+        return {(int)plan.leaves.size(), plan.nearMaxLeaf, dLeafInfo.as<int4>(), dNearPtsPtr.as<int64_t>(),
+                dNearPts.as<int>(), (residentOff ? dNearFOff : dNearKOff).as<int64_t>()};
+    }
     void prepareCharges(int K, const InRows& in, double* fT, double* cT, hipStream_t s);
     void nearUnstaged(int K, const HarmWeights& hw, const HarmWindow* win, int mask, const OutRows& o, hipStream_t s);
     void nearUnstagedF32(int K, const HarmWeights& hw, const OutRows& o, hipStream_t s);
     void nearMode(int K, int id, const OutRows& o, hipStream_t s, ApplyPrec prec = ApplyPrec::F64);
-    // a 16-column chunk's near field on the resident near blocks: columns 0 .. KA-1 from
-    // dFT to oA, 8 .. 8+KB-1 from dFT2 to oB, one launch
-    void nearMode16(int id, int KA, int KB, const OutRows& oA, const OutRows& oB, hipStream_t s);
+    // a two-half chunk's near field on the resident near blocks: columns 0 .. KA-1 from
+    // dFT to a.o, 8 .. 8+KB-1 from dFT2 to b.o, one launch
+    void nearMode16(int id, const ModeHalf& a, const ModeHalf& b, hipStream_t s);
     void corrections(int K, const CorrFold& cf, const double* fT, const double* cT, int64_t begin, int64_t end,
                      int mask, const OutRows& o, hipStream_t s);
     // dHoMult / dHoLocal for K columns (grown, never shrunk), the locals zeroed; second: the
@@ -654,27 +673,30 @@ private:
     // mapping of a mode whose operators are not resident: one pass of the offset form
     // (sigT: tree-order sigma_s multiplied into the charge by the pass's launch_prepare)
     void leanMapping(const double* charge, int id, double* out, hipStream_t s, int mask, const double* sigT = nullptr);
-    // modeApplyDev's chunk of K = 2, 4, 5 or 8 columns on a high-order handle
-    void modeApplyHigh(int id, int K, const InRows& in, const OutRows& o, hipStream_t s, ApplyPrec prec);
-    // its chunk of more than 8 columns on a resident mode: the launches of an 8-column half
-    // and of a K2-column half (K2 = 2, 4, 5 or 8) around one resident M2L for all of them
-    void modeApplyHigh16(int id, int K2, const InRows& inA, const OutRows& oA, const InRows& inB, const OutRows& oB,
-                         hipStream_t s);
-    std::map<int, DevBuf> modeBlocks;  // cacheMode: resident factor blocks per mode id
-    const double* modeResident(int id) const {
-        const auto it = modeBlocks.find(id);
-        return it == modeBlocks.end() ? nullptr : it->second.as<double>();
+    // modeApplyDev's chunk on a high-order handle: one half of K = 2, 4, 5 or 8 columns, or (a
+    // resident mode, or the wide setting) an 8-column half and a second of 2, 4, 5 or 8 around
+    // one M2L for all of them
+    void modeChunkHigh(int id, int nh, const ModeHalf* h, hipStream_t s, ApplyPrec prec);
+    // the most columns of one chunk of modeApplyDev: 16 on a high-order handle in fp64 with the
+    // mode's M2L blocks resident or the wide setting on, else 8
+    int modeChunkWidth(int id, ApplyPrec prec) const {
+        return highOrder() && prec == ApplyPrec::F64 && (modeBlocks.find(id) || wideOn) ? 2 * kMaxRhs : kMaxRhs;
     }
+    // nb rows of x (stride ldx) as a half of K compiled columns writing nb rows of out: in place
+    // (K = nb), or through dPadIn / dPadOut with zero rows (*padded: padRowsOut is due after the chunk)
+    ModeHalf stageHalf(int nb, int K, const double* x, int64_t ldx, const double* sigT, bool sub, double* out,
+                       int64_t ldo, bool* padded, hipStream_t s);
+    // cacheMode's and cacheModeNear's shared checks, memory policy and bookkeeping: `built` and
+    // `noun` name the blocks in the messages, build(F) enqueues the launch that fills them on `own`
+    void cacheResident(const char* api, const char* built, const char* noun, bool needDirected, int id,
+                       ResidentBlocks& rb, size_t need, const std::function<void(double*)>& build);
+    ResidentBlocks modeBlocks;  // cacheMode: resident factor blocks per mode id
     DevBuf dHoMult2, dHoLocal2;
     int hoWorkK2 = 0;
     // setWide: every mode forms 16-column chunks, resident or not (the wide mode M2L measured
     // shorter than two narrow launches at both orders)
     bool wideOn = false;
-    std::map<int, DevBuf> modeNearBlocks;  // cacheModeNear: resident near factor blocks per mode id
-    const double* modeNearResident(int id) const {
-        const auto it = modeNearBlocks.find(id);
-        return it == modeNearBlocks.end() ? nullptr : it->second.as<double>();
-    }
+    ResidentBlocks modeNearBlocks;  // cacheModeNear: resident near factor blocks per mode id
     // the charges of a 16-column chunk's second half while one near launch serves both
     // (grown, never shrunk, as dHoMult2)
     DevBuf dFT2, dCT2;

@@ -253,34 +253,31 @@ __global__ void __launch_bounds__(256) k_near_hm_f32(int nl, const int4* __restr
             throw std::invalid_argument("f32 block operator: unsupported block count " + std::to_string(k)); \
     }
 
-void launch_near_hm_f32(int K, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
-                        const int* nearPts, const int64_t* nearKOff, const float* E, const double* ncx,
-                        const double* ncy, const double* pxT, const double* pyT, const double* sigDiag,
-                        const HarmWeights& hw, const double* fT, const int* operm, int64_t obase, int64_t ldo,
-                        double scale, double* out, hipStream_t s) {
-    if (nl <= 0) return;
-    if (maxLeaf <= 16) {
-        ANISO_BLOCK_F32_DISPATCH_K(K, (k_near_hm_f32<KK, 16, 2><<<blocks_for((int64_t)nl * 16, 256), 256, 0, s>>>(
-                                          nl, leafInfo, nearPtsPtr, nearPts, nearKOff, E, ncx, ncy, pxT, pyT, sigDiag,
-                                          hw, fT, operm, obase, ldo, scale, out)));
+void launch_near_hm_f32(int K, const NearList& nl, const float* E, const NodeBoxes& b, const TreePoints& pts,
+                        const double* sigDiag, const HarmWeights& hw, const double* fT, double scale,
+                        const OutRows& o, hipStream_t s) {
+    if (nl.nl <= 0) return;
+    if (nl.maxLeaf <= 16) {
+        ANISO_BLOCK_F32_DISPATCH_K(K, (k_near_hm_f32<KK, 16, 2><<<blocks_for((int64_t)nl.nl * 16, 256), 256, 0, s>>>(
+                                          nl.nl, nl.leafInfo, nl.ptsPtr, nl.pts, nl.off, E, b.cx, b.cy, pts.px, pts.py,
+                                          sigDiag, hw, fT, o.perm, o.base, o.ld, scale, o.out)));
     } else {
-        ANISO_BLOCK_F32_DISPATCH_K(K, (k_near_hm_f32<KK, 64, 2><<<blocks_for((int64_t)nl * 64, 256), 256, 0, s>>>(
-                                          nl, leafInfo, nearPtsPtr, nearPts, nearKOff, E, ncx, ncy, pxT, pyT, sigDiag,
-                                          hw, fT, operm, obase, ldo, scale, out)));
+        ANISO_BLOCK_F32_DISPATCH_K(K, (k_near_hm_f32<KK, 64, 2><<<blocks_for((int64_t)nl.nl * 64, 256), 256, 0, s>>>(
+                                          nl.nl, nl.leafInfo, nl.ptsPtr, nl.pts, nl.off, E, b.cx, b.cy, pts.px, pts.py,
+                                          sigDiag, hw, fT, o.perm, o.base, o.ld, scale, o.out)));
     }
     HIP_LAUNCH_CHECK();
 }
 
-void launch_ho_m2l_f32(int np, int K, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk,
-                       const float* E, const double* ncx, const double* ncy, const double* nrx, const double* nry,
-                       const HoTables* T, const HarmWeights& hw, const double* mult, double* local, hipStream_t s) {
-    if (ntgt <= 0) return;
+void launch_ho_m2l_f32(int np, int K, const PairList& pl, const float* E, const NodeBoxes& b, const HoTables* T,
+                       const HarmWeights& hw, const double* mult, double* local, hipStream_t s) {
+    if (pl.ntgt <= 0) return;
     if (np == 6) {
-        ANISO_BLOCK_F32_DISPATCH_K(K, (k_ho_m2l_f32<6, KK><<<ntgt, 256, 0, s>>>(tgt, ptr, src, blk, E, ncx, ncy, nrx,
-                                                                               nry, T, hw, mult, local)));
+        ANISO_BLOCK_F32_DISPATCH_K(K, (k_ho_m2l_f32<6, KK><<<pl.ntgt, 256, 0, s>>>(
+                                          pl.tgt, pl.ptr, pl.src, pl.blk, E, b.cx, b.cy, b.rx, b.ry, T, hw, mult, local)));
     } else if (np == 8) {
-        ANISO_BLOCK_F32_DISPATCH_K(K, (k_ho_m2l_f32<8, KK><<<ntgt, 256, 0, s>>>(tgt, ptr, src, blk, E, ncx, ncy, nrx,
-                                                                               nry, T, hw, mult, local)));
+        ANISO_BLOCK_F32_DISPATCH_K(K, (k_ho_m2l_f32<8, KK><<<pl.ntgt, 256, 0, s>>>(
+                                          pl.tgt, pl.ptr, pl.src, pl.blk, E, b.cx, b.cy, b.rx, b.ry, T, hw, mult, local)));
     } else {
         throw std::invalid_argument("f32 block operator: np must be 6 or 8");
     }

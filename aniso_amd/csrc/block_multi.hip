@@ -126,10 +126,11 @@ __global__ void __launch_bounds__(256) k_ho_m2l_src(const int* __restrict__ tgt,
         break;
 #define ANISO_SRC_CASES(np, k) ANISO_SRC_CASE(np, k, 1) ANISO_SRC_CASE(np, k, 2) ANISO_SRC_CASE(np, k, 4)
 
-void launch_ho_m2l_src(int np, int K, int S, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
-                       const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
-                       const double* nry, const HoTables* T, const HarmWeights& hw, const double* mult,
-                       int64_t mstride, double* local, int64_t lstride, hipStream_t s) {
+void launch_ho_m2l_src(int np, int K, int S, const PairList& pl, const double* E, const NodeBoxes& b,
+                       const HoTables* T, const HarmWeights& hw, const double* mult, int64_t mstride, double* local,
+                       int64_t lstride, hipStream_t s) {
+    const auto [ntgt, tgt, ptr, src, blk] = pl;  // (the names ANISO_SRC_CASE passes on)
+    const auto [ncx, ncy, nrx, nry] = b;
     if (ntgt <= 0) return;
     switch ((np * 16 + K) * 8 + S) {
         ANISO_SRC_CASES(6, 2)

@@ -1606,9 +1606,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W4 ? 4
 
 // per-target M2L (ANISO_HM_CLUSTER=0): two Newton steps in 1/r (full fp64), 4 waves
 // per SIMD (measured best, r01e)
-void launch_m2l_hm(int K, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk, const double* E,
-                   const double* ncx, const double* ncy, const double* nrx, const double* nry, const Params* P,
+void launch_m2l_hm(int K, const PairList& pl, const double* E, const NodeBoxes& b, const Params* P,
                    const HarmWeights& hw, const double* mult, double* local, hipStream_t s, const HarmWindow* win) {
+    const auto [ntgt, tgt, ptr, src, blk] = pl;
+    const auto [ncx, ncy, nrx, nry] = b;
     if (ntgt <= 0) return;
     const unsigned nb = blocks_for((int64_t)ntgt * kWave, 256);
     if (win) {  // one pass of a block operator of more than kMaxRhs blocks: the offset form, K = kMaxRhs only
@@ -1850,12 +1851,15 @@ bool near_hs_fusable(int nl, int maxLeaf, int nsMax, const uint16_t* nearLoc, co
     return near_hs_staged(nl, maxLeaf, nsMax, nearLoc) && corr && corr->rows && (flags & kStageNear);
 }
 
-bool launch_near_hm(int K, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr, const int* nearPts,
-                    const int64_t* nearKOff, const double* E, const double* pxT, const double* pyT,
-                    const double* sigDiag, const HarmWeights& hw, const double* fT, const int* operm, int64_t obase,
-                    int64_t ldo, int flags, double scale, double* out, const uint16_t* nearLoc, const int64_t* nsPtr,
-                    const int* nsPts, int nsMax, const NearCorr* corr, int wpe, hipStream_t s, const NearHsArgs* in,
-                    const HarmWindow* win) {
+bool launch_near_hm(int K, const NearList& list, const double* E, const TreePoints& pts, const double* sigDiag,
+                    const HarmWeights& hw, const double* fT, int flags, double scale, const OutRows& o,
+                    const uint16_t* nearLoc, const int64_t* nsPtr, const int* nsPts, int nsMax, const NearCorr* corr,
+                    int wpe, hipStream_t s, const NearHsArgs* in, const HarmWindow* win) {
+    const auto [nl, maxLeaf, leafInfo, nearPtsPtr, nearPts, nearKOff] = list;
+    const auto [pxT, pyT] = pts;
+    const int* const operm = o.perm;
+    const int64_t obase = o.base, ldo = o.ld;
+    double* const out = o.out;
     if (nl <= 0) return false;
     // one pass of a block operator of more than kMaxRhs blocks: the offset form, K = kMaxRhs,
     // the plain directed kernels only

@@ -380,23 +380,22 @@ __global__ void __launch_bounds__(64) k_ho_l2p(const int4* __restrict__ leafInfo
                                         std::to_string(np) + " / " + std::to_string(k));                     \
     }
 
-void launch_ho_cache_att(int np, int64_t npairs, const int* pairTgt, const int* src, const double* ncx,
-                         const double* ncy, const double* nrx, const double* nry, const double* stcoef,
-                         const Params* P, const HoTables* T, double* E, hipStream_t s) {
+void launch_ho_cache_att(int np, int64_t npairs, const int* pairTgt, const int* src, const NodeBoxes& b,
+                         const double* stcoef, const Params* P, const HoTables* T, double* E, hipStream_t s) {
     if (npairs <= 0) return;
     const int64_t total = npairs * np * np * np * np;
     if (blocks_for(total, 256) > 0x7fffffffu) throw std::invalid_argument("high-order E cache: too many pairs for one launch");
-    if (np == 6) k_ho_cache_att<6><<<blocks_for(total, 256), 256, 0, s>>>(total, pairTgt, src, ncx, ncy, nrx, nry, stcoef, P, T, E);
-    else if (np == 8) k_ho_cache_att<8><<<blocks_for(total, 256), 256, 0, s>>>(total, pairTgt, src, ncx, ncy, nrx, nry, stcoef, P, T, E);
+    if (np == 6) k_ho_cache_att<6><<<blocks_for(total, 256), 256, 0, s>>>(total, pairTgt, src, b.cx, b.cy, b.rx, b.ry, stcoef, P, T, E);
+    else if (np == 8) k_ho_cache_att<8><<<blocks_for(total, 256), 256, 0, s>>>(total, pairTgt, src, b.cx, b.cy, b.rx, b.ry, stcoef, P, T, E);
     else throw std::invalid_argument("high-order E cache: np must be 6 or 8");
     HIP_LAUNCH_CHECK();
 }
 
-void launch_ho_p2m(int np, int K, int nl, const int4* leafInfo, const double* ncx, const double* ncy,
-                   const double* nrx, const double* nry, const double* pxT, const double* pyT, const double* fT,
-                   const HoTables* T, double* mult, hipStream_t s) {
+void launch_ho_p2m(int np, int K, int nl, const int4* leafInfo, const NodeBoxes& b, const TreePoints& pts,
+                   const double* fT, const HoTables* T, double* mult, hipStream_t s) {
     if (nl <= 0) return;
-    ANISO_HO_DISPATCH(np, K, (k_ho_p2m<NN, KK><<<nl, 64, 0, s>>>(leafInfo, ncx, ncy, nrx, nry, pxT, pyT, fT, T, mult)));
+    ANISO_HO_DISPATCH(np, K, (k_ho_p2m<NN, KK><<<nl, 64, 0, s>>>(leafInfo, b.cx, b.cy, b.rx, b.ry, pts.px, pts.py, fT, T,
+                                                                  mult)));
     HIP_LAUNCH_CHECK();
 }
 
@@ -407,18 +406,16 @@ void launch_ho_m2m(int np, int K, int nn, const int* nodes, const int4* child, c
     HIP_LAUNCH_CHECK();
 }
 
-void launch_ho_m2l(int np, int K, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk,
-                   const double* E, const double* ncx, const double* ncy, const double* nrx, const double* nry,
-                   const HoTables* T, const HarmWeights& hw, const HarmWindow* win, const double* mult,
-                   double* local, hipStream_t s) {
-    if (ntgt <= 0) return;
+void launch_ho_m2l(int np, int K, const PairList& pl, const double* E, const NodeBoxes& b, const HoTables* T,
+                   const HarmWeights& hw, const HarmWindow* win, const double* mult, double* local, hipStream_t s) {
+    if (pl.ntgt <= 0) return;
     if (win && K != kMaxRhs) throw std::invalid_argument("high-order M2L: the offset form takes 8 blocks per pass");
     HoHarm a;
     static_cast<HarmWeights&>(a) = hw;
     a.i0 = win ? win->i0 : 0;
     a.b0 = win ? win->b0 : 0;
-    ANISO_HO_DISPATCH(np, K, (k_ho_m2l<NN, KK><<<ntgt, 256, 0, s>>>(tgt, ptr, src, blk, E, ncx, ncy, nrx, nry, T, a,
-                                                                     mult, local)));
+    ANISO_HO_DISPATCH(np, K, (k_ho_m2l<NN, KK><<<pl.ntgt, 256, 0, s>>>(pl.tgt, pl.ptr, pl.src, pl.blk, E, b.cx, b.cy,
+                                                                        b.rx, b.ry, T, a, mult, local)));
     HIP_LAUNCH_CHECK();
 }
 
@@ -429,13 +426,12 @@ void launch_ho_l2l(int np, int K, int nn, const int* nodes, const int* parent, c
     HIP_LAUNCH_CHECK();
 }
 
-void launch_ho_l2p(int np, int K, int nl, const int4* leafInfo, const double* ncx, const double* ncy,
-                   const double* nrx, const double* nry, const double* pxT, const double* pyT, const HoTables* T,
-                   const double* local, const int* operm, int64_t obase, int64_t ldo, double scale, double* out,
-                   const double* xsub, int64_t ldx, hipStream_t s) {
+void launch_ho_l2p(int np, int K, int nl, const int4* leafInfo, const NodeBoxes& b, const TreePoints& pts,
+                   const HoTables* T, const double* local, double scale, const OutRows& o, hipStream_t s) {
     if (nl <= 0) return;
-    ANISO_HO_DISPATCH(np, K, (k_ho_l2p<NN, KK><<<nl, 64, 0, s>>>(leafInfo, ncx, ncy, nrx, nry, pxT, pyT, T, local,
-                                                                  operm, obase, ldo, scale, out, xsub, ldx)));
+    ANISO_HO_DISPATCH(np, K, (k_ho_l2p<NN, KK><<<nl, 64, 0, s>>>(leafInfo, b.cx, b.cy, b.rx, b.ry, pts.px, pts.py, T,
+                                                                  local, o.perm, o.base, o.ld, scale, o.out, o.minuend,
+                                                                  o.minuendLd)));
     HIP_LAUNCH_CHECK();
 }
 

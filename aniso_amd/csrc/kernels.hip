@@ -138,21 +138,21 @@ __global__ void k_line_integrals(int n, const double* __restrict__ seg, const do
 
 // ----------------------------------------------------------------- launchers
 
-void launch_cache_m2l(int64_t npairs, const int* pairTgt, const int* src, const double* ncx, const double* ncy,
-                      const double* nrx, const double* nry, const double* stcoef, const Params* P, int mode,
-                      double* K, hipStream_t s) {
+void launch_cache_m2l(int64_t npairs, const int* pairTgt, const int* src, const NodeBoxes& b, const double* stcoef,
+                      const Params* P, int mode, double* K, hipStream_t s) {
     if (npairs <= 0) return;
     int64_t total = npairs * 256;
-    k_cache_m2l<<<blocks_for(total, 256), 256, 0, s>>>(total, pairTgt, src, ncx, ncy, nrx, nry, stcoef, P, mode, K);
+    k_cache_m2l<<<blocks_for(total, 256), 256, 0, s>>>(total, pairTgt, src, b.cx, b.cy, b.rx, b.ry, stcoef, P, mode,
+                                                       K);
     HIP_LAUNCH_CHECK();
 }
 
-void launch_cache_att_m2l(int64_t npairs, const int* pairTgt, const int* src, const double* ncx, const double* ncy,
-                          const double* nrx, const double* nry, const double* stcoef, const Params* P, double* E,
-                          hipStream_t s) {
+void launch_cache_att_m2l(int64_t npairs, const int* pairTgt, const int* src, const NodeBoxes& b,
+                          const double* stcoef, const Params* P, double* E, hipStream_t s) {
     if (npairs <= 0) return;
     int64_t total = npairs * 256;
-    k_cache_att_m2l<<<blocks_for(total, 256), 256, 0, s>>>(total, pairTgt, src, ncx, ncy, nrx, nry, stcoef, P, E);
+    k_cache_att_m2l<<<blocks_for(total, 256), 256, 0, s>>>(total, pairTgt, src, b.cx, b.cy, b.rx, b.ry, stcoef, P,
+                                                           E);
     HIP_LAUNCH_CHECK();
 }
 
@@ -164,12 +164,12 @@ void launch_sigma_diag(int64_t N, const double* pxT, const double* pyT, const do
 }
 
 void launch_cache_near(int nl, const int* leaves, const int64_t* nearPtr, const int* nearSrc, const int64_t* nearKOff,
-                       const int64_t* begin, const int64_t* count, const double* pxT, const double* pyT,
-                       const double* stcoef, const Params* P, int mode, int maxSrc, double* K, hipStream_t s) {
+                       const int64_t* begin, const int64_t* count, const TreePoints& pts, const double* stcoef,
+                       const Params* P, int mode, int maxSrc, double* K, hipStream_t s) {
     if (nl <= 0) return;
     size_t shm = (size_t)maxSrc * sizeof(int64_t) + (size_t)(maxSrc + 1) * sizeof(int);
-    k_cache_near<<<nl, 256, shm, s>>>(nl, leaves, nearPtr, nearSrc, nearKOff, begin, count, pxT, pyT, stcoef, P, mode,
-                                      maxSrc, K);
+    k_cache_near<<<nl, 256, shm, s>>>(nl, leaves, nearPtr, nearSrc, nearKOff, begin, count, pts.px, pts.py, stcoef, P,
+                                      mode, maxSrc, K);
     HIP_LAUNCH_CHECK();
 }
 

@@ -66,6 +66,44 @@ enum StageMask : int {
     kStageForward = 16,  // 16-RHS fp64 operator (f64op.hip): Y = X - K (sigma_s X) instead of Y = K X
 };
 
+// ---- views of the plan's device arrays, as the launchers of the un-fused applies take them
+// (Operator's accessors build them): one type per argument group, so a
+// swapped group does not compile.
+// the pair lists of the mode-shared caches (Plan::attPtr / attSrc / attBlk over m2lTgt)
+struct PairList {
+    int ntgt;
+    const int* tgt;
+    const int64_t* ptr;
+    const int* src;
+    const int* blk;
+};
+struct NodeBoxes {  // per node: centre and half widths
+    const double *cx, *cy, *rx, *ry;
+};
+struct TreePoints {  // the points in tree order
+    const double *px, *py;
+};
+// the directed near lists of the target leaves (maxLeaf: the largest, in points); off: per
+// leaf its first stored entry, Plan::nearKOff for the E blocks or nearFOff for resident near blocks
+struct NearList {
+    int nl, maxLeaf;
+    const int4* leafInfo;
+    const int64_t* ptsPtr;
+    const int* pts;
+    const int64_t* off;
+};
+// The output rows of an apply (Operator::outRows): perm / base place a tree position in `out`
+// (perm = the permutation writes the original-order vector out[perm[k]]; perm = nullptr the
+// owned tree-order slice out[k - base]), ld = the stride between rows; the last writer stores
+// minuend - (...) where minuend is set.
+struct OutRows {
+    double* out;
+    const double* minuend;
+    const int* perm;
+    int64_t ld, base, minuendLd;
+    bool tree;
+};
+
 constexpr int kTierThreads = 256;  // workgroup of the down pass tasks
 // up pass tasks: 256 threads (P2M holds 16 products per lane, ~94 VGPRs = 5 waves
 // per SIMD), so four workgroups fit per CU and 1,024 tasks run in one round
@@ -195,8 +233,7 @@ void launch_corr(int K, int d, int64_t b, int64_t e, const int* perm, const int*
                  const double* fT, const double* Wc, const double* Wm, const Params* P, int flags, double scale,
                  bool treeOut, int64_t ldo, double* out, hipStream_t s);
 // harmonic block apply (harmonic.hip): all modes from the mode-shared E caches
-void launch_m2l_hm(int K, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk, const double* E,
-                   const double* ncx, const double* ncy, const double* nrx, const double* nry, const Params* P,
+void launch_m2l_hm(int K, const PairList& pl, const double* E, const NodeBoxes& b, const Params* P,
                    const HarmWeights& hw, const double* mult, double* local, hipStream_t s,
                    const HarmWindow* win = nullptr);  // win: the offset form (K = 8)
 // the clustered M2L's arguments (harmonic.hip k_m2l_hc, k_top_m2l_hc)
@@ -373,11 +410,10 @@ void launch_abs_max(int64_t n, const double* x, double* out, hipStream_t s);
 int hm_ring_depth();  // ANISO_HM_RING (read at handle creation): the cluster M2L's LDS ring depth
 int hm_ring_xl(int K, int maxCl, int depth);  // its target multipole in LDS / VGPRs / ring off (1, 0, -1)
 // returns true when the corrections were fused (the caller skips launch_corr)
-bool launch_near_hm(int K, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr, const int* nearPts,
-                    const int64_t* nearKOff, const double* E, const double* pxT, const double* pyT,
-                    const double* sigDiag, const HarmWeights& hw, const double* fT, const int* operm, int64_t obase,
-                    int64_t ldo, int flags, double scale, double* out, const uint16_t* nearLoc, const int64_t* nsPtr,
-                    const int* nsPts, int nsMax, const NearCorr* corr, int wpe, hipStream_t s,
+bool launch_near_hm(int K, const NearList& list, const double* E, const TreePoints& pts, const double* sigDiag,
+                    const HarmWeights& hw, const double* fT, int flags, double scale, const OutRows& o,
+                    const uint16_t* nearLoc, const int64_t* nsPtr, const int* nsPts, int nsMax, const NearCorr* corr,
+                    int wpe, hipStream_t s,
                     const NearHsArgs* in = nullptr,  // in->xin: the staged kernel's charges from the input
                     const HarmWindow* win = nullptr);  // win: the offset form (K = 8, directed storage)
 // out[i] = a[i] (add == 0) or out[i] += a[i], rows i < nrhs of n entries: the sum over a block operator's passes
@@ -398,127 +434,104 @@ struct HoTables {
 };
 void ho_tables(int np, HoTables* t);  // host
 // E[pair][s][t] = e^-tau between the pair's Chebyshev nodes (R x R doubles per stored pair)
-void launch_ho_cache_att(int np, int64_t npairs, const int* pairTgt, const int* src, const double* ncx,
-                         const double* ncy, const double* nrx, const double* nry, const double* stcoef,
-                         const Params* P, const HoTables* T, double* E, hipStream_t s);
+void launch_ho_cache_att(int np, int64_t npairs, const int* pairTgt, const int* src, const NodeBoxes& b,
+                         const double* stcoef, const Params* P, const HoTables* T, double* E, hipStream_t s);
 // expansions [node][R][K]; leafInfo as Plan::leafInfo; fT from launch_prepare
-void launch_ho_p2m(int np, int K, int nl, const int4* leafInfo, const double* ncx, const double* ncy,
-                   const double* nrx, const double* nry, const double* pxT, const double* pyT, const double* fT,
-                   const HoTables* T, double* mult, hipStream_t s);
+void launch_ho_p2m(int np, int K, int nl, const int4* leafInfo, const NodeBoxes& b, const TreePoints& pts,
+                   const double* fT, const HoTables* T, double* mult, hipStream_t s);
 // one level: child[n] = the four children of node n (< 0: empty, contributes nothing)
 void launch_ho_m2m(int np, int K, int nn, const int* nodes, const int4* child, const HoTables* T, double* mult,
                    hipStream_t s);
 // the pair lists of the mode-shared plan (Plan::attPtr / attSrc / attBlk over m2lTgt);
 // win: the offset form (K = 8); local = om_i x the unscaled sums, as k_m2l_hm stores them
-void launch_ho_m2l(int np, int K, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk,
-                   const double* E, const double* ncx, const double* ncy, const double* nrx, const double* nry,
-                   const HoTables* T, const HarmWeights& hw, const HarmWindow* win, const double* mult,
-                   double* local, hipStream_t s);
+void launch_ho_m2l(int np, int K, const PairList& pl, const double* E, const NodeBoxes& b, const HoTables* T,
+                   const HarmWeights& hw, const HarmWindow* win, const double* mult, double* local, hipStream_t s);
 // one level, top-down: local[n] += L2L of its parent's (complete) local
 void launch_ho_l2l(int np, int K, int nn, const int* nodes, const int* parent, const int* slot, const HoTables* T,
                    double* local, hipStream_t s);
-// out += scale * L2P (xsub: out = xsub - (out + scale * L2P)), output modes as k_down_tier
-void launch_ho_l2p(int np, int K, int nl, const int4* leafInfo, const double* ncx, const double* ncy,
-                   const double* nrx, const double* nry, const double* pxT, const double* pyT, const HoTables* T,
-                   const double* local, const int* operm, int64_t obase, int64_t ldo, double scale, double* out,
-                   const double* xsub, int64_t ldx, hipStream_t s);
+// out += scale * L2P (o.minuend: out = minuend - (out + scale * L2P)), output modes as k_down_tier
+void launch_ho_l2p(int np, int K, int nl, const int4* leafInfo, const NodeBoxes& b, const TreePoints& pts,
+                   const HoTables* T, const double* local, double scale, const OutRows& o, hipStream_t s);
 // ---- one mode on K columns on the mode-shared caches (mode_apply.hip): a
 // high-order handle, or a lean mode of an np = 4 one.  K in {2, 4, 5, 8}, the entry's factor
 // (E / r) T_id(c) formed once for all K columns.
 // launch_near_hm's unstaged kernel for mode id: out (stored) = scale * (near field + the
 // sigma_t diagonal when id = 0); fT from launch_prepare
-void launch_near_mode(int K, int id, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
-                      const int* nearPts, const int64_t* nearKOff, const double* E, const double* pxT,
-                      const double* pyT, const double* sigDiag, const double* fT, const int* operm, int64_t obase,
-                      int64_t ldo, double scale, double* out, hipStream_t s);
+void launch_near_mode(int K, int id, const NearList& nl, const double* E, const TreePoints& pts,
+                      const double* sigDiag, const double* fT, double scale, const OutRows& o, hipStream_t s);
 // launch_ho_m2l for mode id: mult as launch_ho_p2m / _m2m leave it, local = the plain sums
-void launch_ho_m2l_mode(int np, int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
-                        const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
-                        const double* nry, const HoTables* T, const double* mult, double* local, hipStream_t s);
+void launch_ho_m2l_mode(int np, int K, int id, const PairList& pl, const double* E, const NodeBoxes& b,
+                        const HoTables* T, const double* mult, double* local, hipStream_t s);
 // the same for 8 + KB columns with one factor formation per entry:
 // columns 0 .. 7 from multA / to localA ([node][R][8]), 8 .. 8+KB-1 from multB / to localB
 // ([node][R][KB]), KB = 2, 4, 5 or 8; a column's bits are launch_ho_m2l_mode's
-void launch_ho_m2l_mode_wide(int np, int KB, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
-                             const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
-                             const double* nry, const HoTables* T, const double* multA, const double* multB,
-                             double* localA, double* localB, hipStream_t s);
+void launch_ho_m2l_mode_wide(int np, int KB, int id, const PairList& pl, const double* E, const NodeBoxes& b,
+                             const HoTables* T, const double* multA, const double* multB, double* localA,
+                             double* localB, hipStream_t s);
 // The resident per-mode blocks of a high-order handle (mode_resident.hip):
 // F[pair] = (E / r) T_id(c) of every stored pair (owner / other: its target and source node),
 // R x R doubles per pair in 4 x 4 microtiles, and launch_ho_m2l_mode on them as an fp64 MFMA
 // product for 16 columns: columns 0 .. KA-1 from multA / to localA ([node][R][KA]), columns
 // 8 .. 8+KB-1 from multB / to localB (KB = 0: none), 1 <= KA <= 8, 0 <= KB <= 8.
 void launch_ho_mode_blocks(int np, int id, int64_t npairs, const int* owner, const int* other, const double* E,
-                           const double* ncx, const double* ncy, const double* nrx, const double* nry,
-                           const HoTables* T, double* F, hipStream_t s);
-void launch_ho_m2l_resident(int np, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
-                            const int* blk, const double* F, const double* multA, int KA, const double* multB,
-                            int KB, double* localA, double* localB, hipStream_t s);
+                           const NodeBoxes& b, const HoTables* T, double* F, hipStream_t s);
+void launch_ho_m2l_resident(int np, int id, const PairList& pl, const double* F, const double* multA, int KA,
+                            const double* multB, int KB, double* localA, double* localB, hipStream_t s);
 // The resident near blocks of one mode (mode_near_resident.hip):
 // F = mode_factor<true> of every stored entry of the directed near E blocks, per leaf at
 // nearFOff in 16-row tiles of 4 x 4 microtiles (rows padded to 4, sources to 16, the padding
 // zero), and launch_near_mode on them as an fp64 MFMA product for 16 columns: columns
-// 0 .. KA-1 from fTA ([tree position][kStride<KA>]) to outA, columns 8 .. 8+KB-1 from fTB to
-// outB (KB = 0: none), KA and KB in {2, 4, 5, 8}.  out (stored) as launch_near_mode's.
-void launch_near_mode_blocks(int id, int nl, const int4* leafInfo, const int64_t* nearPtsPtr, const int* nearPts,
-                             const int64_t* nearKOff, const int64_t* nearFOff, const double* E, const double* pxT,
-                             const double* pyT, double* F, hipStream_t s);
-void launch_near_resident(int id, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
-                          const int* nearPts, const int64_t* nearFOff, const double* F, const double* sigDiag,
-                          const double* fTA, int KA, const double* fTB, int KB, const int* operm, int64_t obase,
-                          double scale, double* outA, int64_t ldoA, double* outB, int64_t ldoB, hipStream_t s);
+// 0 .. KA-1 from fTA ([tree position][kStride<KA>]) to oA, columns 8 .. 8+KB-1 from fTB to
+// oB (KB = 0: none, oB = OutRows{}; oA's perm and base place both), KA and KB in {2, 4, 5, 8}.
+// out (stored) as launch_near_mode's.  launch_near_mode_blocks: nl.off = nearKOff, the E blocks'.
+void launch_near_mode_blocks(int id, const NearList& nl, const int64_t* nearFOff, const double* E,
+                             const TreePoints& pts, double* F, hipStream_t s);
+void launch_near_resident(int id, const NearList& nl, const double* F, const double* sigDiag, const double* fTA,
+                          int KA, const double* fTB, int KB, double scale, const OutRows& oA, const OutRows& oB,
+                          hipStream_t s);
 // The reduced-precision operator of a high-order handle (mode_apply_f32.hip, DESIGN.md
 // §3.18.5): both E arrays rounded to float with the same indexing (one launch), and
 // launch_near_mode / launch_ho_m2l_mode on the mirrors with the factor, the products and the
-// accumulators in fp32 (ncx / ncy: the near field takes its points relative to the target
+// accumulators in fp32 (the boxes: the near field takes its points relative to the target
 // leaf's centre).  Charges, multipoles, locals and `out` stay double.
 void launch_cache_f32(int64_t na, const double* a, float* af, int64_t nb, const double* b, float* bf, hipStream_t s);
-void launch_near_mode_f32(int K, int id, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
-                          const int* nearPts, const int64_t* nearKOff, const float* E, const double* ncx,
-                          const double* ncy, const double* pxT, const double* pyT, const double* sigDiag,
-                          const double* fT, const int* operm, int64_t obase, int64_t ldo, double scale, double* out,
-                          hipStream_t s);
-void launch_ho_m2l_mode_f32(int np, int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
-                            const int* blk, const float* E, const double* ncx, const double* ncy, const double* nrx,
-                            const double* nry, const HoTables* T, const double* mult, double* local, hipStream_t s);
+void launch_near_mode_f32(int K, int id, const NearList& nl, const float* E, const NodeBoxes& b,
+                          const TreePoints& pts, const double* sigDiag, const double* fT, double scale,
+                          const OutRows& o, hipStream_t s);
+void launch_ho_m2l_mode_f32(int np, int K, int id, const PairList& pl, const float* E, const NodeBoxes& b,
+                            const HoTables* T, const double* mult, double* local, hipStream_t s);
 // The relaxed-precision block operator of a high-order handle (block_f32.hip, DESIGN.md
 // §3.18.8): launch_near_hm's unstaged kernel (whole operator, near field on) and
 // launch_ho_m2l (no window) on the same mirrors, the entry of all K modes in fp32.
-void launch_near_hm_f32(int K, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
-                        const int* nearPts, const int64_t* nearKOff, const float* E, const double* ncx,
-                        const double* ncy, const double* pxT, const double* pyT, const double* sigDiag,
-                        const HarmWeights& hw, const double* fT, const int* operm, int64_t obase, int64_t ldo,
-                        double scale, double* out, hipStream_t s);
-void launch_ho_m2l_f32(int np, int K, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk,
-                       const float* E, const double* ncx, const double* ncy, const double* nrx, const double* nry,
-                       const HoTables* T, const HarmWeights& hw, const double* mult, double* local, hipStream_t s);
+void launch_near_hm_f32(int K, const NearList& nl, const float* E, const NodeBoxes& b, const TreePoints& pts,
+                        const double* sigDiag, const HarmWeights& hw, const double* fT, double scale,
+                        const OutRows& o, hipStream_t s);
+void launch_ho_m2l_f32(int np, int K, const PairList& pl, const float* E, const NodeBoxes& b, const HoTables* T,
+                       const HarmWeights& hw, const double* mult, double* local, hipStream_t s);
 // launch_m2l_hm for mode id on a rank-16 (np = 4) handle: mult [node][16][K] as the up tiers
 // leave it, local = the plain sums of every listed target (the down tiers read them as they
 // are); ntgt = 0 launches nothing.  A column's bits do not depend on K or on its slot.
-void launch_m2l_mode16(int K, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src, const int* blk,
-                       const double* E, const double* ncx, const double* ncy, const double* nrx, const double* nry,
-                       const Params* P, const double* mult, double* local, hipStream_t s);
+void launch_m2l_mode16(int K, int id, const PairList& pl, const double* E, const NodeBoxes& b, const Params* P,
+                       const double* mult, double* local, hipStream_t s);
 // ---- the block operator for S sources per read of the E blocks (block_multi.hip, DESIGN.md
 // §3.18.3): launch_ho_m2l (whole operator, no window) on S in {1, 2, 4} multipole buffers
 // mult + j * mstride into S local buffers local + j * lstride, each [node][R][K].  A
 // source's bits do not depend on S or on its slot.
-void launch_ho_m2l_src(int np, int K, int S, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
-                       const int* blk, const double* E, const double* ncx, const double* ncy, const double* nrx,
-                       const double* nry, const HoTables* T, const HarmWeights& hw, const double* mult,
-                       int64_t mstride, double* local, int64_t lstride, hipStream_t s);
+void launch_ho_m2l_src(int np, int K, int S, const PairList& pl, const double* E, const NodeBoxes& b,
+                       const HoTables* T, const HarmWeights& hw, const double* mult, int64_t mstride, double* local,
+                       int64_t lstride, hipStream_t s);
 
 // ---- cache build and helpers (kernels.hip)
-void launch_cache_m2l(int64_t npairs, const int* pairTgt, const int* src, const double* ncx, const double* ncy,
-                      const double* nrx, const double* nry, const double* stcoef, const Params* P, int mode,
-                      double* K, hipStream_t s);
+void launch_cache_m2l(int64_t npairs, const int* pairTgt, const int* src, const NodeBoxes& b, const double* stcoef,
+                      const Params* P, int mode, double* K, hipStream_t s);
 void launch_cache_near(int nl, const int* leaves, const int64_t* nearPtr, const int* nearSrc, const int64_t* nearKOff,
-                       const int64_t* begin, const int64_t* count, const double* pxT, const double* pyT,
-                       const double* stcoef, const Params* P, int mode, int maxSrc, double* K, hipStream_t s);
+                       const int64_t* begin, const int64_t* count, const TreePoints& pts, const double* stcoef,
+                       const Params* P, int mode, int maxSrc, double* K, hipStream_t s);
 // mode-shared cache: pair_kernel's mode argument kAttMode gives
 // e^-tau alone (0 at r = 0); launch_cache_near takes it as well
 constexpr int kAttMode = -1;
-void launch_cache_att_m2l(int64_t npairs, const int* pairTgt, const int* src, const double* ncx, const double* ncy,
-                          const double* nrx, const double* nry, const double* stcoef, const Params* P, double* E,
-                          hipStream_t s);
+void launch_cache_att_m2l(int64_t npairs, const int* pairTgt, const int* src, const NodeBoxes& b,
+                          const double* stcoef, const Params* P, double* E, hipStream_t s);
 void launch_sigma_diag(int64_t N, const double* pxT, const double* pyT, const double* stcoef, const Params* P,
                        double* out, hipStream_t s);
 void launch_permute(int64_t N, const int* perm, const double* orig, double* tree, hipStream_t s);

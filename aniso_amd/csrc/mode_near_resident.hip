@@ -194,33 +194,31 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW
     }
 }
 
-void launch_near_mode_blocks(int id, int nl, const int4* leafInfo, const int64_t* nearPtsPtr, const int* nearPts,
-                             const int64_t* nearKOff, const int64_t* nearFOff, const double* E, const double* pxT,
-                             const double* pyT, double* F, hipStream_t s) {
-    if (nl <= 0) return;
+void launch_near_mode_blocks(int id, const NearList& nl, const int64_t* nearFOff, const double* E,
+                             const TreePoints& pts, double* F, hipStream_t s) {
+    if (nl.nl <= 0) return;
     if (id < 0) throw std::invalid_argument("resident near blocks: negative mode");
-    k_near_mode_blocks<<<nl, 256, 0, s>>>(leafInfo, nearPtsPtr, nearPts, nearKOff, nearFOff, E, pxT, pyT, id, F);
+    k_near_mode_blocks<<<nl.nl, 256, 0, s>>>(nl.leafInfo, nl.ptsPtr, nl.pts, nl.off, nearFOff, E, pts.px, pts.py, id, F);
     HIP_LAUNCH_CHECK();
 }
 
-void launch_near_resident(int id, int nl, int maxLeaf, const int4* leafInfo, const int64_t* nearPtsPtr,
-                          const int* nearPts, const int64_t* nearFOff, const double* F, const double* sigDiag,
-                          const double* fTA, int KA, const double* fTB, int KB, const int* operm, int64_t obase,
-                          double scale, double* outA, int64_t ldoA, double* outB, int64_t ldoB, hipStream_t s) {
-    if (nl <= 0) return;
+void launch_near_resident(int id, const NearList& nl, const double* F, const double* sigDiag, const double* fTA,
+                          int KA, const double* fTB, int KB, double scale, const OutRows& oA, const OutRows& oB,
+                          hipStream_t s) {
+    if (nl.nl <= 0) return;
     if (id < 0) throw std::invalid_argument("resident near field: negative mode");
     auto compiled = [](int k) { return k == 2 || k == 4 || k == 5 || k == 8; };
-    if (!compiled(KA) || (KB != 0 && !compiled(KB)) || (KB > 0 && (!fTB || !outB)))
+    if (!compiled(KA) || (KB != 0 && !compiled(KB)) || (KB > 0 && (!fTB || !oB.out)))
         throw std::invalid_argument("resident near field: unsupported column counts " + std::to_string(KA) + " + " +
                                     std::to_string(KB));
     auto stride = [](int k) { return k % 2 == 0 ? k : k + 1; };  // kStride<K>
     const double* sd = id == 0 ? sigDiag : nullptr;
-    if (maxLeaf <= 16)
-        k_near_resident<1, 3><<<nl, 64, 0, s>>>(leafInfo, nearPtsPtr, nearPts, nearFOff, F, sd, fTA, KA, stride(KA), fTB,
-                                                KB, stride(KB), operm, obase, scale, outA, ldoA, outB, ldoB);
+    if (nl.maxLeaf <= 16)
+        k_near_resident<1, 3><<<nl.nl, 64, 0, s>>>(nl.leafInfo, nl.ptsPtr, nl.pts, nl.off, F, sd, fTA, KA, stride(KA), fTB,
+                                                   KB, stride(KB), oA.perm, oA.base, scale, oA.out, oA.ld, oB.out, oB.ld);
     else
-        k_near_resident<4, 4><<<nl, 256, 0, s>>>(leafInfo, nearPtsPtr, nearPts, nearFOff, F, sd, fTA, KA, stride(KA), fTB,
-                                                 KB, stride(KB), operm, obase, scale, outA, ldoA, outB, ldoB);
+        k_near_resident<4, 4><<<nl.nl, 256, 0, s>>>(nl.leafInfo, nl.ptsPtr, nl.pts, nl.off, F, sd, fTA, KA, stride(KA), fTB,
+                                                    KB, stride(KB), oA.perm, oA.base, scale, oA.out, oA.ld, oB.out, oB.ld);
     HIP_LAUNCH_CHECK();
 }
 

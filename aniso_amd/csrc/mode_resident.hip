@@ -163,29 +163,29 @@ __global__ void __launch_bounds__(64 * ((NP * NP + 15) / 16))
 }
 
 void launch_ho_mode_blocks(int np, int id, int64_t npairs, const int* owner, const int* other, const double* E,
-                           const double* ncx, const double* ncy, const double* nrx, const double* nry,
-                           const HoTables* T, double* F, hipStream_t s) {
+                           const NodeBoxes& b, const HoTables* T, double* F, hipStream_t s) {
     if (npairs <= 0) return;
     if (id < 0) throw std::invalid_argument("resident mode blocks: negative mode");
-    if (np == 6) k_ho_mode_blocks<6><<<(unsigned)npairs, 256, 0, s>>>(owner, other, E, ncx, ncy, nrx, nry, T, id, F);
-    else if (np == 8) k_ho_mode_blocks<8><<<(unsigned)npairs, 256, 0, s>>>(owner, other, E, ncx, ncy, nrx, nry, T, id, F);
+    if (np == 6) k_ho_mode_blocks<6><<<(unsigned)npairs, 256, 0, s>>>(owner, other, E, b.cx, b.cy, b.rx, b.ry, T, id, F);
+    else if (np == 8) k_ho_mode_blocks<8><<<(unsigned)npairs, 256, 0, s>>>(owner, other, E, b.cx, b.cy, b.rx, b.ry, T, id, F);
     else throw std::invalid_argument("resident mode blocks: np must be 6 or 8");
     HIP_LAUNCH_CHECK();
 }
 
-void launch_ho_m2l_resident(int np, int id, int ntgt, const int* tgt, const int64_t* ptr, const int* src,
-                            const int* blk, const double* F, const double* multA, int KA, const double* multB,
-                            int KB, double* localA, double* localB, hipStream_t s) {
-    if (ntgt <= 0) return;
+void launch_ho_m2l_resident(int np, int id, const PairList& pl, const double* F, const double* multA, int KA,
+                            const double* multB, int KB, double* localA, double* localB, hipStream_t s) {
+    if (pl.ntgt <= 0) return;
     if (id < 0) throw std::invalid_argument("resident mode apply: negative mode");
     if (KA < 1 || KA > 8 || KB < 0 || KB > 8 || (KB > 0 && (!multB || !localB)))
         throw std::invalid_argument("resident mode apply: unsupported column counts " + std::to_string(KA) + " + " +
                                     std::to_string(KB));
     const double sgn = (id & 1) ? -1.0 : 1.0;
     if (np == 6)
-        k_ho_m2l_resident<6><<<ntgt, 192, 0, s>>>(tgt, ptr, src, blk, F, sgn, multA, KA, multB, KB, localA, localB);
+        k_ho_m2l_resident<6><<<pl.ntgt, 192, 0, s>>>(pl.tgt, pl.ptr, pl.src, pl.blk, F, sgn, multA, KA, multB, KB, localA,
+                                                     localB);
     else if (np == 8)
-        k_ho_m2l_resident<8><<<ntgt, 256, 0, s>>>(tgt, ptr, src, blk, F, sgn, multA, KA, multB, KB, localA, localB);
+        k_ho_m2l_resident<8><<<pl.ntgt, 256, 0, s>>>(pl.tgt, pl.ptr, pl.src, pl.blk, F, sgn, multA, KA, multB, KB, localA,
+                                                     localB);
     else
         throw std::invalid_argument("resident mode apply: np must be 6 or 8");
     HIP_LAUNCH_CHECK();

@@ -3,6 +3,7 @@ no device: the new entries are exported (public, or development for the pass lis
 argtypes and wrappers, and every argument error and refusal comes with its code before the
 device is touched (null or fake device pointers)."""
 import ctypes
+import gc
 
 import numpy as np
 import pytest
@@ -126,6 +127,11 @@ def test_order_4_is_refused_and_pointed_to_its_own_mixed_solve():
 
 
 def test_a_sharded_high_order_handle_is_refused():
+    # the handle of the test above is garbage in a reference cycle (pytest.raises holds its
+    # frame) and is destroyed when the collector next runs; aniso_destroy, like every call, resets
+    # this thread's last error: collect now, so that it cannot fall between a.cache_f32() below and
+    # the aniso_last_error that reads its message (as test_sharded_solve_cpu.py does)
+    gc.collect()
     a = _handle(np_=6, shard=(0, 2))
     N = a.N
     other = ctypes.c_void_p(4096 + 64 * N * 8)

@@ -144,11 +144,11 @@ def _apply(torch, a, cols, m):
 
 # ---- 1. applies, nothing resident
 
-@pytest.mark.parametrize("nrhs", [9, 11, 13, 16, 19, 25])
+@pytest.mark.parametrize("nrhs", [9, 11, 13, 14, 16, 19, 25])
 @pytest.mark.parametrize("shape", SHAPES, ids=_ID)
 def test_wide_applies_match_the_oracle_and_the_narrow_chunks_bit_for_bit(shape, nrhs):
-    """Modes 0, 1 (odd: the sign of a transposed block) and 2; second halves of 1 -> 2, 3 -> 4, 5
-    and 8 columns, then [16, 4] and [16, 16] with a padded half.  Rows of stride N + 7 in and
+    """Modes 0, 1 (odd: the sign of a transposed block) and 2; second halves of 1 -> 2, 3 -> 4, 5,
+    6 -> 8 (zero-padded to the full half) and 8 columns, then [16, 4] and [16, 16] with a padded half.  Rows of stride N + 7 in and
     N + 3 out with NaN in the gaps.  Every column <= 1e-10 from the oracle at the same order
     and bitwise what the same call gives with the setting off; the chunks are those of the
     route; the gaps and x are left alone.  forward_multi_dev likewise."""
