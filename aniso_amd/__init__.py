@@ -127,6 +127,12 @@ def lib():
             "aniso_block_solve_relaxed": [P, dp, dp, I, D, I, D, dp, I, ip, dp],
             "aniso_block_solve_relaxed_dev": [P, P, P, I, D, I, D, dp, I, ip, dp, P],
             "aniso_block_solve_relaxed_calls": [P, ip, I, ip],
+            "aniso_block_op_multi_f32_dev": [P, I, I, P, I64, P, I64, P],
+            "aniso_block_solve_multi_relaxed_dev": [P, I, P, I64, I, P, I64, I, D, I, D, ip, dp, dp, I, P],
+            "aniso_block_solve_multi_relaxed": [P, dp, I, I, dp, I, D, I, D, ip, dp],
+            "aniso_forward_solve_multi_relaxed_dev": [P, I, P, I64, I, P, I64, I, D, I, D, ip, dp, dp, I, P],
+            "aniso_forward_solve_multi_relaxed": [P, dp, I, I, dp, I, D, I, D, ip, dp],
+            "aniso_solve_multi_relaxed_calls": [P, ip, I, ip],
             "aniso_solve16_mixed_dev": [P, P, I64, P, I64, I, D, D, I, I, ip, ip, dp, P],
             "aniso_solve_mixed_dev": [P, I, P, I64, P, I64, I, D, D, I, I, ip, ip, ip, dp, P],
             "aniso_apply_block_dev": [P, I, P, I64, I, I, ip, dp, P, I64, I, P],
@@ -935,6 +941,120 @@ class Aniso:
                                              float(tol), int(maxit),
                                              iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(relres)))
         return X, iters, relres
+
+    # ---- relaxed precision for several sources (np = 6, 8)
+    def block_op_multi_f32_dev(self, which, X, Out, stream=None):
+        """block_op_multi_dev with the near field and the M2L in fp32 on the float mirrors
+        (aniso_block_op_multi_f32_dev): the same tensors and chunking; every source's rows are
+        block_op_f32_dev's of that source bit for bit.  np = 6, 8, unsharded, ks <= 8."""
+        import torch
+
+        nsrc, px = self._src_rows(X, "X")
+        _, po = self._src_rows(Out, "Out")
+        if nsrc >= 0 and Out.shape[0] != X.shape[0]:
+            raise AnisoError(1, f"Out must have X's {X.shape[0]} rows")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _check(lib().aniso_block_op_multi_f32_dev(self.address, int(which), nsrc, px, max(X.stride(0), self.N), po,
+                                                  max(Out.stride(0), self.N), ctypes.c_void_p(s)))
+        return Out
+
+    def block_solve_multi_relaxed_dev(self, Q, X, restart=80, tol=1e-11, maxit=5, relax=-1.0, rhs_is_charge=True,
+                                      stream=None):
+        """block_solve_multi_dev as relaxed GMRES (aniso_block_solve_multi_relaxed_dev): a step's
+        one operator call runs on block_op_multi_f32_dev's operator once the largest latest
+        residual estimate among the group's live sources is <= relax; forward(charge) and every
+        residual stay fp64.  relax < 0: 1e6 * tol; relax = 0: block_solve_multi_dev's bits.  A
+        source's bits depend on the sources beside it in its group.  Arguments and the returned
+        (iters, relres, hist) as block_solve_multi_dev."""
+        import torch
+
+        nsrc, pq = self._src_rows(Q, "Q")
+        _, px = self._src_rows(X, "X")
+        if nsrc >= 0 and X.shape[0] != Q.shape[0]:
+            raise AnisoError(1, f"X must have Q's {Q.shape[0]} rows")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        maxhist = max(1, min(int(restart) * int(maxit), 100000)) if restart > 0 and maxit > 0 else 1
+        n = max(nsrc, 0)
+        iters = np.zeros(n, dtype=np.int32)
+        relres = np.zeros(n)
+        hist = np.zeros((n, maxhist))
+        _check(lib().aniso_block_solve_multi_relaxed_dev(
+            self.address, nsrc, pq, max(Q.stride(0), self.N), int(bool(rhs_is_charge)), px, max(X.stride(0), self.N),
+            int(restart), float(tol), int(maxit), float(relax), iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+            _dp(relres), _dp(hist), maxhist, ctypes.c_void_p(s)))
+        return iters, relres, hist
+
+    def block_solve_multi_relaxed(self, Q, restart=80, tol=1e-11, maxit=5, relax=-1.0, rhs_is_charge=True, x0=None):
+        """The same on numpy arrays (aniso_block_solve_multi_relaxed), as block_solve_multi.
+        Returns (X of Q's shape, iters, relres)."""
+        Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
+        if Q.ndim != 2 or Q.shape[0] != self.ks * self.N:
+            raise AnisoError(1, f"Q must be (ks * N) x nsrc with ks * N = {self.ks * self.N}")
+        if x0 is None:
+            X = np.zeros(Q.shape, order="F")
+        else:
+            X = np.array(x0, dtype=np.float64, order="F")
+            if X.shape != Q.shape:
+                raise AnisoError(1, f"x0 must have Q's shape {Q.shape}")
+        k = Q.shape[1]
+        iters = np.zeros(k, dtype=np.int32)
+        relres = np.zeros(k)
+        _check(lib().aniso_block_solve_multi_relaxed(
+            self.address, _dp(Q), k, int(bool(rhs_is_charge)), _dp(X), int(restart), float(tol), int(maxit),
+            float(relax), iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(relres)))
+        return X, iters, relres
+
+    def forward_solve_multi_relaxed_dev(self, Q, X, restart=80, tol=1e-12, maxit=5, relax=-1.0, rhs_is_source=True,
+                                        stream=None):
+        """forward_solve_multi_dev under the relaxed rule per group of 8 (16 after set_wide)
+        columns (aniso_forward_solve_multi_relaxed_dev): the low operator is mode 0's f32 pass.
+        relax as block_solve_multi_relaxed_dev; arguments and the returned (iters, relres, hist)
+        as forward_solve_multi_dev."""
+        import torch
+
+        nrhs = int(Q.shape[0]) if isinstance(Q, torch.Tensor) and Q.dim() == 2 else -1
+        pq, px = _dev_rows(Q, nrhs, self.N, "Q"), _dev_rows(X, nrhs, self.N, "X")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        maxhist = max(1, min(int(restart) * int(maxit), 100000)) if restart > 0 and maxit > 0 else 1
+        iters = np.zeros(nrhs, dtype=np.int32)
+        relres = np.zeros(nrhs)
+        hist = np.zeros((nrhs, maxhist))
+        _check(lib().aniso_forward_solve_multi_relaxed_dev(
+            self.address, nrhs, pq, max(Q.stride(0), self.N), int(bool(rhs_is_source)), px, max(X.stride(0), self.N),
+            int(restart), float(tol), int(maxit), float(relax), iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+            _dp(relres), _dp(hist), maxhist, ctypes.c_void_p(s)))
+        return iters, relres, hist
+
+    def forward_solve_multi_relaxed(self, Q, restart=80, tol=1e-12, maxit=5, relax=-1.0, rhs_is_source=True, x0=None):
+        """The same on numpy arrays (aniso_forward_solve_multi_relaxed), as forward_solve_multi.
+        Returns (X (N x k), iters, relres)."""
+        Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
+        if Q.ndim != 2 or Q.shape[0] != self.N:
+            raise AnisoError(1, f"Q must be N x k with N = {self.N}")
+        if x0 is None:
+            X = np.zeros(Q.shape, order="F")
+        else:
+            X = np.array(x0, dtype=np.float64, order="F")
+            if X.shape != Q.shape:
+                raise AnisoError(1, f"x0 must have Q's shape {Q.shape}")
+        k = Q.shape[1]
+        iters = np.zeros(k, dtype=np.int32)
+        relres = np.zeros(k)
+        _check(lib().aniso_forward_solve_multi_relaxed(
+            self.address, _dp(Q), k, int(bool(rhs_is_source)), _dp(X), int(restart), float(tol), int(maxit),
+            float(relax), iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(relres)))
+        return X, iters, relres
+
+    def solve_multi_relaxed_calls(self):
+        """{precision, columns} of every operator call of the last block_solve_multi_relaxed(_dev)
+        or forward_solve_multi_relaxed(_dev), in order (aniso_solve_multi_relaxed_calls): an
+        (n, 2) int array, precision 64 or 32."""
+        n = ctypes.c_int()
+        _check(lib().aniso_solve_multi_relaxed_calls(self.address, None, 0, ctypes.byref(n)))
+        calls = np.zeros((max(n.value, 0), 2), dtype=np.int32)
+        _check(lib().aniso_solve_multi_relaxed_calls(self.address, calls.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                     n.value, ctypes.byref(n)))
+        return calls
 
     # ---- direct evaluation at chosen targets (DESIGN.md "Accuracy of the method")
     def mapping_direct(self, charge, id_, targets):

@@ -2368,7 +2368,7 @@ void Operator::blockMultiReserve(int S) {
 // (which = 2: x - mforward(x) through the L2P's minuend).  An absent source (nreal < S) is a
 // zero multipole buffer whose locals nobody reads.
 void Operator::blockMultiChunk(int which, int S, int nreal, const double* x, int64_t ldx, double* out, int64_t ldo,
-                               hipStream_t s) {
+                               hipStream_t s, ApplyPrec prec) {
     const int nb = ks, nm = 2 * ks - 1, K = nb == 1 ? 2 : rhs_padded(nb);
     const int64_t N = geo.N;
     std::vector<double> mix = blockMixes(nb, g, which != 0);
@@ -2378,6 +2378,11 @@ void Operator::blockMultiChunk(int which, int S, int nreal, const double* x, int
     if (!harmonicWeights(K, nm, ids.data(), mix.data(), hw))
         throw std::logic_error("multi-source block operator: the mode-shared caches are not ready");
     const double* sigT = which != 0 ? dSigmaT.as<double>() : nullptr;
+    // the relaxed-precision chunk: applyBlockHigh's f32 near field per source
+    // and the f32 M2L, on the mirrors the caller has built; every other stage is the fp64 one
+    const bool f32 = prec == ApplyPrec::F32;
+    if (f32 && ((dAttM2L.bytes && !dAttM2LF.p) || (dAttNear.bytes && !dAttNearF.p)))
+        throw std::logic_error("the f32 multi-source block operator: no float mirrors");
     blockMultiReserve(S);
     const size_t exp = hoDoubles(K);
     const CorrFold& cf = corrTable(K, nm, ids.data(), mix.data());
@@ -2401,7 +2406,8 @@ void Operator::blockMultiChunk(int which, int S, int nreal, const double* x, int
         const OutRows o = rowsOut(j);
         sp.start();
         prepareCharges(K, rowsIn(j), dFT.as<double>(), dCT.as<double>(), s);
-        nearUnstaged(K, hw, nullptr, kStageAll, o, s);
+        if (f32) nearUnstagedF32(K, hw, o, s);
+        else nearUnstaged(K, hw, nullptr, kStageAll, o, s);
         sp.end(4);
         corrections(K, cf, dFT.as<double>(), dCT.as<double>(), plan.ownBegin, plan.ownEnd, kStageAll, o, s);
         sp.end(6);
@@ -2409,8 +2415,12 @@ void Operator::blockMultiChunk(int which, int S, int nreal, const double* x, int
         sp.end(1);
     }
     sp.start();
-    launch_ho_m2l_src(np, K, S, pairList(), dAttM2L.as<double>(), nodeBoxes(), dHoTab.as<HoTables>(), hw,
-                      dMsMult.as<double>(), (int64_t)exp, dMsLocal.as<double>(), (int64_t)exp, s);
+    if (f32)
+        launch_ho_m2l_src_f32(np, K, S, pairList(), dAttM2LF.as<float>(), nodeBoxes(), dHoTab.as<HoTables>(), hw,
+                              dMsMult.as<double>(), (int64_t)exp, dMsLocal.as<double>(), (int64_t)exp, s);
+    else
+        launch_ho_m2l_src(np, K, S, pairList(), dAttM2L.as<double>(), nodeBoxes(), dHoTab.as<HoTables>(), hw,
+                          dMsMult.as<double>(), (int64_t)exp, dMsLocal.as<double>(), (int64_t)exp, s);
     sp.end(2);
     for (int j = 0; j < nreal; ++j) {
         const OutRows o = rowsOut(j);
@@ -2434,6 +2444,25 @@ void Operator::blockOpMultiDev(int which, int nsrc, const double* x, int64_t ldx
     for (int j0 = 0; j0 < nsrc; j0 += 4) {
         const int n = std::min(4, nsrc - j0);
         blockMultiChunk(which, n == 3 ? 4 : n, n, x + (size_t)j0 * ks * ldx, ldx, out + (size_t)j0 * ks * ldo, ldo, s);
+    }
+}
+
+// The relaxed-precision operator for several sources: blockOpMultiDev's
+// chunking on the f32 chunk.  What the handle rules out, the arguments and the state are
+// raised before the device is touched; the mirrors are built on first use, before any launch.
+void Operator::blockOpMultiF32Dev(int which, int nsrc, const double* x, int64_t ldx, double* out, int64_t ldo,
+                                  hipStream_t s) {
+    const char* const what = "aniso_block_op_multi_f32_dev";
+    blockOpF32Refuse(what);
+    if (!blockOpMultiCheck(what, which, nsrc, x, ldx, out, ldo)) return;
+    blockOpF32Ready(what);
+    checkDeviceErrors();
+    ensureDevice();
+    cacheF32();
+    for (int j0 = 0; j0 < nsrc; j0 += 4) {
+        const int n = std::min(4, nsrc - j0);
+        blockMultiChunk(which, n == 3 ? 4 : n, n, x + (size_t)j0 * ks * ldx, ldx, out + (size_t)j0 * ks * ldo, ldo, s,
+                        ApplyPrec::F32);
     }
 }
 

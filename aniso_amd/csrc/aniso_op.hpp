@@ -433,6 +433,33 @@ public:
                            hipStream_t s);
     int blockSolveMultiHost(const double* Q, int nsrc, bool rhsIsCharge, double* X, int restart, double tol, int maxit,
                             int* iters, double* relres);  // (ks N) x nsrc column-major
+    // --- the relaxed-precision multi-source operator and lockstep solves (DESIGN.md §3.18.10;
+    // np = 6, 8, unsharded, ks <= 8).  blockOpMultiF32Dev: blockOpMultiDev's chunking with the
+    // near field and the M2L in fp32 on the float mirrors (built on first use); a source's bits
+    // are blockOpF32Dev's.  The two solves are blockSolveMultiDev / forwardSolveMultiDev with
+    // the relaxed rule per GROUP: a step's one operator call runs on the f32 operator iff
+    // relax > 0 and the largest latest relative-residual estimate among the step's live columns
+    // is <= relax (step 0 of a cycle: the cycle's explicit relres).  Every residual, and
+    // forward(charge), stays fp64, so convergence and relres are decided as in the fp64 entries.
+    // Under the group rule a column's bits depend on the columns beside it -- the one property
+    // of the fp64 entries this gives up; identical calls still return equal bits.  relax < 0:
+    // kRelaxFactor x tol; relax = 0: the fp64 entry's launches and bits, no mirrors; NaN:
+    // invalid_argument.  Refusals (blockOpF32Refuse, the arguments, blockOpF32Ready) come before
+    // the device is touched; the mirrors and every buffer before the first launch.
+    // multiRelaxedCalls(): {64 | 32, columns} of every operator call of the last such solve.
+    void blockOpMultiF32Dev(int which, int nsrc, const double* x, int64_t ldx, double* out, int64_t ldo,
+                            hipStream_t s);
+    int blockSolveMultiRelaxedDev(int nsrc, const double* q, int64_t ldq, bool rhsIsCharge, double* x, int64_t ldx,
+                                  int restart, double tol, int maxit, double relax, int* iters, double* relres,
+                                  double* hist, int maxhist, hipStream_t s);
+    int blockSolveMultiRelaxedHost(const double* Q, int nsrc, bool rhsIsCharge, double* X, int restart, double tol,
+                                   int maxit, double relax, int* iters, double* relres);
+    int forwardSolveMultiRelaxedDev(int nrhs, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx,
+                                    int restart, double tol, int maxit, double relax, int* iters, double* relres,
+                                    double* hist, int maxhist, hipStream_t s);
+    int forwardSolveMultiRelaxedHost(const double* Q, int k, bool rhsIsSource, double* X, int restart, double tol,
+                                     int maxit, double relax, int* iters, double* relres);
+    const std::vector<std::pair<int, int>>& multiRelaxedCalls() const { return multiCalls; }
     // the same solve on a sharded handle with a communicator, every rank together
     // (DESIGN.md §3.17): rhs / x are this rank's owned slices in tree order, ks rows of
     // `owned` doubles at strides ldr / ldx (device).  Every branch is taken from
@@ -666,8 +693,10 @@ private:
     // blockOpMultiDev's chunk of S in {1, 2, 4} sources (nreal of them present, the rest zero)
     // on a high-order handle: its S multipole and S local buffers, and the chunk's rows padded
     // to the compiled block count (grown, never shrunk: a hipFree synchronises the device)
+    // prec = F32: the near field of applyBlockHigh's f32 route per source and
+    // the f32 M2L (block_multi_f32.hip) on the float mirrors, every other stage unchanged
     void blockMultiChunk(int which, int S, int nreal, const double* x, int64_t ldx, double* out, int64_t ldo,
-                         hipStream_t s);
+                         hipStream_t s, ApplyPrec prec = ApplyPrec::F64);
     void blockMultiReserve(int S);
     DevBuf dMsMult, dMsLocal, dMsIn, dMsOut;
     // mapping of a mode whose operators are not resident: one pass of the offset form
@@ -768,7 +797,22 @@ private:
         int64_t L;
         const char* what;
         std::function<void(int, const double*, double*)> A;
+        // the relaxed rule: Alow serves a step's call iff relax > 0 and the
+        // largest latest estimate among the step's live columns is <= relax; residuals stay on A
+        std::function<void(int, const double*, double*)> Alow = nullptr;
+        double relax = 0.0;
+        std::vector<std::pair<int, int>>* rec = nullptr;  // {64 | 32, columns} per operator call
     };
+    // the bodies of the multi-source solves, relaxed (relax > 0) or not
+    int blockSolveMultiRun(const char* what, int nsrc, const double* q, int64_t ldq, bool rhsIsCharge, double* x,
+                           int64_t ldx, int restart, double tol, int maxit, double relax, int* iters, double* relres,
+                           double* hist, int maxhist, std::vector<std::pair<int, int>>* rec, hipStream_t s);
+    int forwardSolveMultiRun(int nrhs, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx,
+                             int restart, double tol, int maxit, double relax, int* iters, double* relres,
+                             double* hist, int maxhist, std::vector<std::pair<int, int>>* rec, hipStream_t s);
+    // what the relaxed multi entries check before the device is touched; returns the relax in force
+    double multiRelaxedEnter(const char* what, bool block, double tol, double relax) const;
+    std::vector<std::pair<int, int>> multiCalls;  // multiRelaxedCalls()
     int colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* x, int64_t ldx, int m, double tol, int maxit,
                        int* iters, double* relres, double* hist, int maxhist, hipStream_t s);
     // the restarted GMRES of one system: the loop blockSolveDev and blockSolveShardedDev share

@@ -430,6 +430,62 @@ int aniso_block_solve_multi(aniso_handle h, const double* Q, int nsrc, int rhs_i
     });
 }
 
+int aniso_block_op_multi_f32_dev(aniso_handle h, int which, int nsrc, const double* x, int64_t ldx, double* out,
+                                 int64_t ldo, void* stream) {
+    ENTER(h);
+    return guarded([&] { get(h).blockOpMultiF32Dev(which, nsrc, x, ldx, out, ldo, (hipStream_t)stream); });
+}
+
+int aniso_block_solve_multi_relaxed_dev(aniso_handle h, int nsrc, const double* q, int64_t ldq, int rhs_is_charge,
+                                        double* x, int64_t ldx, int restart, double tol, int maxit, double relax,
+                                        int* iters, double* relres, double* hist, int maxhist, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        get(h).blockSolveMultiRelaxedDev(nsrc, q, ldq, rhs_is_charge != 0, x, ldx, restart, tol, maxit, relax, iters,
+                                         relres, maxhist > 0 ? hist : nullptr, maxhist, (hipStream_t)stream);
+    });
+}
+
+int aniso_block_solve_multi_relaxed(aniso_handle h, const double* Q, int nsrc, int rhs_is_charge, double* X,
+                                    int restart, double tol, int maxit, double relax, int* iters, double* relres) {
+    ENTER(h);
+    return guarded([&] {
+        get(h).blockSolveMultiRelaxedHost(Q, nsrc, rhs_is_charge != 0, X, restart, tol, maxit, relax, iters, relres);
+    });
+}
+
+int aniso_forward_solve_multi_relaxed_dev(aniso_handle h, int nrhs, const double* q, int64_t ldq, int rhs_is_source,
+                                          double* x, int64_t ldx, int restart, double tol, int maxit, double relax,
+                                          int* iters, double* relres, double* hist, int maxhist, void* stream) {
+    ENTER(h);
+    return guarded([&] {
+        get(h).forwardSolveMultiRelaxedDev(nrhs, q, ldq, rhs_is_source != 0, x, ldx, restart, tol, maxit, relax, iters,
+                                           relres, maxhist > 0 ? hist : nullptr, maxhist, (hipStream_t)stream);
+    });
+}
+
+int aniso_forward_solve_multi_relaxed(aniso_handle h, const double* Q, int k, int rhs_is_source, double* X,
+                                      int restart, double tol, int maxit, double relax, int* iters, double* relres) {
+    ENTER(h);
+    return guarded([&] {
+        get(h).forwardSolveMultiRelaxedHost(Q, k, rhs_is_source != 0, X, restart, tol, maxit, relax, iters, relres);
+    });
+}
+
+int aniso_solve_multi_relaxed_calls(aniso_handle h, int* calls, int cap, int* n) {
+    ENTER(h);
+    return guarded([&] {
+        CHECK_PTR(n);
+        const auto& c = get(h).multiRelaxedCalls();
+        *n = (int)c.size();
+        if (calls)
+            for (int i = 0; i < cap && i < (int)c.size(); ++i) {
+                calls[2 * i] = c[i].first;
+                calls[2 * i + 1] = c[i].second;
+            }
+    });
+}
+
 int aniso_forward_solve_calls(aniso_handle h, int* counts, int cap, int* n) {
     ENTER(h);
     return guarded([&] {

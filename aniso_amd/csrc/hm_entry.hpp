@@ -188,4 +188,36 @@ __device__ __forceinline__ void hm_entry_f32(float e, float dx, float dy2, const
     for (int i = 0; i < K; ++i) o[i] = __builtin_fmaf(T[i], v, o[i]);
 }
 
+// One entry in fp32 for S sources (block_multi_f32.hip): hm_rows_src's
+// sharing -- r^2, 1 / r, c, T_0 .. T_{K-1} and E / r formed once -- around hm_entry_f32<K,
+// false>'s chain per source, operation by operation (it starts with fmaf(T_1, xw[1], xw[0])).
+// A source reads nothing of another source: its bits are hm_entry_f32's, whatever S and its
+// slot.
+template <int K, int S>
+__device__ __forceinline__ void hm_rows_src_f32(float e, float dx, float dy2, const float (&xw)[S][K],
+                                                float (&o)[S][K]) {
+    static_assert(K >= 2, "at least T_0 and T_1");
+    const float r2 = __builtin_fmaf(dx, dx, dy2);
+    const float ri = rsqrt_nr_f32(r2);
+    const float c = dx * ri, c2 = 2.0f * c, er = e * ri;  // (2 c: c + c exactly, with no add to contract)
+    float T[K];
+    T[0] = 1.0f;
+    T[1] = c;
+#pragma unroll
+    for (int i = 2; i < K; ++i) T[i] = __builtin_fmaf(c2, T[i - 1], -T[i - 2]);
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        float v = __builtin_fmaf(T[1], xw[s][1], xw[s][0]);
+#pragma unroll
+        for (int b = 2; b < K; ++b) v = __builtin_fmaf(T[b], xw[s][b], v);
+        // T_0 = 1: hm_entry_f32's o[0] = fmaf(1, v er, o[0]) is an add of the product v er, which
+        // the build's floating-point contraction fuses in every instance of k_ho_m2l_f32.  Written
+        // out here, so that no instance of this function can come out otherwise.
+        o[s][0] = __builtin_fmaf(v, er, o[s][0]);
+        v *= er;  // (E / r) V
+#pragma unroll
+        for (int i = 1; i < K; ++i) o[s][i] = __builtin_fmaf(T[i], v, o[s][i]);
+    }
+}
+
 }  // namespace aniso

@@ -520,6 +520,11 @@ void launch_m2l_mode16(int K, int id, const PairList& pl, const double* E, const
 void launch_ho_m2l_src(int np, int K, int S, const PairList& pl, const double* E, const NodeBoxes& b,
                        const HoTables* T, const HarmWeights& hw, const double* mult, int64_t mstride, double* local,
                        int64_t lstride, hipStream_t s);
+// The same launch with the entry in fp32 on the float mirror of E (block_multi_f32.hip,
+// DESIGN.md §3.18.10): a source's local expansion is launch_ho_m2l_f32's, bit for bit.
+void launch_ho_m2l_src_f32(int np, int K, int S, const PairList& pl, const float* E, const NodeBoxes& b,
+                           const HoTables* T, const HarmWeights& hw, const double* mult, int64_t mstride,
+                           double* local, int64_t lstride, hipStream_t s);
 
 // ---- cache build and helpers (kernels.hip)
 void launch_cache_m2l(int64_t npairs, const int* pairTgt, const int* src, const NodeBoxes& b, const double* stcoef,

@@ -1300,6 +1300,16 @@ int Operator::forwardSolveMultiDev(int nrhs, const double* q, int64_t ldq, bool 
                                    int maxhist, hipStream_t s) {
     if (!forwardSolveMultiCheck("aniso_forward_solve_multi_dev", nrhs, q, ldq, x, ldx, iters, restart, tol, maxit))
         return 0;
+    return forwardSolveMultiRun(nrhs, q, ldq, rhsIsSource, x, ldx, restart, tol, maxit, 0.0, iters, relres, hist, maxhist,
+                                nullptr, s);
+}
+
+// forwardSolveMultiDev's body (the arguments checked); relax > 0: the relaxed rule of
+// DESIGN.md §3.18.10 with mode 0's f32 pass as the low operator (chunks of 8 whatever the
+// group size), every call recorded in rec
+int Operator::forwardSolveMultiRun(int nrhs, const double* q, int64_t ldq, bool rhsIsSource, double* x, int64_t ldx,
+                                   int restart, double tol, int maxit, double relax, int* iters, double* relres,
+                                   double* hist, int maxhist, std::vector<std::pair<int, int>>* rec, hipStream_t s) {
     ensureDevice();
     checkDeviceErrors();
     // the group size: 16 with the wide setting on (a step's live columns are one operator
@@ -1315,12 +1325,20 @@ int Operator::forwardSolveMultiDev(int nrhs, const double* q, int64_t ldq, bool 
              "forward solve: the Krylov bases of (restart + 1) x " + g + " x N = " + std::to_string(m + 1) + " x " + g +
                  " x " + std::to_string(N),
              tail.c_str());
+    if (relax > 0.0) cacheF32();  // the float mirrors, if this is their first use: before anything is launched
     arn_small_kernel_attrs();
     solveCalls.clear();
     const double* sigS = sigmaSTree();
     // the shared loop over mode 0's x - K_0(sigma_s x)
-    const ColsSolve cs{N, "forward solve",
-                       [&](int nrows, const double* in, double* w) { modeApplyDev(0, nrows, in, N, sigS, true, w, N, s); }};
+    ColsSolve cs{N, "forward solve",
+                 [&](int nrows, const double* in, double* w) { modeApplyDev(0, nrows, in, N, sigS, true, w, N, s); }};
+    if (relax > 0.0) {
+        cs.Alow = [&](int nrows, const double* in, double* w) {
+            modeApplyDev(0, nrows, in, N, sigS, true, w, N, s, false, ApplyPrec::F32);
+        };
+        cs.relax = relax;
+    }
+    cs.rec = rec;
     int steps = 0;
     try {
         for (int r0 = 0; r0 < nrhs; r0 += G) {
@@ -1389,6 +1407,7 @@ int Operator::colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* 
         int total = 0, used = 0, nh = 0;
         bool done = false, conv = false, frozen = false, xzero = false;
         double normb = 0.0, rel = 0.0, r = 0.0;
+        double est = 0.0;  // the latest relative-residual estimate: the cycle's explicit relres, then each step's
     } col[arn::kMaxCols];
     auto slot = [&](int c) {
         arn::ColSlot sl{};
@@ -1411,12 +1430,15 @@ int Operator::colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* 
         }
     };
     // A on the rows `src` of table t (nrows of them), W's compact rows out: one operator call
-    auto op = [&](const arn::ColTable& t, int nrows, int row, int64_t ldv) {
+    // (low: on the relaxed rule's f32 operator)
+    auto op = [&](const arn::ColTable& t, int nrows, int row, int64_t ldv, bool low) {
         arn::k_arn_gather_cols<<<dim3(nb, nrows), arn::kThreads, 0, s>>>(N, row, ldv, t, In);
         HIP_LAUNCH_CHECK();
-        cs.A(nrows, In, W);
+        (low ? cs.Alow : cs.A)(nrows, In, W);
         solveCalls.push_back(nrows);
+        if (cs.rec) cs.rec->emplace_back(low ? 32 : 64, nrows);
     };
+    const bool relaxed = cs.Alow && cs.relax > 0.0;
     {  // |b|^2 and |x|^2 per column
         arn::ColTable tb{}, tx{};
         for (int c = 0; c < ng; ++c) {
@@ -1461,7 +1483,7 @@ int Operator::colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* 
             }  // else w = x = 0: r = b
             hstat[4 * c + 2] = -1.0;
         }
-        if (nop > 0) op(tg, nop, 0, 0);
+        if (nop > 0) op(tg, nop, 0, 0, false);  // every residual is fp64
         arn::k_arn_resid_cols<<<dim3(nb, (unsigned)cols.size()), arn::kThreads, 0, s>>>(N, t);
         HIP_LAUNCH_CHECK();
         for (size_t a = 0; a < cols.size(); ++a) t.c[a].w = t.c[a].V;
@@ -1477,6 +1499,7 @@ int Operator::colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* 
             col[c].rel = hstat[4 * c];
             col[c].r = hstat[4 * c + 1];
             col[c].conv = col[c].rel <= tol;
+            col[c].est = col[c].rel;
         }
     };
     std::vector<int> act, live;
@@ -1504,7 +1527,10 @@ int Operator::colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* 
                 t.c[a].w = W + (size_t)a * N;
                 hstat[4 * live[a] + 2] = -1.0;
             }
-            op(t, nl, j, N);
+            // the relaxed rule, per group: f32 iff every live column's latest estimate is <= relax
+            bool low = relaxed;
+            for (int a = 0; low && a < nl; ++a) low = col[live[a]].est <= cs.relax;
+            op(t, nl, j, N, low);
             arn::launch_project_cols(N, j + 1, N, t, nl, s);
             runs(live, [&](int c0, int len) {
                 arn::k_arn_coef<<<len, arn::kThreads, arn::coef_lds(j), s>>>(m, j, st + (size_t)c0 * sts,
@@ -1525,6 +1551,7 @@ int Operator::colsSolveGroup(const ColsSolve& cs, ColsWork& cw, int ng, double* 
                 const double rel = hstat[4 * c], rnext = hstat[4 * c + 1];
                 ++k.total;
                 k.used = j + 1;
+                k.est = rel;
                 if (hist && k.nh < maxhist) hist[(size_t)c * maxhist + k.nh++] = rel;
                 k.frozen = rel <= tol || rnext == 0.0;  // converged (estimate) or lucky breakdown
             }
@@ -1791,6 +1818,16 @@ int Operator::blockSolveMultiDev(int nsrc, const double* q, int64_t ldq, bool rh
                                  int restart, double tol, int maxit, int* iters, double* relres, double* hist,
                                  int maxhist, hipStream_t s) {
     if (!blockSolveMultiCheck("aniso_block_solve_multi_dev", nsrc, q, ldq, x, ldx, iters, restart, tol, maxit)) return 0;
+    return blockSolveMultiRun("multi-source block solve", nsrc, q, ldq, rhsIsCharge, x, ldx, restart, tol, maxit, 0.0,
+                              iters, relres, hist, maxhist, nullptr, s);
+}
+
+// blockSolveMultiDev's body (the arguments checked); relax > 0: the relaxed rule of DESIGN.md
+// §3.18.10 with blockOpMultiF32Dev(2, ...) as the low operator, every call recorded in rec
+int Operator::blockSolveMultiRun(const char* what, int nsrc, const double* q, int64_t ldq, bool rhsIsCharge, double* x,
+                                 int64_t ldx, int restart, double tol, int maxit, double relax, int* iters,
+                                 double* relres, double* hist, int maxhist, std::vector<std::pair<int, int>>* rec,
+                                 hipStream_t s) {
     ensureDevice();
     checkDeviceErrors();
     constexpr int G = arn::kNarrowCols;
@@ -1800,17 +1837,21 @@ int Operator::blockSolveMultiDev(int nsrc, const double* q, int64_t ldq, bool rh
     const std::string g = std::to_string(gmax);
     ColsWork cw;  // X: the group's guesses as compact vectors
     cw.alloc(L, G, gmax, m, true,
-             "multi-source block solve: the Krylov bases of (restart + 1) x " + g + " x ks x N = " +
+             std::string(what) + ": the Krylov bases of (restart + 1) x " + g + " x ks x N = " +
                  std::to_string(m + 1) + " x " + g + " x " + std::to_string(ks) + " x " + std::to_string(N),
              "work rows", [&] {
                  if (highOrder() && ks <= kMaxRhs) blockMultiReserve(gmax == 3 ? 4 : gmax);
              });
     DevBuf &bB = cw.B, &bX = cw.X;
+    if (relax > 0.0) cacheF32();  // the float mirrors, if this is their first use: before anything is launched
     arn_small_kernel_attrs();
     solveCalls.clear();
-    const ColsSolve cs{L, "multi-source block solve", [&](int nrows, const double* in, double* w) {
-                           blockOpMultiDev(2, nrows, in, N, w, N, s);
-                       }};
+    ColsSolve cs{L, what, [&](int nrows, const double* in, double* w) { blockOpMultiDev(2, nrows, in, N, w, N, s); }};
+    if (relax > 0.0) {
+        cs.Alow = [&](int nrows, const double* in, double* w) { blockOpMultiF32Dev(2, nrows, in, N, w, N, s); };
+        cs.relax = relax;
+    }
+    cs.rec = rec;
     int steps = 0;
     try {
         for (int r0 = 0; r0 < nsrc; r0 += kBlockGroup) {
@@ -1823,6 +1864,7 @@ int Operator::blockSolveMultiDev(int nsrc, const double* q, int64_t ldq, bool rh
             if (rhsIsCharge) {
                 blockOpMultiDev(0, ng, qg, ldq, bB.as<double>(), N, s);
                 solveCalls.push_back(ng);
+                if (rec) rec->emplace_back(64, ng);
             } else {
                 HIP_CHECK(hipMemcpy2DAsync(bB.p, N * sizeof(double), qg, ldq * sizeof(double), N * sizeof(double),
                                            (size_t)ng * ks, hipMemcpyDeviceToDevice, s));
@@ -1854,6 +1896,90 @@ int Operator::blockSolveMultiHost(const double* Q, int nsrc, bool rhsIsCharge, d
     HIP_CHECK(hipMemcpyAsync(dx.p, X, bytes, hipMemcpyHostToDevice, own));
     const int steps = blockSolveMultiDev(nsrc, dq.as<double>(), geo.N, rhsIsCharge, dx.as<double>(), geo.N, restart, tol,
                                          maxit, iters, relres, nullptr, 0, own);
+    HIP_CHECK(hipMemcpyAsync(X, dx.p, bytes, hipMemcpyDeviceToHost, own));
+    HIP_CHECK(hipStreamSynchronize(own));
+    return steps;
+}
+
+// ---- the relaxed multi-source solves ----
+
+// What the handle itself rules out (np = 4, a shard; the block solve: ks > 8), then NaN: before
+// the arguments, the state and the device.  Returns the relax in force (< 0: the default).
+double Operator::multiRelaxedEnter(const char* what, bool block, double tol, double relax) const {
+    if (block) {
+        blockOpF32Refuse(what);
+    } else {
+        if (!highOrder())
+            throw std::logic_error(std::string(what) + ": the f32 mode operator is built for np = 6, 8; the "
+                                                       "reduced-precision route of an np = 4 handle is aniso_solve_mixed_dev");
+        refuseHoShard(what);
+        if (plan.nranks > 1) throw std::logic_error(std::string(what) + " on a sharded handle (use an unsharded handle)");
+    }
+    if (std::isnan(relax)) throw std::invalid_argument(std::string(what) + ": relax is NaN");
+    return relax < 0.0 ? kRelaxFactor * tol : relax;
+}
+
+int Operator::blockSolveMultiRelaxedDev(int nsrc, const double* q, int64_t ldq, bool rhsIsCharge, double* x,
+                                        int64_t ldx, int restart, double tol, int maxit, double relax, int* iters,
+                                        double* relres, double* hist, int maxhist, hipStream_t s) {
+    const char* const what = "aniso_block_solve_multi_relaxed_dev";
+    relax = multiRelaxedEnter(what, true, tol, relax);
+    multiCalls.clear();
+    if (!blockSolveMultiCheck(what, nsrc, q, ldq, x, ldx, iters, restart, tol, maxit)) return 0;
+    blockOpF32Ready(what);
+    return blockSolveMultiRun("relaxed multi-source block solve", nsrc, q, ldq, rhsIsCharge, x, ldx, restart, tol, maxit,
+                              relax, iters, relres, hist, maxhist, &multiCalls, s);
+}
+
+// (ks N) x nsrc column-major host arrays: one staging copy each way
+int Operator::blockSolveMultiRelaxedHost(const double* Q, int nsrc, bool rhsIsCharge, double* X, int restart,
+                                         double tol, int maxit, double relax, int* iters, double* relres) {
+    const char* const what = "aniso_block_solve_multi_relaxed";
+    multiRelaxedEnter(what, true, tol, relax);
+    multiCalls.clear();
+    if (!blockSolveMultiCheck(what, nsrc, Q, geo.N, X, geo.N, iters, restart, tol, maxit)) return 0;
+    blockOpF32Ready(what);
+    ensureDevice();
+    const size_t bytes = (size_t)nsrc * ks * geo.N * sizeof(double);
+    DevBuf dq, dx;
+    dq.alloc(bytes);
+    dx.alloc(bytes);
+    HIP_CHECK(hipMemcpyAsync(dq.p, Q, bytes, hipMemcpyHostToDevice, own));
+    HIP_CHECK(hipMemcpyAsync(dx.p, X, bytes, hipMemcpyHostToDevice, own));
+    const int steps = blockSolveMultiRelaxedDev(nsrc, dq.as<double>(), geo.N, rhsIsCharge, dx.as<double>(), geo.N,
+                                                restart, tol, maxit, relax, iters, relres, nullptr, 0, own);
+    HIP_CHECK(hipMemcpyAsync(X, dx.p, bytes, hipMemcpyDeviceToHost, own));
+    HIP_CHECK(hipStreamSynchronize(own));
+    return steps;
+}
+
+int Operator::forwardSolveMultiRelaxedDev(int nrhs, const double* q, int64_t ldq, bool rhsIsSource, double* x,
+                                          int64_t ldx, int restart, double tol, int maxit, double relax, int* iters,
+                                          double* relres, double* hist, int maxhist, hipStream_t s) {
+    const char* const what = "aniso_forward_solve_multi_relaxed_dev";
+    relax = multiRelaxedEnter(what, false, tol, relax);
+    multiCalls.clear();
+    if (!forwardSolveMultiCheck(what, nrhs, q, ldq, x, ldx, iters, restart, tol, maxit)) return 0;
+    return forwardSolveMultiRun(nrhs, q, ldq, rhsIsSource, x, ldx, restart, tol, maxit, relax, iters, relres, hist,
+                                maxhist, &multiCalls, s);
+}
+
+// N x k column-major host arrays: one staging copy each way
+int Operator::forwardSolveMultiRelaxedHost(const double* Q, int k, bool rhsIsSource, double* X, int restart,
+                                           double tol, int maxit, double relax, int* iters, double* relres) {
+    const char* const what = "aniso_forward_solve_multi_relaxed";
+    multiRelaxedEnter(what, false, tol, relax);
+    multiCalls.clear();
+    if (!forwardSolveMultiCheck(what, k, Q, geo.N, X, geo.N, iters, restart, tol, maxit)) return 0;
+    ensureDevice();
+    const size_t bytes = (size_t)k * geo.N * sizeof(double);
+    DevBuf dq, dx;
+    dq.alloc(bytes);
+    dx.alloc(bytes);
+    HIP_CHECK(hipMemcpyAsync(dq.p, Q, bytes, hipMemcpyHostToDevice, own));
+    HIP_CHECK(hipMemcpyAsync(dx.p, X, bytes, hipMemcpyHostToDevice, own));
+    const int steps = forwardSolveMultiRelaxedDev(k, dq.as<double>(), geo.N, rhsIsSource, dx.as<double>(), geo.N, restart,
+                                                  tol, maxit, relax, iters, relres, nullptr, 0, own);
     HIP_CHECK(hipMemcpyAsync(X, dx.p, bytes, hipMemcpyDeviceToHost, own));
     HIP_CHECK(hipStreamSynchronize(own));
     return steps;

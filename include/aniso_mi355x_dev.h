@@ -178,6 +178,13 @@ int aniso_forward_solve_mixed_calls(aniso_handle h, int *calls, int cap, int *n)
  * *n = their number, calls (cap >= 0 entries, may be NULL) = the precision of each, 64 (the
  * cycle-boundary residuals and the Arnoldi matvecs before the switch) or 32.  Host only. */
 int aniso_block_solve_relaxed_calls(aniso_handle h, int *calls, int cap, int *n);
+/* ---- the relaxed multi-source solves ---- */
+/* every operator call of the handle's last aniso_block_solve_multi_relaxed(_dev) or
+ * aniso_forward_solve_multi_relaxed(_dev) call, in order: *n = their number, calls (cap >= 0
+ * pairs, may be NULL) = {precision, columns} of each, precision 64 (the block solve's
+ * forward(charge), every residual, the Arnoldi calls before the group's switch) or 32.  The
+ * calls and their column counts are aniso_forward_solve_calls's.  Host only. */
+int aniso_solve_multi_relaxed_calls(aniso_handle h, int *calls, int cap, int *n);
 
 #ifdef __cplusplus
 }

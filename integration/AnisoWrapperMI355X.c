@@ -22,6 +22,9 @@
  * and the same solve for several charges in one medium, one stacked charge per column of Q
  * (the right-hand sides forward(Q(:, s)) are formed in the call):
  *   [U, relres, iters] = AnisoWrapperMI355X('solveMulti', h, Q, 80, 1e-11, 5);
+ * and on a high-order handle the same with the operator passes in fp32 once the group's
+ * residual estimates are <= relax (relax < 0: the library's default, 1e6 * tol):
+ *   [U, relres, iters] = AnisoWrapperMI355X('solveMultiRelaxed', h, Q, 80, 1e-11, 5, -1);
  *
  * MATLAB is absent from this image and from the GPU box: tests/test_integration.py
  * compiles this file for syntax against a declaration-only mex.h (tests/mex_stub).
@@ -156,17 +159,20 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                                (int)mxGetScalar(prhs[5]), NULL, 0, &iters, &relres));
         if (nlhs > 1) plhs[1] = mxCreateDoubleScalar(relres);
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar((double)iters);
-    } else if (!strcmp(op, "solveMulti")) {
+    } else if (!strcmp(op, "solveMulti") || !strcmp(op, "solveMultiRelaxed")) {
         /* aniso.m's solve (aniso.m:159-173) for several charges in one medium:
          *   [U, relres, iters] = ('solveMulti', h, Q, restart, tol, maxit)
          * Q is (ks * N) x nsrc, one stacked charge per column; column s of U solves
          * x - mforward(x) = forward(Q(:, s)) (aniso.m:160).  On a high-order handle the
-         * sources share the reads of the M2L blocks, 4 per pass (aniso_block_solve_multi) */
+         * sources share the reads of the M2L blocks, 4 per pass (aniso_block_solve_multi).
+         *   [U, relres, iters] = ('solveMultiRelaxed', h, Q, restart, tol, maxit, relax)
+         * is the same solve as relaxed GMRES (aniso_block_solve_multi_relaxed; np = 6, 8) */
+        const int relaxed = !strcmp(op, "solveMultiRelaxed");
         aniso_handle h;
         int64_t len, total, nsrc, s;
         mxArray *scratch, *relres, *steps;
         int* iters;
-        need(nrhs, 6, op);
+        need(nrhs, relaxed ? 7 : 6, op);
         h = handle_of(prhs[1]);
         len = num_blocks(h) * num_nodes(h);
         total = (int64_t)mxGetNumberOfElements(prhs[2]);
@@ -178,8 +184,14 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         steps = mxCreateDoubleMatrix((size_t)nsrc, 1, mxREAL);
         scratch = mxCreateNumericMatrix((size_t)nsrc, 1, mxINT64_CLASS, mxREAL); /* room for nsrc ints; MATLAB frees it */
         iters = (int*)mxGetData(scratch);
-        CALL(aniso_block_solve_multi(h, mxGetPr(prhs[2]), (int)nsrc, 1, mxGetPr(plhs[0]), (int)mxGetScalar(prhs[3]),
-                                     mxGetScalar(prhs[4]), (int)mxGetScalar(prhs[5]), iters, mxGetPr(relres)));
+        if (relaxed)
+            CALL(aniso_block_solve_multi_relaxed(h, mxGetPr(prhs[2]), (int)nsrc, 1, mxGetPr(plhs[0]),
+                                                 (int)mxGetScalar(prhs[3]), mxGetScalar(prhs[4]),
+                                                 (int)mxGetScalar(prhs[5]), mxGetScalar(prhs[6]), iters,
+                                                 mxGetPr(relres)));
+        else
+            CALL(aniso_block_solve_multi(h, mxGetPr(prhs[2]), (int)nsrc, 1, mxGetPr(plhs[0]), (int)mxGetScalar(prhs[3]),
+                                         mxGetScalar(prhs[4]), (int)mxGetScalar(prhs[5]), iters, mxGetPr(relres)));
         for (s = 0; s < nsrc; ++s) mxGetPr(steps)[s] = (double)iters[s];
         if (nlhs > 1) plhs[1] = relres;
         if (nlhs > 2) plhs[2] = steps;
