@@ -91,16 +91,11 @@ Operator::Operator(int sz, int d, int ks_, double g_, int ns_, int np_, int maxL
     plan.nearSymmetric = ks == 1;
     if (const char* e = std::getenv("ANISO_NEAR_SYMMETRIC")) plan.nearSymmetric = e[0] == '1';
     plan.maxCanon = ks == 1 ? kMaxCanon : kMaxCanonBlock;
-    // ANISO_NEAR_HS_SYM=1: the harmonic block apply stores the U pairs between owned
-    // leaves once (Plan::nearSymHs; K <= 5: the canonical loop's registers leave K = 8
-    // at one wave per SIMD).  Off by default: measured slower
-    plan.nearSymHs = false;
-    if (const char* e = std::getenv("ANISO_NEAR_HS_SYM")) plan.nearSymHs = ks > 1 && ks <= 5 && e[0] == '1';
     // ANISO_UPPER_PARTIAL=0: a sharded one-collective matvec exchanges the tier-0 roots
     // and runs the upper up tiers on every rank (the round-4 form)
     if (const char* e = std::getenv("ANISO_UPPER_PARTIAL")) plan.xUpPartialIn = std::atoi(e) != 0;
     if (highOrder()) {  // the mode-shared caches only (ks = 1 too), directed near lists, no rank-16 schedules
-        plan.nearSymmetric = plan.nearSymHs = false;
+        plan.nearSymmetric = false;
         plan.listsOnly = true;
         hoShard = shardRanks != 0;  // the rank's own lists; setShard keeps refusing
     }
@@ -119,19 +114,10 @@ Operator::Operator(int sz, int d, int ks_, double g_, int ns_, int np_, int maxL
     if (const char* e = std::getenv("ANISO_FUSE_SUB")) fuseSub = e[0] != '0';
     if (const char* e = std::getenv("ANISO_TOP_SPIN_LIMIT")) topSpinLimit = (unsigned)std::strtoul(e, nullptr, 10);
     if (const char* e = std::getenv("ANISO_TOP_TRACE")) topTraceOn = std::atoi(e) != 0;
-    if (const char* e = std::getenv("ANISO_NEAR_IN_TOP")) nearInTop = std::atoi(e) != 0;
     if (const char* e = std::getenv("ANISO_NEAR_EARLY")) nearEarly = std::atoi(e) != 0;
     if (const char* e = std::getenv("ANISO_ONE_EXCHANGE")) oneXOn = std::atoi(e) != 0;
-    if (const char* e = std::getenv("ANISO_SHARD_NEAR_EARLY")) shardNearEarly = std::atoi(e) != 0;
-    if (const char* e = std::getenv("ANISO_UP_TAILS")) upTailsOn = std::atoi(e) != 0;
-    if (const char* e = std::getenv("ANISO_NEAR_AFTER_PACK")) nearAfterPack = std::atoi(e) != 0;
-    if (const char* e = std::getenv("ANISO_SIDE_PRIO")) sidePrio = std::atoi(e);
     if (const char* e = std::getenv("ANISO_DET_PER_TARGET")) detPerTarget = std::atoi(e) != 0;
     if (const char* e = std::getenv("ANISO_NEAR_UP")) nearUpOn = std::atoi(e) != 0;
-    if (const char* e = std::getenv("ANISO_NEAR_ORDER")) nearOrderUp = std::strcmp(e, "first") != 0;
-    hmRing = hm_ring_depth();
-    if (const char* e = std::getenv("ANISO_HM_WPE")) hmWpe = std::atoi(e);
-    if (const char* e = std::getenv("ANISO_NEAR_WPE")) nearWpe = std::atoi(e);
     if (const char* e = std::getenv("ANISO_TOP_FUSED")) topFusedMode = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("ANISO_DIRECT_TARGETS")) directChunk = std::min(std::max(std::atoi(e), 1), 65535);
     sigma_s.assign(geo.N, 0.0);
@@ -219,14 +205,8 @@ void Operator::ensureDevice() {
     HIP_CHECK(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
     // side stream at normal priority (a high-priority one measured slower, r01f; the
     // lowest priority 11-25 % slower, r04l; a CU-masked one serialised the two streams
-    // on a rank of 8: 0.455 against 0.235 ms, r06q).  ANISO_SIDE_PRIO: -1 lowest, 1 highest
-    if (sidePrio != 0) {
-        int lo = 0, hi = 0;
-        HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIP_CHECK(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, sidePrio < 0 ? lo : hi));
-    } else {
-        HIP_CHECK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-    }
+    // on a rank of 8: 0.455 against 0.235 ms, r06q)
+    HIP_CHECK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
     HIP_CHECK(hipEventCreateWithFlags(&evFork, hipEventDisableTiming));
     HIP_CHECK(hipEventCreateWithFlags(&evJoin, hipEventDisableTiming));
     HIP_CHECK(hipEventCreateWithFlags(&evDirect, hipEventDisableTiming));
@@ -252,16 +232,6 @@ void Operator::ensureDevice() {
     up(dNcy, tree.ncy);
     up(dNrx, tree.nrx);
     up(dNry, tree.nry);
-    {  // per node {cx, cy, rx, ry}: the source box one LDS-DMA lane pair fetches (k_m2l_hcr)
-        std::vector<double> g4((size_t)tree.nn * 4);
-        for (int i = 0; i < tree.nn; ++i) {
-            g4[4 * (size_t)i] = tree.ncx[i];
-            g4[4 * (size_t)i + 1] = tree.ncy[i];
-            g4[4 * (size_t)i + 2] = tree.nrx[i];
-            g4[4 * (size_t)i + 3] = tree.nry[i];
-        }
-        up(dNodeGeo, g4);
-    }
     up(dBegin, tree.begin);
     up(dCount, tree.count);
     up(dParent, tree.parent);
@@ -402,7 +372,7 @@ void Operator::ensureWork(int K) {
     HIP_CHECK(hipMemset(dMult.p, 0, dMult.bytes));
     HIP_CHECK(hipMemset(dLocal.p, 0, dLocal.bytes));
     dM2LPart.alloc((size_t)std::max(plan.m2lCanon, 1) * kRank * K * sizeof(double));
-    dNearPart.alloc((size_t)std::max<int64_t>({plan.nearPartTotal, plan.hsPartTotal, 1}) * K * sizeof(double));
+    dNearPart.alloc((size_t)std::max<int64_t>(plan.nearPartTotal, 1) * K * sizeof(double));
 }
 
 static std::vector<int4> to_int4(const std::vector<std::array<int, 4>>& v) {
@@ -470,31 +440,13 @@ void Operator::uploadPlan() {
     up(dDnChainFold, plan.dnChainFold);
     up(dDnNearPtr, plan.dnNearPtr);
     up(dDnNearOff, plan.dnNearOff);
-    dNearPart.alloc((size_t)std::max<int64_t>({plan.nearPartTotal, plan.hsPartTotal, 1}) * workK * sizeof(double));
-    if (plan.nearSymHsOn) {
-        up(dHsPtsPtr, plan.hsPtsPtr);
-        up(dHsLoc, plan.hsLoc);
-        up(dHsKOff, plan.hsKOff);
-        std::vector<int2> hs(plan.hsSym.size());
-        for (size_t i = 0; i < hs.size(); ++i) hs[i] = make_int2(plan.hsSym[i][0], plan.hsSym[i][1]);
-        up(dHsSym, hs);
-        up(dHsSrcPtr, plan.hsSrcPtr);
-        up(dHsSrc, plan.hsSrc);
-        up(dHsDst, plan.hsDst);
-        up(dNearSelfRow, plan.nearSelfRow);
-        up(dNearGrpInPtr, plan.nearGrpInPtr);
-        up(dNearGrpIn, plan.nearGrpIn);
-    }
+    dNearPart.alloc((size_t)std::max<int64_t>(plan.nearPartTotal, 1) * workK * sizeof(double));
     up(dLeafInfo, to_int4(plan.leafInfo));
     up(dNearPtsPtr, plan.nearPtsPtr);
     up(dNearPts, plan.nearPts);
     up(dXT0Tasks, plan.xT0Tasks);
     up(dXOwnT0Tasks, plan.xOwnT0Tasks);
     up(dXUpTask, plan.xUpTask);
-    up(dXT0Part, plan.xT0Part);
-    up(dXUpRoots, plan.xUpRoots);
-    dXUpCnt.alloc(std::max<size_t>(plan.xUpRoots.size(), 1) * sizeof(unsigned));
-    HIP_CHECK(hipMemset(dXUpCnt.p, 0, dXUpCnt.bytes));  // each tail resets its counter after use
     up(dNearUpGrp, plan.nearUpGrp);
     up(dNearGrpEarly, plan.nearGrpEarly);
     up(dNearGrpLate, plan.nearGrpLate);
@@ -727,7 +679,7 @@ void Operator::cacheResident(const char* api, const char* built, const char* nou
     if (!coeffSet || !attReady || !modes[id].tables)
         throw std::runtime_error(a + " before aniso_set_coeff and aniso_cache(" + std::to_string(id) +
                                  ") or aniso_cache_block");
-    if (needDirected && (plan.nearSymHsOn || plan.nearPartTotal != 0))
+    if (needDirected && plan.nearPartTotal != 0)
         throw std::logic_error(a + ": the near E blocks are not stored directed");
     if (rb.blocks.count(id)) return;
     ensureDevice();
@@ -813,11 +765,9 @@ void Operator::buildAttCache() {
     const int64_t npairs = (int64_t)(plan.attOwner.size() + plan.hmCopyOwner.size());  // stored blocks + copies
     const size_t rank = (size_t)np * np;
     dAttM2L.alloc((size_t)npairs * rank * rank * sizeof(double));
-    // the near blocks in the layout the harmonic near field reads: directed, or with
-    // symmetric U storage its own lists (Plan::buildNearHs)
-    const bool hs = plan.nearSymHsOn;
-    const std::vector<int64_t>& nptr = hs ? plan.hsSrcPtr : plan.nearPtr;
-    dAttNear.alloc((size_t)(hs ? plan.hsKTotal : plan.nearKTotal) * sizeof(double));
+    // the near blocks in the layout the harmonic near field reads: directed
+    const std::vector<int64_t>& nptr = plan.nearPtr;
+    dAttNear.alloc((size_t)plan.nearKTotal * sizeof(double));
     dSigDiag.alloc((size_t)geo.N * sizeof(double));
     int maxSrc = 1;
     for (size_t li = 0; li < plan.leaves.size(); ++li) maxSrc = std::max<int>(maxSrc, (int)(nptr[li + 1] - nptr[li]));
@@ -827,10 +777,9 @@ void Operator::buildAttCache() {
     else
         launch_cache_att_m2l(npairs, dAttOwner.as<int>(), dAttOther.as<int>(), nodeBoxes(), dStCoef.as<double>(), P,
                              dAttM2L.as<double>(), own);
-    launch_cache_near((int)plan.leaves.size(), dLeaves.as<int>(), (hs ? dHsSrcPtr : dNearPtr).as<int64_t>(),
-                      (hs ? dHsSrc : dNearSrc).as<int>(), (hs ? dHsKOff : dNearKOff).as<int64_t>(),
-                      dBegin.as<int64_t>(), dCount.as<int64_t>(), treePoints(), dStCoef.as<double>(), P, kAttMode,
-                      maxSrc, dAttNear.as<double>(), own);
+    launch_cache_near((int)plan.leaves.size(), dLeaves.as<int>(), dNearPtr.as<int64_t>(), dNearSrc.as<int>(),
+                      dNearKOff.as<int64_t>(), dBegin.as<int64_t>(), dCount.as<int64_t>(), treePoints(),
+                      dStCoef.as<double>(), P, kAttMode, maxSrc, dAttNear.as<double>(), own);
     launch_sigma_diag(geo.N, dPxT.as<double>(), dPyT.as<double>(), dStCoef.as<double>(), P, dSigDiag.as<double>(),
                       own);
     if (!highOrder()) {  // the deterministic sums' bound: rank 16 only
@@ -1191,7 +1140,7 @@ void Operator::prepareCharges(int K, const InRows& in, double* fT, double* cT, h
 void Operator::nearUnstaged(int K, const HarmWeights& hw, const HarmWindow* win, int mask, const OutRows& o,
                             hipStream_t s) {
     launch_near_hm(K, nearList(), dAttNear.as<double>(), treePoints(), dSigDiag.as<double>(), hw, dFT.as<double>(), mask,
-                   kScale, o, nullptr, nullptr, nullptr, 0, nullptr, nearWpe, s, nullptr, win);
+                   kScale, o, nullptr, nullptr, nullptr, 0, nullptr, s, nullptr, win);
 }
 
 void Operator::nearUnstagedF32(int K, const HarmWeights& hw, const OutRows& o, hipStream_t s) {
@@ -1275,12 +1224,12 @@ void Operator::hoDownPass(int K, double* local, const OutRows& o, hipStream_t s)
 // tier k: `list` (nullptr: every task of the tier) names ntask tasks; fT / cT (nullptr: none)
 // receive the charges its P2M forms; recv / send: the tier-0 roots of a sharded apply
 void Operator::upTier16(int K, int k, const int* list, int ntask, double* fT, double* cT, const double* recv,
-                        double* send, unsigned* zeroCnt, const UpTail* tail, const InRows& in, hipStream_t s) {
+                        double* send, unsigned* zeroCnt, const InRows& in, hipStream_t s) {
     launch_up_tier(K, ntask, plan.upTierTask[k], list, plan.upTierMaxTask[k], dUpDesc.as<int4>(), dUpGrpFix.as<int>(),
                    dUpNode.as<int>(), dUpCode.as<int4>(), dUpGeom.as<double4>(), dUpLeaf.as<int2>(), dPxT.as<double>(),
                    dPyT.as<double>(), in.x, in.ld, in.tree ? 1 : 0, dPerm.as<int>(), in.sigT, dWT.as<double>(), fT, cT,
                    dParams.as<Params>(), dMult.as<double>(), recv ? dXRootSlot.as<int>() : nullptr, recv,
-                   send ? dXSendSlot.as<int>() : nullptr, send, s, zeroCnt, tail);
+                   send ? dXSendSlot.as<int>() : nullptr, send, s, zeroCnt);
 }
 
 // L2L + L2P + the gathered partials (nearPart: transposed near products; hpart: the clustered
@@ -1321,7 +1270,7 @@ void Operator::padRowsOut(const double* group, int nb, int64_t n, double* out, i
 // and the down pass.  `call` says which of these, and what else, this call is (ApplyCall).
 void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, const double* sigT, int nterm,
                           const int* ids, const double* mixes, double* out, int64_t ldo, bool treeOut, hipStream_t s,
-                          int mask, ApplyCall& call) {
+                          int mask, const ApplyCall& call) {
     const int phase = call.phase;
     double* const rootsSend = call.rootsSend;
     const double* const rootsRecv = call.rootsRecv;
@@ -1391,22 +1340,13 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     // the upper tiers ride in the M2L launch (k_top_m2l_hc) when every leaf is in the
     // bottom tier: the near field then forks after it
     const bool topFused = harmonic && (mask & kStageFar) && topFusedOn() && !upPartial && !win;
-    // ANISO_NEAR_IN_TOP: the near field (+ corrections) as the last blocks of that
-    // launch (the one-block M2L form; a shard's phase 1 then leaves it to phase 2)
-    const bool ringOn = hmRing > 0 && hm_ring_xl(K, plan.hmMaxLds, hmRing) >= 0;
-    // symmetric U storage (Plan::nearSymHsOn): the harmonic near field reads its own
-    // column lists and leaves the partner products of other groups to the down pass
-    const bool hsSym = harmonic && plan.nearSymHsOn;
-    const bool nearFused = topFused && overlapOn() && nearInTop && !ringOn && !hsSym && plan.nearCorrOk &&
-                           near_hs_fusable((int)plan.leaves.size(), plan.nearMaxLeaf, plan.nsMax,
-                                           dNearLoc.as<uint16_t>(), &nc, mask);
-    const bool fork = harmonic && overlapOn() && !nearFused;
+    const bool fork = harmonic && overlapOn();
     const hipStream_t sn = fork ? side : s;
     // the staged near field with its fused corrections forms its charges from the
     // input itself (NearHsArgs::xin), so it needs nothing from the up pass: it forks
     // at the start of the apply, beside the latency-bound up tiers, and the up pass
     // stores no fT / cT (ANISO_NEAR_EARLY=0: it forks after the up pass and reads them)
-    const bool nearIn = harmonic && nearEarly && !nearFused && plan.nearCorrOk && (mask & kStageNear) &&
+    const bool nearIn = harmonic && nearEarly && plan.nearCorrOk && (mask & kStageNear) &&
                         near_hs_fusable((int)plan.leaves.size(), plan.nearMaxLeaf, plan.nsMax,
                                         dNearLoc.as<uint16_t>(), &nc, mask);
     // the one-collective exchange (blockOpShardedDev): phase 1 runs the own tier-0
@@ -1423,25 +1363,9 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     const int forkTier = phase == 0 && !topFused ? std::max(ntier - 1, 0) : plan.upLastLeafTier;
     // one up tier; a sharded apply's bottom tier runs this rank's tasks only (list)
     // and stores its tier-0 roots into send, its next tier reads the gathered ones
-    // the partial tasks of the upper multipoles ride as tails of the own tier-0 launch
-    // (shardedExchange decides: ExchangeForm::upTails; they write into the send buffer)
-    UpTail tail;
-    if (upPartial && call.exch.upTails) {
-        tail.partOf = dXT0Part.as<int2>();
-        const size_t sb = plan.xUpRoots.size() * 16 * kRank * K * sizeof(double);
-        if (dXUpStage.bytes < sb) dXUpStage.alloc(sb);
-        tail.stage = dXUpStage.as<double>();
-        tail.cnt = dXUpCnt.as<unsigned>();
-        tail.nroots = dXUpRoots.as<int>();
-        tail.task = dXUpTask.as<int>();
-        tail.rec = dXUpRec.as<double>();
-        tail.nPeer = (int)oxRootParts;
-        tail.peerOff = dOxRootSend.as<int64_t>();
-        tail.buf = dOxSendBuf.as<double>();
-    }
-    auto upTier = [&](int k, const int* list, int ntask, const double* recv, double* send, const UpTail* tl = nullptr) {
+    auto upTier = [&](int k, const int* list, int ntask, const double* recv, double* send) {
         unsigned* const zeroCnt = topFused && k == 0 ? dTopCnt.as<unsigned>() : nullptr;
-        upTier16(K, k, list, ntask, fTw, cTw, recv, send, zeroCnt, tl, in, s);
+        upTier16(K, k, list, ntask, fTw, cTw, recv, send, zeroCnt, in, s);
         if (fork && !nearIn && k == forkTier) HIP_CHECK(hipEventRecord(evFork, s));
     };
     auto tierTasks = [&](int k) { return plan.upTierTask[k + 1] - plan.upTierTask[k]; };
@@ -1457,7 +1381,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     // the bottom up tier inside the staged near field (one GPU, serial: the near field
     // runs first, so tier 1 -- in the fused launch or its own -- finds the tier-0 roots)
     // (K <= 5: the 4-wave near kernel with the tail spills at K = 8)
-    const bool nearUp = phase == 0 && nearIn && !fork && nearUpTier() && ntier >= 1 && !hsSym && K <= 5;
+    const bool nearUp = phase == 0 && nearIn && !fork && nearUpTier() && ntier >= 1 && K <= 5;
     if (nearUp) {
         nin.upMult = dMult.as<double>();
         nin.upGrp = dNearUpGrp.as<int>();
@@ -1468,21 +1392,6 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         nin.upNry = dNry.as<double>();
         nin.zeroCnt = topFused ? dTopCnt.as<unsigned>() : nullptr;
     }
-    if (hsSym) {
-        nin.nearSym = dHsSym.as<int2>();
-        nin.colDst = dHsDst.as<int>();
-        nin.selfRow = dNearSelfRow.as<uint16_t>();
-        nin.nearPart = dNearPart.as<double>();
-        nin.grpInPtr = dNearGrpInPtr.as<int>();
-        nin.grpIn = dNearGrpIn.as<int>();
-        nin.grpSlots = plan.nearGrpSlots;
-    }
-    const int64_t* const hmPtsPtr = (hsSym ? dHsPtsPtr : dNearPtsPtr).as<int64_t>();
-    const int64_t* const hmKOff = (hsSym ? dHsKOff : dNearKOff).as<int64_t>();
-    const uint16_t* const hmLoc = (hsSym ? dHsLoc : dNearLoc).as<uint16_t>();
-    NearList hmList = nearList();  // (symmetric U storage: its own column lists)
-    hmList.ptsPtr = hmPtsPtr;
-    hmList.off = hmKOff;
     // near field + corrections (they need only fT / cT, or with nearIn the input)
     auto nearStage = [&] {
         if (fork) HIP_CHECK(hipStreamWaitEvent(side, evFork, 0));
@@ -1491,9 +1400,9 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         if (harmonic) {
             // the corrections ride in the staged near kernel (d = 1, its table holds
             // every stencil neighbour; Plan::nearCorrRow)
-            corrFused = launch_near_hm(K, hmList, dAttNear.as<double>(), treePoints(), dSigDiag.as<double>(), hw,
-                                       dFT.as<double>(), mask, kScale, o, hmLoc, dNsPtr.as<int64_t>(), dNsPts.as<int>(),
-                                       plan.nsMax, plan.nearCorrOk ? &nc : nullptr, nearWpe, sn, &nin, win);
+            corrFused = launch_near_hm(K, nearList(), dAttNear.as<double>(), treePoints(), dSigDiag.as<double>(), hw,
+                                       dFT.as<double>(), mask, kScale, o, dNearLoc.as<uint16_t>(), dNsPtr.as<int64_t>(),
+                                       dNsPts.as<int>(), plan.nsMax, plan.nearCorrOk ? &nc : nullptr, sn, &nin, win);
         } else if (plan.nearPartTotal > 0) {
             // symmetric U storage (K = 1 handles): one launch per term; the transposed
             // products go to partials summed over the terms
@@ -1522,9 +1431,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     const int ncl = (int)plan.hmClPtr.size() - 1;
     HcArgs hca{dHmClPtr.as<int>(), dHmTgt.as<int>(), dHmPtr.as<int64_t>(), dHmNDir.as<int>(), dHmSrc.as<int>(),
                      dHmBlk.as<int>(), dHmSlot.as<int>(), dAttM2L.as<double>(), dNcx.as<double>(), dNcy.as<double>(),
-                     dNrx.as<double>(), dNry.as<double>(), P, hw, dMult.as<double>(), dLocal.as<double>(),
-                     dNodeGeo.as<double>()};
-    hca.wpe = hmWpe;
+                     dNrx.as<double>(), dNry.as<double>(), P, hw, dMult.as<double>(), dLocal.as<double>()};
     const bool halo = !plan.hmHaloNode.empty();
     if (halo) {  // the halo form: partials of the cross-cluster partner products (Plan::hmHaloPtr)
         const size_t hb = plan.hmHaloNode.size() * kRank * K * sizeof(double);
@@ -1532,11 +1439,6 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         hca.haloPtr = dHmHaloPtr.as<int>();
         hca.haloPos = dHmHaloPos.as<int>();
         hca.hpart = dHmPart.as<double>();
-    }
-    if (hmRing > 0) {
-        const int xl = hm_ring_xl(K, plan.hmMaxLds, hmRing);
-        hca.ring = xl < 0 ? 0 : hmRing;
-        hca.ringXL = xl > 0;
     }
     auto m2lClusters = [&](int c0, int c1, hipStream_t st) {
         HcArgs a = hca;
@@ -1565,24 +1467,20 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         // order) the near field and the corrections read
         e0 = tm ? mark(s) : -1;
         eStart = e0;
-        const bool nearEarlyGroups = nearIn && oneX && !plan.nearGrpEarly.empty() && shardNearEarly && !passShard;
-        const bool earlyAfterPack = nearEarlyGroups && phase == 1 && ntier >= 1 && call.exch.pack;
-        auto nearEarlyStage = [&] {
+        if (nearIn && oneX && !plan.nearGrpEarly.empty() && !passShard) {
             // one-collective form: the groups that read only the own range start now,
-            // beside the own tier-0 tasks (or after the pack); the rest waits for the
-            // exchange (phase 2)
+            // beside the own tier-0 tasks; the rest waits for the exchange (phase 2)
             nin.grpList = dNearGrpEarly.as<int>();
             nin.ngrp = (int)plan.nearGrpEarly.size();
             if (fork) HIP_CHECK(hipEventRecord(evFork, s));
             nearStage();
             if (!fork && tm) e0 = mark(s);
-        };
-        if (nearEarlyGroups && !earlyAfterPack) nearEarlyStage();
+        }
         // the fork point is the start of the apply, but the near field's launch is issued
         // after the bottom up tier's, so the dispatcher tends to hand the up tasks their
         // workgroup slots first (0.6-1.2 % per block matvec on one GPU, 1.6 % on a rank
-        // of 8, r04z; ANISO_NEAR_ORDER=first issues it first)
-        const bool nearAfterUp = nearIn && !oneX && fork && nearOrderUp && phase == 0 && ntier >= 1;
+        // of 8, r04z)
+        const bool nearAfterUp = nearIn && !oneX && fork && phase == 0 && ntier >= 1;
         if (nearIn && !oneX && !passShard) {  // the near field first: beside the up pass (fork) or before it (serial)
             if (fork) HIP_CHECK(hipEventRecord(evFork, s));
             if (!nearAfterUp) {
@@ -1597,14 +1495,9 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         }
         if (phase == 1 && ntier >= 1) {
             if (oneX)
-                upTier(0, dXOwnT0Tasks.as<int>(), (int)plan.xOwnT0Tasks.size(), nullptr, upPartial ? nullptr : rootsSend,
-                       tail.partOf ? &tail : nullptr);
+                upTier(0, dXOwnT0Tasks.as<int>(), (int)plan.xOwnT0Tasks.size(), nullptr,
+                       upPartial ? nullptr : rootsSend);
             else upTier(0, dXT0Tasks.as<int>(), (int)plan.xT0Tasks.size(), nullptr, rootsSend);
-            if (earlyAfterPack) {  // the pack's partial tasks take their slots before the near groups do
-                call.exch.pack(s);
-                call.exch.issued = true;
-                nearEarlyStage();
-            }
         }
         for (int k = nearUp ? 1 : 0; k < (topFused ? 1 : ntier) && phase == 0; ++k) {
             upTier(k, nullptr, tierTasks(k), nullptr, nullptr);
@@ -1616,7 +1509,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         if (phase == 1) {
             const int ep = tm ? mark(s) : -1;
             span(1, e0, ep);
-            if ((ntier < 1 || forkTier == 0) && !nearFused && !nearDone && !oneX && !passShard) {
+            if ((ntier < 1 || forkTier == 0) && !nearDone && !oneX && !passShard) {
                 nearStage();
                 nearDone = true;
             }
@@ -1637,8 +1530,8 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
         if (phase == 2) span(0, pend.ePack, ex);  // the caller's root exchange
         else eStart = ex;                         // a repeat's total span is its own
         if (oneX && !nearDone) {  // the rest of the near field after the one exchange (it filled the input's halo)
-            // (ANISO_SHARD_NEAR_EARLY=0, and every pass: every group here, in one launch)
-            const bool late = shardNearEarly && !passShard;
+            // (a pass: every group here, in one launch)
+            const bool late = !passShard;
             nin.grpList = late ? dNearGrpLate.as<int>() : nullptr;
             nin.ngrp = late ? (int)plan.nearGrpLate.size() : 0;
             if (fork) HIP_CHECK(hipEventRecord(evFork, s));
@@ -1662,7 +1555,7 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     const int ep = tr ? mark(s) : -1;
     span(1, e0, ep);
     StageSpans sp(*this, s, eStart, ep);  // the tail's spans: M2L, gather, down pass, total
-    if (!nearDone && !nearFused) {
+    if (!nearDone) {
         // a sharded pass in the two-collective form: the side stream waits here, behind the
         // previous window's k_add_rows, which reads the rows this near field writes
         if (passShard && fork) HIP_CHECK(hipEventRecord(evFork, s));
@@ -1690,19 +1583,13 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
             ta.spinLimit = topSpinLimit;
             ta.steals = dTopSteals.as<unsigned>();
             HIP_CHECK(hipHostGetDevicePointer((void**)&ta.err, topErr, 0));
-            const NearHsArgs na{(int)plan.leaves.size(), plan.nsMax, dLeafInfo.as<int4>(), hmPtsPtr, hmLoc,
-                          dNsPtr.as<int64_t>(), dNsPts.as<int>(), hmKOff, dAttNear.as<double>(), dPxT.as<double>(),
-                          dPyT.as<double>(), dSigDiag.as<double>(), hw, dFT.as<double>(), o.perm, o.base, ldo, mask,
-                          kScale, out, nc};
-
             if (topTraceOn) {
-                topTraceNear = nearFused ? (na.nl + 15) / 16 : 0;
-                topTraceBlocks = ta.nUp + ncl + topTraceNear;
+                topTraceBlocks = ta.nUp + ncl;
                 if (dTopTrace.bytes < (size_t)topTraceBlocks * 4 * sizeof(int64_t))
                     dTopTrace.alloc((size_t)topTraceBlocks * 4 * sizeof(int64_t));
                 ta.trace = dTopTrace.as<int64_t>();
             }
-            launch_top_m2l_hc(K, ncl, plan.hmMaxLds, ua, ta, hca, nearFused ? &na : nullptr, s);
+            launch_top_m2l_hc(K, ncl, plan.hmMaxLds, ua, ta, hca, s);
         } else if (clustered) {
             m2lClusters(0, ncl, s);
         } else if (harmonic) {
@@ -1722,9 +1609,9 @@ void Operator::applyBlock(int K, const double* x, int64_t ldx, bool treeIn, cons
     }
     if (fork) HIP_CHECK(hipStreamWaitEvent(s, evJoin, 0));
     // down pass (owned part), once for the sum over the terms (it is linear in the locals and
-    // the partials).  The near partials: a single-RHS symmetric plan, or the harmonic one's
+    // the partials).  The near partials: a single-RHS symmetric plan's
     if (mask & (kStageFar | kStageNear))
-        downPass16(K, mask, (harmonic ? hsSym : plan.nearPartTotal > 0) ? dNearPart.as<double>() : nullptr,
+        downPass16(K, mask, !harmonic && plan.nearPartTotal > 0 ? dNearPart.as<double>() : nullptr,
                    halo && clustered ? dHmPart.as<double>() : nullptr, o, s);
     sp.end(5);
     sp.total();  // (at level 2 this route has no first mark, so no total: DESIGN.md §3.18.4)
@@ -1898,7 +1785,7 @@ void Operator::modeApplyLean16(int id, int K, const InRows& in, const OutRows& o
     // (the up tiers form their charges from the input again and store none: launch_prepare did)
     for (int k = 0; k < ntier; ++k)
         upTier16(K, k, nullptr, plan.upTierTask[k + 1] - plan.upTierTask[k], nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, in, s);
+                 nullptr, in, s);
     sp.end(1);
     sp.startRoofline();
     launch_m2l_mode16(K, id, pairList(), dAttM2L.as<double>(), nodeBoxes(), dParams.as<Params>(), dMult.as<double>(),
@@ -1937,8 +1824,7 @@ void Operator::modeApplyDev(int id, int nrhs, const double* x, int64_t ldx, cons
     const int64_t N = geo.N;
     // a lean mode of an np = 4 handle on the mode-shared caches (leanMapping's conditions;
     // the mode kernels read the directed near blocks)
-    const bool lean16 = !highOrder() && !modes[id].resident && useAtt && attReady && plan.nearPartTotal == 0 &&
-                        !plan.nearSymHsOn;
+    const bool lean16 = !highOrder() && !modes[id].resident && useAtt && attReady && plan.nearPartTotal == 0;
     // its down tiers are the last writer of every point and fuse the forward form's
     // subtraction; a lone leaf has none and goes through the buffer below
     const bool viaBuffer = minuend && !highOrder() && !(lean16 && !plan.dnDesc.empty());
@@ -2715,8 +2601,6 @@ std::vector<int64_t> Operator::topTrace() {
             int k = 1;
             while (k + 1 < ntier && b >= plan.upTierTask[k + 1] - u1) ++k;
             out.insert(out.end(), {(int64_t)-k, (int64_t)(k - 1), 0, 0});
-        } else if (b >= topTraceBlocks - topTraceNear) {  // a near-field group (16 leaves)
-            out.insert(out.end(), {(int64_t)-99, 0, 16, 0});
         } else {
             const int c = b - nUp, t0 = plan.hmClPtr[c], t1 = plan.hmClPtr[c + 1];
             out.insert(out.end(), {(int64_t)c, (int64_t)plan.hmClWait[c], (int64_t)(t1 - t0),
@@ -3080,7 +2964,6 @@ void Operator::commInit(std::unique_ptr<Collectives> c) {
             Plan q;  // the same plan inputs (Plan::build keeps these), rank r's shard
             if (r != me) {
                 q.nearSymmetric = plan.nearSymmetric;
-                q.nearSymHs = plan.nearSymHs;
                 q.maxCanon = plan.maxCanon;
                 q.xUpPartialIn = plan.xUpPartialIn;
                 q.build(tree, np, r, P);
@@ -3448,9 +3331,8 @@ void Operator::blockOpShardedHigh(int which, double* x, int64_t ldx, double* yo,
 // the mode caches, which every rank builds alike before a block matvec.
 bool Operator::oneExchangeLocal() const {
     // (more than kMaxRhs blocks: the exchange carries one chunk of kMaxRhs rows)
-    if (!plan.xOneOk || !oneXOn || !useAtt || !rhs_supported(std::min(ks, kMaxRhs)) || !nearEarly || nearInTop ||
-        !plan.nearCorrOk ||
-        plan.nearPartTotal > 0)
+    if (!plan.xOneOk || !oneXOn || !useAtt || !rhs_supported(std::min(ks, kMaxRhs)) || !nearEarly ||
+        !plan.nearCorrOk || plan.nearPartTotal > 0)
         return false;
     const NearCorr probe{dNearCorrRow.as<uint16_t>(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     return near_hs_fusable((int)plan.leaves.size(), plan.nearMaxLeaf, plan.nsMax, dNearLoc.as<uint16_t>(), &probe,
@@ -3630,7 +3512,6 @@ void Operator::shardedExchange(int nb, double* x, int64_t ldx, bool one, hipStre
         ExchangeForm& form = call.exch;
         form.oneX = true;
         form.upPartial = oxUp;
-        form.upTails = oxUp && upTailsOn && !plan.xUpRoots.empty();
         if (oxUp && oxRootParts > 63) throw std::logic_error("partial-sum records: more than 63 peer parts");
         const int RK = kRank * rootRhs(nb);
         // one pack launch (this rank's roots -- or its partial-sum records -- into
@@ -3638,44 +3519,35 @@ void Operator::shardedExchange(int nb, double* x, int64_t ldx, bool one, hipStre
         // reads), one all-to-all-v, one unpack launch (the peers' roots into the slot
         // layout and the own roots -- or every upper node's records summed -- the
         // input's halo, the multipoles)
-        // (built when the pack is enqueued: phase 1 may size the work buffers, dMult)
-        OxArgs pk;
-        auto packArgs = [&] {
-            pk.nRoot = oxRootParts;
-            pk.rec = oxUp ? (int64_t)plan.xUpRecNode.size() * RK : rec;
-            pk.rootOff = dOxRootSend.as<int64_t>();
-            pk.roots = oxUp ? dXUpRec.as<double>() : dXRootsSend.as<double>();
-            pk.nPts = oxNsendPts;
-            pk.nb = nb;
-            pk.pos = dOxSendPos.as<int64_t>();
-            pk.base = dOxSendBase.as<int64_t>();
-            pk.stride = dOxSendStride.as<int64_t>();
-            pk.x = x;
-            pk.ldx = ldx;
-            pk.nNode = oxNsendNodes;
-            pk.len = RK;
-            pk.node = dOxSendNode.as<int>();
-            pk.nodeBase = dOxSendNodeBase.as<int64_t>();
-            pk.mult = dMult.as<double>();
-            pk.buf = dOxSendBuf.as<double>();
-        };
-        auto pack = [&](hipStream_t st) {
-            packArgs();
-            if (oxUp) {  // the pack launch forms this rank's records (its first workgroups) unless the
-                         // bottom tier's tails already did
-                OxArgs pr = pk;
-                pr.nRoot = 0;
-                launch_ox_pack_up(rootRhs(nb), form.upTails ? 0 : (int)(plan.xUpTask.size() / Plan::kUpTaskInts),
-                                  dXUpTask.as<int>(), dMult.as<double>(), dParams.as<Params>(),
-                                  dXUpRec.as<double>(), (int)oxRootParts, dOxRootSend.as<int64_t>(), pr, st);
-            } else {
-                launch_ox(pk, true, st);
-            }
-        };
-        if (nearAfterPack) form.pack = pack;
         phase1(call);
-        form.pack = nullptr;
-        if (!form.issued) pack(s);
+        // (built after phase 1, which may size the work buffers, dMult)
+        OxArgs pk;
+        pk.nRoot = oxRootParts;
+        pk.rec = oxUp ? (int64_t)plan.xUpRecNode.size() * RK : rec;
+        pk.rootOff = dOxRootSend.as<int64_t>();
+        pk.roots = oxUp ? dXUpRec.as<double>() : dXRootsSend.as<double>();
+        pk.nPts = oxNsendPts;
+        pk.nb = nb;
+        pk.pos = dOxSendPos.as<int64_t>();
+        pk.base = dOxSendBase.as<int64_t>();
+        pk.stride = dOxSendStride.as<int64_t>();
+        pk.x = x;
+        pk.ldx = ldx;
+        pk.nNode = oxNsendNodes;
+        pk.len = RK;
+        pk.node = dOxSendNode.as<int>();
+        pk.nodeBase = dOxSendNodeBase.as<int64_t>();
+        pk.mult = dMult.as<double>();
+        pk.buf = dOxSendBuf.as<double>();
+        if (oxUp) {  // the pack launch forms this rank's records (its first workgroups)
+            OxArgs pr = pk;
+            pr.nRoot = 0;
+            launch_ox_pack_up(rootRhs(nb), (int)(plan.xUpTask.size() / Plan::kUpTaskInts), dXUpTask.as<int>(),
+                              dMult.as<double>(), dParams.as<Params>(), dXUpRec.as<double>(), (int)oxRootParts,
+                              dOxRootSend.as<int64_t>(), pr, s);
+        } else {
+            launch_ox(pk, true, s);
+        }
         comm->alltoallv(dOxSendBuf.as<double>(), oxScount.data(), oxSoff.data(), dOxRecvBuf.as<double>(),
                         oxRcount.data(), oxRoff.data(), s);
         OxArgs uk = pk;

@@ -69,11 +69,6 @@ struct StageTimes {
 struct ExchangeForm {
     bool oneX = false;       // the two phases run around the one grouped exchange
     bool upPartial = false;  // the upper multipoles travel as partial sums (Plan::xUpPartial on every rank)
-    bool upTails = false;    // ... their partial tasks as tails of the bottom tier (ANISO_UP_TAILS=1)
-    // ANISO_NEAR_AFTER_PACK=1: the pack launch, which phase 1 enqueues right after the own
-    // tier-0 launch (and sets `issued`) when the near field's early groups fork after it
-    std::function<void(hipStream_t)> pack;
-    bool issued = false;
 };
 
 // The precision of an apply's M2L and near field on a high-order handle (an argument of
@@ -206,8 +201,7 @@ public:
     // M2L.  np = 4: a resident mode runs applyBlock's identity
     // mix in chunks of 8; a lean mode runs the same chunks through modeApplyLean16 (the
     // near-field mode kernel and the rank-16 mode M2L between the up and down tiers), one
-    // read of the shared caches per chunk.  (A handle whose harmonic near field keeps
-    // symmetric U storage, ANISO_NEAR_HS_SYM, runs one leanMapping per column.)
+    // read of the shared caches per chunk.
     // modeApplyCheck raises everything that can be refused before the device is touched
     // (false: nrhs = 0, nothing to do).
     // f32: the reduced-precision entries, refused on np = 4 and on sharded handles.
@@ -587,10 +581,9 @@ public:
 private:
     void apply(const double* charge, bool treeIn, const double* sigT, int id, double* out, bool treeOut, hipStream_t s,
                int mask);
-    // (writes call.exch.issued; everything else of the call is read only)
     void applyBlock(int K, const double* x, int64_t ldx, bool treeIn, const double* sigT, int nterm, const int* ids,
                     const double* mixes, double* out, int64_t ldo, bool treeOut, hipStream_t s, int mask,
-                    ApplyCall& call);
+                    const ApplyCall& call);
     // blockOpDev at ks <= kMaxRhs on a call description (a sharded matvec's carries its exchange form)
     void blockOp(int which, const double* x, int64_t ldx, double* out, int64_t ldo, bool treeIo, hipStream_t s,
                  double gval, const double* sigT, ApplyCall& call);
@@ -684,7 +677,7 @@ private:
     void hoUpPass(int K, const double* fT, double* mult, bool allLeaves, hipStream_t s);
     void hoDownPass(int K, double* local, const OutRows& o, hipStream_t s);
     void upTier16(int K, int k, const int* list, int ntask, double* fT, double* cT, const double* recv, double* send,
-                  unsigned* zeroCnt, const UpTail* tail, const InRows& in, hipStream_t s);
+                  unsigned* zeroCnt, const InRows& in, hipStream_t s);
     void downPass16(int K, int mask, const double* nearPart, const double* hpart, const OutRows& o, hipStream_t s);
     // groups of nb rows (stride ldx) into the first nb of each group's K rows of buf (stride N),
     // the other rows zero; and the first n points of the nb rows of one group back out
@@ -828,27 +821,15 @@ private:
     std::vector<std::pair<int, int>> nearCalls;  // modeNearCalls()
     void arnoldiParts(int rows);  // dKryPart for sweeps of `rows` rows
     bool topTraceOn = false;
-    int hmRing = 0;  // the cluster M2L's LDS ring depth (ANISO_HM_RING; 0: the one-block-in-flight form)
-    int hmWpe = 0;   // ANISO_HM_WPE=3/4/8: the one-block form's occupancy (0: 4 where LDS allows)
-    // ANISO_NEAR_WPE: the staged near field capped at 128 VGPRs, 4 waves per SIMD (the default
-    // since round 5: 0.312 against 0.329 ms standalone, r05y), or 3 (121 VGPRs, the round-4 form)
-    int nearWpe = 4;
     int topFusedMode = 1;  // ANISO_TOP_FUSED=0: the upper up tiers as launches of their own
-    // the near field's groups ride at the end of the fused top-of-tree + M2L launch
-    // instead of a side-stream launch (ANISO_NEAR_IN_TOP=1; on a shard in phase 2)
-    bool nearInTop = false;
     // the staged near field forms its charges from the input and forks at the start
     // of the block apply, beside the up pass (ANISO_NEAR_EARLY=0: after it, from fT)
     bool nearEarly = true;
-    bool nearOrderUp = true;  // the near launch issued after the bottom up tier's (ANISO_NEAR_ORDER=first: before)
-    // a one-collective sharded matvec starts the near field's own-range groups beside
-    // phase 1 (ANISO_SHARD_NEAR_EARLY=0: every group after the exchange)
-    bool shardNearEarly = true;
     // the bottom up tier inside the staged near field on one GPU (Plan::nearUpOk, serial
     // schedule; ANISO_NEAR_UP=0: its own launch)
     bool nearUpOn = true;
     DevBuf dNearUpGrp;
-    int topTraceBlocks = 0, topTraceNear = 0;
+    int topTraceBlocks = 0;
     // the attached communicator and its halo exchange plan (commInit): per element of
     // the send / receive position lists its tree position and its place in the
     // peer-major buffers (base + b * stride for block b); doubles per peer
@@ -874,15 +855,6 @@ private:
     // node's records (oxUpSumNode / Ptr / Src: >= 0 an offset into the receive buffer,
     // < 0 ~offset into this rank's own records)
     bool oxUp = false;
-    // the partial tasks as tails of the bottom tier (ANISO_UP_TAILS=1; default: in the
-    // pack launch, measured faster on a rank of 8: r06h)
-    bool upTailsOn = false;
-    // the one-collective exchange's pack launch, enqueued by phase 1 right after the own
-    // tier-0 launch when the near field's early groups fork after it
-    // (ANISO_NEAR_AFTER_PACK=1; ExchangeForm::pack)
-    bool nearAfterPack = false;
-    int sidePrio = 0;  // ANISO_SIDE_PRIO: the side stream's priority (-1 lowest, 0 default, 1 highest)
-    DevBuf dXT0Part, dXUpRoots, dXUpCnt, dXUpStage;
     DevBuf dXUpTask, dXUpRec, dOxUpSumNode, dOxUpSumPtr, dOxUpSumSrc;
     int64_t oxUpSums = 0;
     bool oneExchangeUsable(int which);
@@ -961,16 +933,12 @@ private:
     };
     int maxNearS = 0;
     // geometry / tree on device
-    DevBuf dPxT, dPyT, dPerm, dW, dNcx, dNcy, dNrx, dNry, dBegin, dCount, dParent, dSlot, dChild, dIsLeaf, dNodeGeo;
+    DevBuf dPxT, dPyT, dPerm, dW, dNcx, dNcy, dNrx, dNry, dBegin, dCount, dParent, dSlot, dChild, dIsLeaf;
     DevBuf dLeaves, dNearPtr, dNearSrc, dNearKOff, dNearFOff, dM2LTgt, dM2LPtr, dM2LSrc, dM2LPairTgt;
     DevBuf dUpTaskPtr, dUpGrpPtr, dUpGrp, dUpNode, dUpCode, dUpDesc, dUpGrpFix, dUpGeom, dUpLeaf;                       // up-pass tiers
     DevBuf dDnTaskPtr, dDnGrpPtr, dDnGrp, dDnNode, dDnLeafPtr, dDnLeafSlot, dDnLeafIdx, dDnLeafPts, dDnPtsRange, dDnDesc, dDnGrpFix, dDnLeafGeom;  // down
     DevBuf dLeafInfo, dNearPtsPtr, dNearPts;
     DevBuf dNsPtr, dNsPts, dNearLoc;  // near field sources staged per workgroup (k_near_hs)
-    // the harmonic near field's symmetric U storage (Plan::nearSymHsOn): its column
-    // lists, canonical partner blocks and the leaves' first table rows
-    DevBuf dHsPtsPtr, dHsLoc, dHsKOff, dHsSym, dHsSrcPtr, dHsSrc, dHsDst, dNearSelfRow;
-    DevBuf dNearGrpInPtr, dNearGrpIn;
     DevBuf dNearCorrRow;              // d = 1: the stencil's table rows (corrections fused into k_near_hs)
     DevBuf dXT0Tasks, dXRootRecv, dXRootSlot, dXSendSlot;  // sharded up pass (plan.buildExchange)
     DevBuf dM2LNDir, dM2LCanonBase, dM2LInPtr, dM2LOutSlot, dM2LPart;  // symmetric M2L

@@ -114,17 +114,15 @@ constexpr int up_partial_lds() {
     return Plan::kUpTaskInts + (kUpMaxPeers + 1) + 4 * kRank * kRank + 16 * kRank * K +
            (5 + Plan::kUpChainMax) * kRank * K;
 }
-// stage (tails): the roots from the write-through staging copies, slot q at
-// stage + q * RK, read with sc1 loads (no acquire fence; MI355X_MICROARCH.md, the
-// last-adder hand-off with write-through payload); else from mult by node id.
-// Every record is formed in LDS first and stored in one final pass: a barrier
-// between the levels then waits for LDS work only, not for the records' global
-// stores (with a store pass per level the task took ~30 us under the near field).
+// The roots are read from mult by node id.  Every record is formed in LDS first and
+// stored in one final pass: a barrier between the levels then waits for LDS work only,
+// not for the records' global stores (with a store pass per level the task took ~30 us
+// under the near field).
 template <int K>
 __device__ __forceinline__ void up_partial_task(const int* __restrict__ tk, const Params* __restrict__ P,
                                                 const double* __restrict__ mult, double* __restrict__ rec, int nPeer,
                                                 const int64_t* __restrict__ peerOff, double* __restrict__ buf,
-                                                double* sm, double* stage = nullptr) {
+                                                double* sm) {
     constexpr int RK = kRank * K;
     constexpr int NI = Plan::kUpTaskInts;
     int* T = reinterpret_cast<int*>(sm);                // NI ints (NI doubles reserved)
@@ -136,18 +134,10 @@ __device__ __forceinline__ void up_partial_task(const int* __restrict__ tk, cons
     for (int i = threadIdx.x; i < NI; i += blockDim.x) T[i] = tk[i];
     for (int i = threadIdx.x; i < nPeer; i += blockDim.x) PO[i] = peerOff[i];
     for (int i = threadIdx.x; i < 4 * kRank * kRank; i += blockDim.x) Rm[i] = (&P->R[0][0])[i];
-    if (stage) {  // slot q's root at stage + q RK (absent slots: never staged, read as 0 below)
-        for (int i = threadIdx.x; i < 16 * RK; i += blockDim.x)
-            X[i] = __hip_atomic_load(stage + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        for (int i = threadIdx.x; i < 16 * RK; i += blockDim.x)
-            if (T[i / RK] < 0) X[i] = 0.0;
-    } else {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 16 * RK; i += blockDim.x) {
-            const int r = T[i / RK];
-            X[i] = r >= 0 ? mult[(size_t)r * RK + i % RK] : 0.0;
-        }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 16 * RK; i += blockDim.x) {
+        const int r = T[i / RK];
+        X[i] = r >= 0 ? mult[(size_t)r * RK + i % RK] : 0.0;
     }
     __syncthreads();
     // parent entry (r, b) = sum over quadrants q and rows rr of R[q][r, rr] child_q[rr, b]
@@ -195,8 +185,6 @@ __device__ __forceinline__ void up_partial_task(const int* __restrict__ tk, cons
     }
 }
 
-typedef __attribute__((address_space(1))) unsigned gu32_up;
-
 template <int K>
 __global__ void __launch_bounds__(kUpThreads) k_up_tier(
     int taskBase, const int* __restrict__ taskList, int maxTask, const int4* __restrict__ desc, const int* __restrict__ grpFix,
@@ -206,50 +194,13 @@ __global__ void __launch_bounds__(kUpThreads) k_up_tier(
     const double* __restrict__ sigT, const double* __restrict__ wT, double* __restrict__ fT, double* __restrict__ cT,
     const Params* __restrict__ P, double* __restrict__ mult, const int* __restrict__ rootSlot,
     const double* __restrict__ recv, const int* __restrict__ sendSlot, double* __restrict__ send,
-    unsigned* __restrict__ zeroCnt, UpTail tail) {
+    unsigned* __restrict__ zeroCnt) {
     extern __shared__ double sm[];
     // the counters of the fused top-of-tree launch that follows (k_top_m2l_hc)
     if (zeroCnt && blockIdx.x == 0 && threadIdx.x <= kMaxTopTiers) zeroCnt[threadIdx.x] = 0u;
     const int task = taskList ? taskList[blockIdx.x] : taskBase + (int)blockIdx.x;
     up_task<K>(task, maxTask, desc, grpFix, node, code, geom, leafRange, pxT, pyT, xin, ldi, treeIn, perm, sigT, wT,
                fT, cT, P, mult, rootSlot, recv, sendSlot, send, sm);
-    if (!tail.partOf) return;
-    // the partial task's last root (MI355X_MICROARCH.md, inter-workgroup visibility:
-    // the last-adder hand-off with a write-through payload, no fences): this block's
-    // root multipole (its own plain stores, re-read after the barrier) is copied into
-    // the staging slot with sc1 (write-through) stores; every storing wave waits for
-    // them, then one lane adds to the partial task's counter; the block whose add
-    // completes the count resets the counter for the next apply and runs the partial
-    // task, loading the staged roots with sc1 loads.  No block waits for another, so
-    // dispatch order does not matter.
-    constexpr int RK = kRank * K;
-    __shared__ int lastOf;
-    const int2 pq = tail.partOf[blockIdx.x];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the root's plain stores by every wave of this block
-    __syncthreads();
-    if (pq.x >= 0)
-        for (int e = threadIdx.x; e < RK; e += blockDim.x)
-            __hip_atomic_store(tail.stage + (size_t)pq.x * RK + e, mult[(size_t)pq.y * RK + e], __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        if (pq.x >= 0) {
-            const int p = pq.x >> 4;
-            const unsigned old = __hip_atomic_fetch_add((gu32_up*)(tail.cnt + p), 1u, __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_AGENT);
-            if (old + 1u == (unsigned)tail.nroots[p]) {
-                __hip_atomic_store((gu32_up*)(tail.cnt + p), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                run = p + 1;
-            }
-        }
-        lastOf = run;
-    }
-    __syncthreads();
-    if (lastOf)
-        up_partial_task<K>(tail.task + (size_t)(lastOf - 1) * Plan::kUpTaskInts, P, mult, tail.rec, tail.nPeer,
-                           tail.peerOff, tail.buf, sm, tail.stage + (size_t)(lastOf - 1) * 16 * RK);
 }
 
 
@@ -1160,7 +1111,7 @@ void launch_up_tier(int K, int ntask, int taskBase, const int* taskList, int max
                     const double* pxT, const double* pyT, const double* xin, int64_t ldi, int treeIn, const int* perm,
                     const double* sigT, const double* wT, double* fT, double* cT, const Params* P, double* mult,
                     const int* rootSlot, const double* recv, const int* sendSlot, double* send, hipStream_t s,
-                    unsigned* zeroCnt, const UpTail* tail) {
+                    unsigned* zeroCnt) {
     if (ntask <= 0) {
         if (zeroCnt) {
             const hipError_t e = hipMemsetAsync(zeroCnt, 0, (kMaxTopTiers + 1) * sizeof(unsigned), s);
@@ -1168,14 +1119,9 @@ void launch_up_tier(int K, int ntask, int taskBase, const int* taskList, int max
         }
         return;
     }
-    const UpTail tl = tail ? *tail : UpTail{};
-    ANISO_DISPATCH_K(K, ({
-        const size_t shm = std::max(up_tier_lds(maxTask, KK),
-                                    tl.partOf ? (size_t)up_partial_lds<KK>() * sizeof(double) : (size_t)0);
-        k_up_tier<KK><<<ntask, kUpThreads, shm, s>>>(taskBase, taskList, maxTask, desc, grpFix, node, code, geom,
-                                                     leafRange, pxT, pyT, xin, ldi, treeIn, perm, sigT, wT, fT, cT, P,
-                                                     mult, rootSlot, recv, sendSlot, send, zeroCnt, tl);
-    }));
+    ANISO_DISPATCH_K(K, (k_up_tier<KK><<<ntask, kUpThreads, up_tier_lds(maxTask, KK), s>>>(
+                            taskBase, taskList, maxTask, desc, grpFix, node, code, geom, leafRange, pxT, pyT, xin, ldi,
+                            treeIn, perm, sigT, wT, fT, cT, P, mult, rootSlot, recv, sendSlot, send, zeroCnt)));
     HIP_LAUNCH_CHECK();
 }
 
@@ -1287,7 +1233,6 @@ struct UpPack {
     double* rec = nullptr;            // this rank's records
     int nPeer = 0;
     const int64_t* peerOff = nullptr;  // each peer part's first record (doubles into the send buffer)
-    int prio = 0;                      // raised wave priority for the task workgroups (ANISO_PACK_PRIO)
 };
 
 template <int K>
@@ -1298,8 +1243,9 @@ __global__ void __launch_bounds__(256) k_ox_pack_up(UpPack u, OxArgs a) {
     }
     __shared__ double sm[up_partial_lds<K>()];
     // the exchange waits on these few latency-bound workgroups, and the near field's own
-    // groups run beside them: their waves issue first on a contended SIMD
-    if (u.prio) __builtin_amdgcn_s_setprio(3);
+    // groups run beside them: their waves issue first on a contended SIMD (0.216 / 0.230
+    // against 0.220 / 0.236 ms per rank of 8 at the default priority, ranks 0 / 3, r05zd)
+    __builtin_amdgcn_s_setprio(3);
     up_partial_task<K>(u.task + (size_t)blockIdx.x * Plan::kUpTaskInts, u.P, u.mult, u.rec, u.nPeer, u.peerOff, a.buf,
                        sm);
 }
@@ -1310,13 +1256,7 @@ void launch_ox_pack_up(int K, int ntask, const int* task, const double* mult, co
     const int64_t n = a.nPts * a.nb + a.nNode * a.len;
     const unsigned nb = (unsigned)ntask + (unsigned)blocks_for(n, 256);
     if (nb == 0) return;
-    // raised priority: 0.216 / 0.230 against 0.220 / 0.236 ms per rank of 8 (ranks 0 / 3,
-    // r05zd); ANISO_PACK_PRIO=0 leaves it at the default
-    static const int prio = [] {
-        const char* e = std::getenv("ANISO_PACK_PRIO");
-        return e ? std::atoi(e) : 1;
-    }();
-    const UpPack u{ntask, task, mult, P, rec, nPeer, peerOff, prio};
+    const UpPack u{ntask, task, mult, P, rec, nPeer, peerOff};
     ANISO_DISPATCH_K(K, (k_ox_pack_up<KK><<<nb, 256, 0, s>>>(u, a)));
     HIP_LAUNCH_CHECK();
 }

@@ -1103,9 +1103,9 @@ static void stats_fill(aniso::Operator& op, int64_t* s) {
     s[20] = op.plan.hmMaxLds;
     s[21] = (int64_t)op.plan.hmSrc.size();
     s[22] = op.topRecoveries;
-    // the harmonic near field's symmetric U storage (0: directed, Plan::nearSymHsOn)
-    s[23] = op.plan.nearSymHsOn ? op.plan.hsStored : 0;
-    s[24] = op.plan.nearSymHsOn ? op.plan.hsPartTotal : 0;
+    // (kept for the ABI: the counts of a near-field storage that no longer exists)
+    s[23] = 0;
+    s[24] = 0;
     s[25] = op.oneXApplies;  // sharded matvecs through the one-collective exchange
     s[26] = op.mrhsM2LPairs();  // directed M2L pairs of the 16-RHS MFMA operators (0 before their plan)
     s[27] = op.topSteals();     // upper-tier tasks computed by waiting blocks of the fused launch

@@ -360,13 +360,6 @@ __device__ __forceinline__ void hc_det_scale(int cid, const HcSlots& cs, const H
     isc = ldexp(1.0, -S);
 }
 
-// The same distances for the 4-wave form (LR): from wave-uniform values only,
-// dx_j = axs - r cheb_j (one FMA with two scalar operands; ~2-4 % more VALU, but no
-// VGPRs held for the target's columns).
-__device__ __forceinline__ double cheb_dx_lr(int j, double axs, double r, const Params* __restrict__ P) {
-    return __builtin_fma(-r, P->cheb[j], axs);
-}
-
 // The harmonic M2L in clusters: one 4-wave workgroup per
 // cluster (the active targets of one level under one ancestor kClusterDepth levels
 // up), the cluster's locals accumulated in LDS.  Each wave takes the cluster's
@@ -377,9 +370,7 @@ __device__ __forceinline__ double cheb_dx_lr(int j, double axs, double r, const 
 // (ds_add_f64).  The block stream drops by the in-cluster share (0.65 of the V
 // pairs at 64 targets per cluster, tools/vfrac.py); the summation order of the LDS
 // adds is not fixed (results repeat to rounding, not bitwise).
-// LR: the 4-wave-per-SIMD form (<= 128 VGPRs, k_m2l_hc / k_top_m2l_hc with WPE = 4)
-// for launches whose LDS allows 4 workgroups per CU (small clusters: shards)
-template <int K, int NR, bool LR = false, bool DET = false>
+template <int K, int NR, bool DET = false>
 __device__ __forceinline__ void m2l_hc_cluster(const int cid, const HcArgs& a, double* sm) {
     const int* __restrict__ clPtr = a.clPtr;
     const int* __restrict__ tgt = a.tgt;
@@ -437,14 +428,12 @@ __device__ __forceinline__ void m2l_hc_cluster(const int cid, const HcArgs& a, d
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // xa visible to every lane of the wave
         __builtin_amdgcn_wave_barrier();
-        // the target's Chebyshev x coordinates: held in 8 VGPRs (the 3-wave form; the
-        // two-value form cheb_dx measured 3 % slower per block matvec, r03zc), or from
-        // wave-uniform values (LR, the 4-wave form, <= 128 VGPRs)
-        const double tcx = LR ? ncx[n] : 0.0, trx = nrx[n], tcx1 = ncx[n];
+        // the target's Chebyshev x coordinates: held in 8 VGPRs (the two-value form
+        // cheb_dx measured 3 % slower per block matvec, r03zc)
+        const double trx = nrx[n], tcx1 = ncx[n];
         double bx[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bx[j] = LR ? 0.0 : ncx[n] + trx * P->cheb[j];
-        auto dxj = [&](int j, double axs) { return LR ? cheb_dx_lr(j, axs, trx, P) : axs - bx[j]; };
+        for (int j = 0; j < 4; ++j) bx[j] = ncx[n] + trx * P->cheb[j];
         const double by = ncy[n] + nry[n] * P->cheb[q];
         double c[4][K];
 #pragma unroll
@@ -483,14 +472,14 @@ __device__ __forceinline__ void m2l_hc_cluster(const int cid, const HcArgs& a, d
                     }
     #pragma unroll
                     for (int g = 0; g < PG; ++g) {
-                        const double axs = LR ? (ncx[B[g]] - tcx) + nrx[B[g]] * chx : ncx[B[g]] + nrx[B[g]] * chx;
+                        const double axs = ncx[B[g]] + nrx[B[g]] * chx;
                         const double dy = (ncy[B[g]] + nry[B[g]] * chy) - by;
                         const double dy2 = dy * dy;
                         double xw[K];
     #pragma unroll
                         for (int b = 0; b < K; ++b) xw[b] = hw.hw[b] * xm[g][b];
     #pragma unroll
-                        for (int j = 0; j < 4; ++j) hm_entry<K, false, NR>(e4[g][j], dxj(j, axs), dy2, xw, c[j]);
+                        for (int j = 0; j < 4; ++j) hm_entry<K, false, NR>(e4[g][j], axs - bx[j], dy2, xw, c[j]);
                     }
                 }
             }
@@ -503,9 +492,7 @@ __device__ __forceinline__ void m2l_hc_cluster(const int cid, const HcArgs& a, d
                 const int cnt = (int)min<int64_t>(kWave, p1 - cb);
                 const int mySrc = lane < cnt ? src[cb + lane] : 0;
                 const int myBlk = lane < cnt ? blk[cb + lane] : 0;
-                // LR: the partner's slot by a scalar load (needed only at the flush), one
-                // VGPR fewer across the stream
-                const int mySlot = !LR && lane < cnt ? slot[cb + lane] : 0;
+                const int mySlot = lane < cnt ? slot[cb + lane] : 0;
                 dbl2 k0, k1;
                 double xm[K], gcx, grx, gcy, gry;
                 auto fetch = [&](int jj, dbl2& a0, dbl2& a1, double (&x)[K], double& fcx, double& frx, double& fcy,
@@ -527,8 +514,8 @@ __device__ __forceinline__ void m2l_hc_cluster(const int cid, const HcArgs& a, d
                 // other (unrolled by two: no register copies between the sets)
                 auto pair = [&](int jj, const dbl2& a0, const dbl2& a1, const double (&xv)[K], double fcx,
                                 double frx, double fcy, double fry) {
-                    const int sl = LR ? slot[cb + jj] : __builtin_amdgcn_readlane(mySlot, jj);
-                    // the distances from wave-uniform values (as the LR form): 8 VGPRs
+                    const int sl = __builtin_amdgcn_readlane(mySlot, jj);
+                    // the distances from wave-uniform values: 8 VGPRs
                     // fewer than the held target columns bx, the same VALU count
                     const double axs = (fcx - tcx1) + frx * chx;
                     const double dy = (fcy + fry * chy) - by;
@@ -584,278 +571,17 @@ __device__ __forceinline__ void m2l_hc_cluster(const int cid, const HcArgs& a, d
     hc_flush<K, DET>(cs, a, acc, isc);
 }
 
-// ---- the ring form of the cluster M2L ----
-//
-// m2l_hc_cluster keeps one block (two in the directed loop) in flight per wave:
-// every pair is a dependent HBM round trip (~1.7 us per block per wave at 1 and at 8
-// shards, tools/top_trace.py), and deeper register prefetch does not fit beside the
-// 40 accumulator VGPRs at 3 waves per SIMD.  Here each wave streams its pair list
-// through a private ring of D slots in LDS filled by LDS-DMA (global_load_lds_dwordx4:
-// no VGPR holds a block in flight): slot = the 2 KB E block, the source's 16 x K
-// multipole and its box (cx, cy, rx, ry).  The wave issues pair k + D - 1, waits with
-// a counted vmcnt for pair k and computes it from LDS, so D - 1 blocks stay in flight
-// across the compute.  The target's own weighted multipole (the dual products'
-// operand) lives in registers.
-//
-// The compiler's wait-count pass treats every LDS access as possibly reading an
-// LDS-DMA destination and would put vmcnt(0) before it, draining the ring.  So every
-// LDS access inside the stream is inline asm, which that pass does not see: the slot
-// reads (closed by one lgkmcnt(0) that re-defines their outputs) and the partner
-// products' ds_add_f64; the counted vmcnt waits are asm too.
-constexpr int kRingMaxK = 5;  // the ring forms compile without spills up to 5 blocks (hm_ring_xl)
-
-template <int K>
-struct Ring {
-    static_assert(K <= kRingMaxK, "the ring form spills above 5 blocks");
-    static constexpr int kMultB = kRank * K * 8;        // the multipole's bytes
-    static constexpr int kMultL = kMultB / 16;          // its 16-byte lanes
-    static constexpr bool kSplit = kMultL + 2 > kWave;  // the box in an instruction of its own (K = 8)
-    static constexpr int kNI = kSplit ? 4 : 3;          // LDS-DMA instructions per slot
-    static constexpr int kSlot = 2048 + kMultB + 32;    // bytes per slot
-};
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ unsigned lds_offset(const void* p) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
-
-__device__ __forceinline__ void glds16(const double* g, unsigned lds) {
-    __builtin_amdgcn_global_load_lds(g, (lds_void*)(uintptr_t)lds, 16, 0, 0);
-}
-
-// no "memory" clobbers on the stream's asm: one would make every later global load of
-// the kernel a vector load (the wave-uniform pair indices must stay scalar loads, or
-// their vmcnt waits drain the ring); volatile asm keeps its order with the LDS-DMA
-// intrinsics and with each other
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N));
-}
-
-// wait until the slot issued `after` slots ago (0 .. 3) has landed
-template <int NI>
-__device__ __forceinline__ void ring_wait(int after) {
-    if (after >= 3) wait_vm<3 * NI>();
-    else if (after == 2) wait_vm<2 * NI>();
-    else if (after == 1) wait_vm<NI>();
-    else wait_vm<0>();
-}
-
-// fill a slot: block b of E, multipole and box of source node B (wave-uniform b, B)
-template <int K>
-__device__ __forceinline__ void ring_issue(const double* __restrict__ E, const double* __restrict__ mult,
-                                           const double* __restrict__ geo, int b, int B, unsigned slot, int lane) {
-    using R = Ring<K>;
-    const double* eg = E + (size_t)b * 256 + 2 * lane;
-    glds16(eg, slot);
-    glds16(eg + 128, slot + 1024);
-    const double* mg = mult + (size_t)B * (kRank * K) + 2 * lane;
-    const double* gg = geo + 4 * (size_t)B + 2 * (lane - (R::kSplit ? 0 : R::kMultL));
-    if constexpr (R::kSplit) {
-        glds16(mg, slot + 2048);
-        if (lane < 2) glds16(gg, slot + 2048 + R::kMultB);
-    } else {
-        if (lane < R::kMultL + 2) glds16(lane < R::kMultL ? mg : gg, slot + 2048);
-    }
-}
-
-// lane (s, q)'s operands from a landed slot: rows 4q .. 4q+3 of column s of the
-// block, the source multipole's row s, the source box
-template <int K>
-__device__ __forceinline__ void ring_read(unsigned slot, int lane, int s, double (&e4)[4], double (&xm)[K],
-                                          double (&g)[4]) {
-    using R = Ring<K>;
-    const unsigned eo = slot + 32 * lane, go = slot + 2048 + R::kMultB, mo = slot + 2048 + 8 * K * s;
-    dbl2 e01, e23, g01, g23;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(e01) : "v"(eo));
-    asm volatile("ds_read_b128 %0, %1 offset:16" : "=v"(e23) : "v"(eo));
-    asm volatile("ds_read_b128 %0, %1" : "=v"(g01) : "v"(go));
-    asm volatile("ds_read_b128 %0, %1 offset:16" : "=v"(g23) : "v"(go));
-#pragma unroll
-    for (int b = 0; b < K; ++b) asm volatile("ds_read_b64 %0, %1" : "=v"(xm[b]) : "v"(mo + 8 * b));
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e01), "+v"(e23), "+v"(g01), "+v"(g23));
-#pragma unroll
-    for (int b = 0; b < K; ++b) asm volatile("" : "+v"(xm[b]));
-    e4[0] = e01.x;
-    e4[1] = e01.y;
-    e4[2] = e23.x;
-    e4[3] = e23.y;
-    g[0] = g01.x;
-    g[1] = g01.y;
-    g[2] = g23.x;
-    g[3] = g23.y;
-}
-
-// rows 4q .. 4q+3 of the wave's weighted target multipole (4K doubles from `off`)
-template <int K>
-__device__ __forceinline__ void ring_read_xa(unsigned off, double (&x)[4 * K]) {
-    dbl2 v[2 * K];
-#pragma unroll
-    for (int i = 0; i < 2 * K; ++i) asm volatile("ds_read_b128 %0, %1" : "=v"(v[i]) : "v"(off + 16 * i));
-    asm volatile("s_waitcnt lgkmcnt(0)");
-#pragma unroll
-    for (int i = 0; i < 2 * K; ++i) {
-        asm volatile("" : "+v"(v[i]));
-        x[2 * i] = v[i].x;
-        x[2 * i + 1] = v[i].y;
-    }
-}
-
-template <int K, int NR, int D, bool XL>
-__device__ __forceinline__ void m2l_hcr_cluster(const int cid, const HcArgs& a, double* sm) {
-    static_assert(D >= 2 && D <= 4, "ring depth");
-    using R = Ring<K>;
-    const int* __restrict__ clPtr = a.clPtr;
-    const int* __restrict__ tgt = a.tgt;
-    const int64_t* __restrict__ ptr = a.ptr;
-    const int* __restrict__ ndir = a.ndir;
-    const int* __restrict__ src = a.src;
-    const int* __restrict__ blk = a.blk;
-    const int* __restrict__ slot = a.slot;
-    const double* __restrict__ E = a.E;
-    const double* __restrict__ geo = a.geo;
-    const double* __restrict__ ncx = a.ncx;
-    const double* __restrict__ ncy = a.ncy;
-    const double* __restrict__ nrx = a.nrx;
-    const double* __restrict__ nry = a.nry;
-    const Params* __restrict__ P = a.P;
-    const HarmWeights& hw = a.hw;
-    const double* __restrict__ mult = a.mult;
-    constexpr int RK = kRank * K;
-    const HcSlots cs = hc_slots(cid, a);
-    const int c0 = cs.c0, nt = cs.nt, nsl = cs.nt + cs.nh;
-    (void)clPtr;
-    const int nw = (int)(blockDim.x / kWave);
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-    double* acc = sm;                                                       // (nt + nh) x 16 x K: locals, halo
-    double* xl = sm + (size_t)nsl * RK + (XL ? (size_t)w * RK : 0);         // XL: this wave's target multipole
-    const unsigned ring = lds_offset(sm + (size_t)nsl * RK + (XL ? (size_t)nw * RK : 0)) + (unsigned)(w * D * R::kSlot);
-    const unsigned accOff = lds_offset(acc);
-    for (int i = threadIdx.x; i < nsl * RK; i += blockDim.x) acc[i] = 0.0;
-    __syncthreads();
-    const int lane = threadIdx.x & (kWave - 1);
-    const int s = lane >> 2, q = lane & 3;
-    const double chx = P->cheb[s & 3], chy = P->cheb[s >> 2];
-    for (int ti = w; ti < nt; ti += nw) {
-        const int n = tgt[c0 + ti];
-        // the target's multipole rows 4q + j, (-1)^b hw_b weighted (the dual products):
-        // in registers (40 VGPRs at K = 5, 2 waves per SIMD), or (XL) in LDS, read per
-        // dual block (3 waves per SIMD)
-        double xa[XL ? 1 : 4][K];
-        if constexpr (XL) {
-            for (int e = lane; e < RK; e += kWave) {
-                const int b = e % K;
-                xl[e] = ((b & 1) ? -hw.hw[b] : hw.hw[b]) * mult[(size_t)n * RK + e];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // xl visible to every lane of the wave
-            __builtin_amdgcn_wave_barrier();
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int b = 0; b < K; ++b)
-                    xa[j][b] = ((b & 1) ? -hw.hw[b] : hw.hw[b]) * mult[(size_t)n * RK + (4 * q + j) * K + b];
-        }
-        double bx[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bx[j] = ncx[n] + nrx[n] * P->cheb[j];
-        const double by = ncy[n] + nry[n] * P->cheb[q];
-        double c[4][K];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int i = 0; i < K; ++i) c[j][i] = 0.0;
-        const int64_t p0 = ptr[c0 + ti], pd = p0 + ndir[c0 + ti], p1 = ptr[c0 + ti + 1];
-        // the pair list in chunks of 64: its indices in lanes (one vector load each, while
-        // the ring is empty -- the compiler's wait for them would drain it), the ring
-        // filled and drained per chunk
-        for (int64_t cb = p0; cb < p1; cb += kWave) {
-            const int cnt = (int)min<int64_t>(kWave, p1 - cb);
-            const int mySrc = lane < cnt ? src[cb + lane] : 0;
-            const int myBlk = lane < cnt ? blk[cb + lane] : 0;
-            const int mySlot = lane < cnt && cb + lane >= pd ? slot[cb + lane] : 0;
-            const int nDir = (int)max<int64_t>(0, min<int64_t>(cnt, pd - cb));  // directed entries of the chunk
-            for (int k = 0; k < D - 1 && k < cnt; ++k)
-                ring_issue<K>(E, mult, geo, __builtin_amdgcn_readlane(myBlk, k), __builtin_amdgcn_readlane(mySrc, k),
-                              ring + k * R::kSlot, lane);
-            int cur = 0;  // the slot of pair k
-            for (int k = 0; k < cnt; ++k) {
-                int after = cnt - 1 - k;
-                if (k + D - 1 < cnt) {
-                    const int ns = cur == 0 ? D - 1 : cur - 1;  // the slot pair k - 1 used: free again
-                    ring_issue<K>(E, mult, geo, __builtin_amdgcn_readlane(myBlk, k + D - 1),
-                                  __builtin_amdgcn_readlane(mySrc, k + D - 1), ring + ns * R::kSlot, lane);
-                    after = D - 1;
-                }
-                ring_wait<R::kNI>(after);
-                double e4[4], xm[K], g[4];
-                ring_read<K>(ring + cur * R::kSlot, lane, s, e4, xm, g);
-                cur = cur == D - 1 ? 0 : cur + 1;
-                const double ax = g[0] + g[2] * chx;
-                const double dy = (g[1] + g[3] * chy) - by;
-                const double dy2 = dy * dy;
-                double xw[K];
-#pragma unroll
-                for (int b = 0; b < K; ++b) xw[b] = hw.hw[b] * xm[b];
-                if (k < nDir) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) hm_entry<K, false, NR>(e4[j], ax - bx[j], dy2, xw, c[j]);
-                } else {
-                    double ob[K];
-#pragma unroll
-                    for (int b = 0; b < K; ++b) ob[b] = 0.0;
-                    if constexpr (XL) {
-                        double xr[4 * K];
-                        ring_read_xa<K>(lds_offset(xl) + 32 * K * q, xr);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) hm_entry2<K, NR>(e4[j], ax - bx[j], dy2, xw, xr + j * K, c[j], ob);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) hm_entry2<K, NR>(e4[j], ax - bx[j], dy2, xw, xa[j], c[j], ob);
-                    }
-#pragma unroll
-                    for (int i = 0; i < K; ++i) ob[i] = quad_sum(ob[i]);  // rows 4q'+j over the quad
-                    if (q == 0) {
-                        const int sl = __builtin_amdgcn_readlane(mySlot, k);
-                        const unsigned d = accOff + (unsigned)(((sl * kRank + s) * K) * 8);
-#pragma unroll
-                        for (int i = 0; i < K; ++i)
-                            asm volatile("ds_add_f64 %0, %1" ::"v"(d + 8 * i), "v"((i & 1) ? -ob[i] : ob[i]));
-                    }
-                }
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)");  // the partner adds, before the compiler's LDS ops
-        m2l_hc_store_target<K>(c, acc + (size_t)ti * RK, lane, s, q);
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-    hc_flush<K>(cs, a, acc);
-}
-
-template <int K, int NR, int D, bool XL, int WPE>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) k_m2l_hcr(HcArgs a) {
-    extern __shared__ double sm[];
-    m2l_hcr_cluster<K, NR, D, XL>((int)blockIdx.x, a, sm);
-}
-
 // WPE, the cluster form's occupancy: 3 = 4-wave workgroups at 3 waves per SIMD (3 per
 // CU); 6 = 6-wave workgroups at 3 waves per SIMD (2 per CU: the halo form's 64-target
-// clusters need ~72 KB of LDS); 4 = the LR form (<= 128 VGPRs) in 4-wave workgroups;
-// 8 = the LR form with 8 waves (512 threads) per cluster, 2 clusters per CU
+// clusters need ~72 KB of LDS)
 template <int WPE>
-constexpr int kHcThreads = WPE == 8 ? 512 : WPE == 6 ? 384 : 256;
-template <int WPE>
-constexpr int kHcWaves = WPE == 8 ? 4 : WPE == 6 ? 3 : WPE;
-template <int WPE>
-constexpr bool kHcLR = WPE == 4 || WPE == 8;
+constexpr int kHcThreads = WPE == 6 ? 384 : 256;
 
 template <int K, int NR, int WPE, bool DET = false>
-__global__ void __launch_bounds__(kHcThreads<WPE>) __attribute__((amdgpu_waves_per_eu(kHcWaves<WPE>)))
+__global__ void __launch_bounds__(kHcThreads<WPE>) __attribute__((amdgpu_waves_per_eu(3)))
 k_m2l_hc(HcArgs a) {
     extern __shared__ double sm[];
-    m2l_hc_cluster<K, NR, kHcLR<WPE>, DET>((int)blockIdx.x, a, sm);
+    m2l_hc_cluster<K, NR, DET>((int)blockIdx.x, a, sm);
 }
 
 // ----------------------------------------------------------------- fused top of tree + M2L
@@ -949,21 +675,9 @@ __device__ __forceinline__ void top_mark(const TopArgs& t, int field) {
     }
 }
 
-template <int K, int NR, int D, bool XL, bool LR = false>
-__device__ __forceinline__ void m2l_cluster_form(int cid, const HcArgs& a, double* sm) {
-    if constexpr (D == 0) m2l_hc_cluster<K, NR, LR>(cid, a, sm);
-    else m2l_hcr_cluster<K, NR, D, XL>(cid, a, sm);
-}
-
-template <int K, int U, int NR, bool FUSE, bool SYM = false, bool UP = false, bool OFF = false>
-__device__ __forceinline__ void near_hs_group(int g, const NearHsArgs& n, double* tab, int i0 = 0, int b0 = 0);
-
-// NEAR: the staged near field's groups (k_near_hs with fused corrections) are the last
-// blocks (ANISO_NEAR_IN_TOP).  The dispatcher hands out blocks in
-// order, so they take the slots the clusters free at the launch's tail.
-template <int K, int NR, int WPE, int D, bool XL, bool TRACE = false, bool NEAR = false>
-__global__ void __launch_bounds__(kHcThreads<WPE>) __attribute__((amdgpu_waves_per_eu(kHcWaves<WPE>)))
-k_top_m2l_hc(UpArgs u, TopArgs t, HcArgs a, NearHsArgs n) {
+template <int K, int NR, int WPE, bool TRACE = false>
+__global__ void __launch_bounds__(kHcThreads<WPE>) __attribute__((amdgpu_waves_per_eu(3)))
+k_top_m2l_hc(UpArgs u, TopArgs t, HcArgs a) {
     extern __shared__ double sm[];
     const int b = (int)blockIdx.x;
     top_mark<TRACE>(t, 0);
@@ -980,26 +694,18 @@ k_top_m2l_hc(UpArgs u, TopArgs t, HcArgs a, NearHsArgs n) {
         return;
     }
     const int cid = b - t.nUp;
-    if constexpr (NEAR) {
-        if (cid >= t.nCl) {
-            top_mark<TRACE>(t, 1);
-            near_hs_group<K, 4, 2, true>(cid - t.nCl, n, sm);
-            top_mark<TRACE>(t, 2);
-            return;
-        }
-    }
     const int w = t.clWait[cid];
     if (w > 0) {  // its own copy: behind the wait's fence the source boxes load through the vector path
         top_ensure<K>(t, u, w, sm);
         top_mark<TRACE>(t, 1);
-        m2l_cluster_form<K, NR, D, XL, kHcLR<WPE>>(cid, a, sm);
+        m2l_hc_cluster<K, NR>(cid, a, sm);
         top_mark<TRACE>(t, 2);
         return;
     }
     // no store or fence on the way here, so the compiler keeps the wave-uniform
     // source-box reads (ncx[B] ...) on scalar loads as in k_m2l_hc
     top_mark<TRACE>(t, 1);
-    m2l_cluster_form<K, NR, D, XL, kHcLR<WPE>>(cid, a, sm);
+    m2l_hc_cluster<K, NR>(cid, a, sm);
     top_mark<TRACE>(t, 2);
 }
 
@@ -1286,10 +992,10 @@ __device__ __forceinline__ void near_up_tail(int g, bool active, int nT, int64_t
     }
 }
 
-// OFF: the offset form (hm_rows_win with the pass's windows i0, b0; directed storage only)
-template <int K, int U, int NR, bool FUSE, bool SYM, bool UP, bool OFF>
-__device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, double* tab, int i0, int b0) {
-    static_assert(!(OFF && (SYM || UP)), "the offset form: the plain staged near field");
+// OFF: the offset form (hm_rows_win with the pass's windows i0, b0)
+template <int K, int U, int NR, bool FUSE, bool UP = false, bool OFF = false>
+__device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, double* tab, int i0 = 0, int b0 = 0) {
+    static_assert(!(OFF && UP), "the offset form: the plain staged near field");
     constexpr int KS = kStride<K>;
     constexpr int RW = kTabRow<K>;  // table row: x, y, the charges (padded)
     const int nl = n.nl;
@@ -1323,11 +1029,6 @@ __device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, 
             load_charges<K>(fT + (size_t)p * KS, f);
         }
     };
-    // SYM: symmetric U storage (NearHsArgs::colDst; its own instance: the canonical
-    // loop's registers would cost the directed kernel a wave per SIMD); the partner
-    // products within the group go to LDS slots after the table, 16 rows x K each
-    const bool sym = SYM && nearOn;
-    double* dslot = tab + (size_t)n.nsMax * RW;
     if (nearOn) {
         const int64_t r0 = nsPtr[g];
         const int nr = (int)(nsPtr[g + 1] - r0);
@@ -1342,10 +1043,6 @@ __device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, 
             for (int v = 0; v < K; ++v) row[2 + v] = f[v];
         }
     }
-#ifdef ANISO_NEAR_SYM_ATOMIC
-    if (sym)
-        for (int i = threadIdx.x; i < 256 * K; i += blockDim.x) dslot[i] = 0.0;
-#endif
     __syncthreads();
     const int gl = threadIdx.x & 15;
     const int li = g * 16 + (int)(threadIdx.x >> 4);
@@ -1358,8 +1055,7 @@ __device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, 
         koff = nearKOff[li];
     }
     const int nT = info.z;
-    // the directed columns (symmetric storage: the canonical blocks follow them)
-    const int S = !nearOn ? 0 : sym && active ? n.nearSym[li].x : info.w;
+    const int S = !nearOn ? 0 : info.w;
     const int64_t tb = info.y;
     const int nq = (nT + 3) >> 2;
     const int cstr = 2 * nq;
@@ -1423,73 +1119,6 @@ __device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, 
             step(kk, ix);
         }
     }
-    if constexpr (SYM) if (sym && active) {
-        // canonical partner blocks (the U pairs this leaf stores, bbfmm.h:1081-1099): one
-        // read of E(t, s) serves both ends -- this leaf's rows as above, and the
-        // partner's point s, whose product sums the leaf's rows (in-lane, then over the
-        // row quads by DPP: every lane of an active leaf takes part, padded rows read 0)
-        // and goes to the pair's LDS slot or to the partner's partial slot (colDst).
-        // The reversed direction has cos = -c: (-1)^b on the leaf's charges, (-1)^i on
-        // the product (as hm_entry2 in the cluster M2L).  UC columns in flight per lane.
-        constexpr int UC = 2;
-        double xa[4][K];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int t = 4 * rq + j;
-            const double* row = tab + (size_t)(n.selfRow[li] + min(t, max(nT - 1, 0))) * RW + 2;
-#pragma unroll
-            for (int b = 0; b < K; ++b) xa[j][b] = t < nT ? ((b & 1) ? -hw.hw[b] : hw.hw[b]) * row[b] : 0.0;
-        }
-        const dbl2* kc = reinterpret_cast<const dbl2*>(E + koff) + 2 * rq;
-        const int S1 = n.nearSym[li].y;
-        const int* __restrict__ dst = n.colDst + pb;
-        for (int c0 = S + cph; c0 < S1; c0 += UC * 4) {
-            dbl2 kk[UC][2];
-            int ix[UC], dd[UC];
-#pragma unroll
-            for (int u = 0; u < UC; ++u) {
-                const int sc = min(c0 + u * 4, S1 - 1);
-                const bool ok = c0 + u * 4 < S1 && rq < nq;
-                const dbl2* p = kc + (size_t)sc * cstr;
-                kk[u][0] = ok ? __builtin_nontemporal_load(p) : dbl2{0.0, 0.0};
-                kk[u][1] = ok ? __builtin_nontemporal_load(p + 1) : dbl2{0.0, 0.0};
-                ix[u] = nearLoc[pb + sc];
-                dd[u] = dst[sc];
-            }
-#pragma unroll
-            for (int u = 0; u < UC; ++u) {
-                if (c0 + u * 4 >= S1) break;  // uniform over the quad (one column phase)
-                const double* row = tab + (size_t)ix[u] * RW;
-                const double sx = row[0], sy = row[1];
-                double xw[K], ob[K];
-#pragma unroll
-                for (int b = 0; b < K; ++b) {
-                    xw[b] = hw.hw[b] * row[2 + b];
-                    ob[b] = 0.0;
-                }
-                const double e4[4] = {kk[u][0].x, kk[u][0].y, kk[u][1].x, kk[u][1].y};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const double dy = sy - ty[j];
-                    hm_entry2<K, NR>(e4[j], sx - tx[j], dy * dy, xw, xa[j], a[j], ob);
-                }
-#pragma unroll
-                for (int i = 0; i < K; ++i) ob[i] = quad_sum(ob[i]);  // the leaf's rows: over the row quads
-                // lane rq of the quad stores products i = rq (and rq + 4)
-#pragma unroll
-                for (int i = 0; i < K; ++i) {
-                    if ((i & 3) != rq) continue;
-                    const double v = (i & 1) ? -ob[i] : ob[i];
-#ifdef ANISO_NEAR_SYM_ATOMIC
-                    if (dd[u] < 0) atomicAdd(dslot + (size_t)(~dd[u]) * K + i, v);
-#else
-                    if (dd[u] < 0) dslot[(size_t)(~dd[u]) * K + i] = v;
-#endif
-                    else n.nearPart[(size_t)dd[u] * K + i] = hw.om[i] * v;
-                }
-            }
-        }
-    }
 #pragma unroll
     for (int j = 0; j < 4; ++j)  // sum over the column phases
 #pragma unroll
@@ -1499,7 +1128,6 @@ __device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, 
             v += dpp_f64<0x128>(v);  // row_ror:8
             a[j][i] = v;
         }
-    if (sym) __syncthreads();  // every partner product of the group is in LDS
     double fq[K];  // the lane's point's weighted charges (the fused up tail's P2M)
 #pragma unroll
     for (int i = 0; i < K; ++i) fq[i] = 0.0;
@@ -1508,23 +1136,6 @@ __device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, 
         double av[K];
 #pragma unroll
         for (int i = 0; i < K; ++i) av[i] = cph == 0 ? a[0][i] : cph == 1 ? a[1][i] : cph == 2 ? a[2][i] : a[3][i];
-#ifdef ANISO_NEAR_SYM_ATOMIC
-        if (sym && t < nT) {
-            const double* d = dslot + ((size_t)(li & 15) * 16 + t) * K;
-#pragma unroll
-            for (int i = 0; i < K; ++i) av[i] += d[i];
-        }
-        if (false) {
-#else
-        if (sym && t < nT) {  // the products this group's smaller-id partners left for the row, in slot order
-#endif
-            const int q1 = n.grpInPtr[li + 1];
-            for (int q = n.grpInPtr[li]; q < q1; ++q) {
-                const double* d = dslot + ((size_t)n.grpIn[q] * 16 + t) * K;
-#pragma unroll
-                for (int i = 0; i < K; ++i) av[i] += d[i];
-            }
-        }
         if (t < nT) {
             const int64_t k = tb + t;
             double f[K];
@@ -1560,19 +1171,13 @@ __device__ __forceinline__ void near_hs_group(const int g, const NearHsArgs& n, 
     if constexpr (UP) near_up_tail<K>(g, active, nT, tb, info.x, n, fq, tab);
 }
 
-// the staged near field's LDS: the source table, and with symmetric U storage the
-// group's partner product slots (16 rows x K each)
+// the staged near field's LDS: the source table
 template <int K>
 static size_t near_hs_lds(const NearHsArgs& n) {
-    const size_t tab = (size_t)n.nsMax * kTabRow<K> * sizeof(double) +
-                       (n.colDst ? (size_t)n.grpSlots * 16 * K * sizeof(double) : 0);
+    const size_t tab = (size_t)n.nsMax * kTabRow<K> * sizeof(double);
     return std::max(tab, n.upMult ? near_up_lds_doubles(K) * sizeof(double) : (size_t)0);  // the up tail reuses the table
 }
 
-// W4: capped at 128 VGPRs (4 waves per SIMD; ANISO_NEAR_WPE=4)
-#ifndef ANISO_NEAR_SYM_WPE
-#define ANISO_NEAR_SYM_WPE 1
-#endif
 template <bool OFF>
 struct NearHsArg : NearHsArgs {};
 template <>
@@ -1581,15 +1186,16 @@ struct NearHsArg<true> : NearHsArgs {
 };
 static_assert(sizeof(NearHsArg<false>) == sizeof(NearHsArgs), "the flag-off kernels take NearHsArgs as it is");
 
-template <int K, int U, int NR, bool FUSE, bool W4 = false, bool SYM = false, bool UP = false, bool OFF = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W4 ? 4 : SYM ? ANISO_NEAR_SYM_WPE : 1))) k_near_hs(NearHsArg<OFF> n) {
+// W4: capped at 128 VGPRs (4 waves per SIMD); the offset form's windows need more
+template <int K, int U, int NR, bool FUSE, bool W4, bool UP = false, bool OFF = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W4 ? 4 : 1))) k_near_hs(NearHsArg<OFF> n) {
     extern __shared__ double tab[];
     // the fused top-of-tree launch's counters (the bottom tier launch that zeroes them is skipped)
     if (n.zeroCnt && blockIdx.x == 0 && threadIdx.x <= kMaxTopTiers) n.zeroCnt[threadIdx.x] = 0u;
     if constexpr (OFF)
-        near_hs_group<K, U, NR, FUSE, SYM, UP, true>(n.grpList ? n.grpList[blockIdx.x] : (int)blockIdx.x, n, tab, n.i0,
-                                                     n.b0);
-    else near_hs_group<K, U, NR, FUSE, SYM, UP>(n.grpList ? n.grpList[blockIdx.x] : (int)blockIdx.x, n, tab);
+        near_hs_group<K, U, NR, FUSE, UP, true>(n.grpList ? n.grpList[blockIdx.x] : (int)blockIdx.x, n, tab, n.i0,
+                                                n.b0);
+    else near_hs_group<K, U, NR, FUSE, UP>(n.grpList ? n.grpList[blockIdx.x] : (int)blockIdx.x, n, tab);
 }
 
 
@@ -1626,68 +1232,16 @@ void launch_m2l_hm(int K, const PairList& pl, const double* E, const NodeBoxes& 
     HIP_LAUNCH_CHECK();
 }
 
-// clustered M2L (the default): 4 waves per cluster of <= 64 targets (512 / 768
-// threads, 2 waves per SIMD, 128-target clusters, a software-pipelined stream and an
-// XCD-contiguous cluster order all measured equal or slower, r01e-r01j), 3 waves per
-// SIMD; 1/r = v_rsq_f64 + ONE Newton step (~1e-13 relative per entry, 4 % faster
-// than two; the reduced-precision choice is tested at 1M points)
-size_t m2l_hc_lds(int K, int maxCl, int depth, bool xl, int nw) {
-    size_t b = (size_t)maxCl * kRank * K * sizeof(double);
-    if (depth == 0 || xl) b += (size_t)nw * kRank * K * sizeof(double);  // each wave's weighted target multipole
-    if (depth == 0) return b;
-    const size_t slot = 2048 + (size_t)kRank * K * 8 + 32;
-    return b + (size_t)nw * depth * slot;
-}
+// a cluster launch's LDS per workgroup of nw waves: the locals of the cluster and its
+// halo (maxCl slots), and each wave's weighted target multipole
+size_t m2l_hc_lds(int K, int maxCl, int nw) { return (size_t)(maxCl + nw) * kRank * K * sizeof(double); }
 
-// the ring form (k_m2l_hcr, the default) and its depth: ANISO_HM_RING=0 restores the
-// one-block-in-flight form (A/B runs), ANISO_HM_RING=2..4 sets the depth
-int hm_ring_depth() {
-    const char* e = std::getenv("ANISO_HM_RING");
-    const int v = e ? std::atoi(e) : 0;
-    return v == 0 ? 0 : std::max(2, std::min(4, v));
-}
+// The cluster form's workgroup: 3 waves per SIMD, in 4-wave
+// workgroups (3) where 3 fit per CU in LDS (shm4: the launch's LDS per workgroup with
+// 4 waves), else in 6-wave ones (6; the halo form's 64-target clusters: ~72 KB).
+static int hm_form(size_t shm4) { return 3 * shm4 <= 160 * 1024 ? 3 : 6; }
 
-// the ring form's target multipole: 1 in LDS (3 waves per SIMD), 0 in VGPRs (2 waves
-// per SIMD), -1 the ring form not used.  By default the LDS form where three
-// workgroups per CU fit in LDS with it (small clusters: shards); elsewhere the
-// one-block-in-flight form, which keeps 3 waves per SIMD there (r03m: at 64-target
-// clusters the ring's LDS allows 2 workgroups per CU and is 5-7 % slower).
-// ANISO_HM_RING_XL=0 / 1 forces the VGPR / LDS form.
-// K = 8 (aniso.m with more than 5 blocks) keeps the one-block-in-flight form: both
-// ring forms spill there, and a scratch store inside the stream would break the
-// counted vmcnt waits (stores retire out of order with the LDS-DMA loads).
-int hm_ring_xl(int K, int maxCl, int depth) {
-    if (K > kRingMaxK) return -1;
-    if (const char* e = std::getenv("ANISO_HM_RING_XL")) return std::atoi(e) != 0 ? 1 : 0;
-    return 3 * m2l_hc_lds(K, maxCl, depth, true, 4) <= 160 * 1024 ? 1 : -1;
-}
-
-#define ANISO_HM_DISPATCH_RING(d, CALL)                                            \
-    switch (d) {                                                                   \
-        case 0: { constexpr int DD = 0; CALL; } break;                             \
-        case 2: { constexpr int DD = 2; CALL; } break;                             \
-        case 3: { constexpr int DD = 3; CALL; } break;                             \
-        case 4: { constexpr int DD = 4; CALL; } break;                             \
-        default: throw std::invalid_argument("harmonic M2L: bad ring depth");      \
-    }
-
-// The one-block cluster form's occupancy, ANISO_HM_WPE:
-// 3 = 3 waves per SIMD in 4-wave workgroups; 6 = 3 waves per SIMD in 6-wave
-// workgroups (2 per CU); 4 = 4 waves per SIMD (<= 128 VGPRs, m2l_hc_cluster<LR>) in
-// 4-wave workgroups, which needs 4 of them per CU in LDS (small clusters: shards);
-// 8 = the LR form in 8-wave workgroups, 2 per CU.  The 4-wave-per-SIMD forms
-// measured slower (r03lr: a rank of 8 0.300 against 0.269 ms fused; one GPU with
-// 8-wave workgroups 1.300 against 1.324 ms, but 1.343 beside the 4-wave near field).
-// Default: 3 waves per SIMD, in 4-wave workgroups where 3 fit per CU in LDS
-// (shm4: the launch's LDS per workgroup with 4 waves), else in 6-wave ones (the halo
-// form's 64-target clusters: ~72 KB).
-static int hm_form(int K, int wpe, size_t shm4) {
-    if ((wpe == 4 || wpe == 8) && K <= kRingMaxK) return wpe;
-    if (wpe == 3 || wpe == 6) return wpe;
-    return 3 * shm4 <= 160 * 1024 ? 3 : 6;
-}
-
-static int hm_threads(int form) { return form == 8 ? 512 : form == 6 ? 384 : 256; }
+static int hm_threads(int form) { return form == 6 ? 384 : 256; }
 static int hm_waves(int form) { return hm_threads(form) / kWave; }
 
 template <typename F>
@@ -1706,38 +1260,15 @@ static void set_lds(F f, size_t shm) {
 // than two; the reduced-precision choice is tested at 1M points)
 void launch_m2l_hc(int K, int ncl, int maxCl, const HcArgs& a, hipStream_t s) {
     if (ncl <= 0) return;
-    const int depth = a.geo && K <= kRingMaxK ? a.ring : 0;
-    const bool xl = a.ringXL;
-    size_t shm = m2l_hc_lds(K, maxCl, depth, xl, 4);
-    const int form = depth == 0 ? hm_form(K, a.wpe, shm) : 3;
-    if (form != 3) shm = m2l_hc_lds(K, maxCl, depth, xl, hm_waves(form));
+    const int form = hm_form(m2l_hc_lds(K, maxCl, 4));
+    const size_t shm = m2l_hc_lds(K, maxCl, hm_waves(form));
     if (shm > 160 * 1024) throw std::invalid_argument("harmonic M2L: a cluster and its halo exceed the LDS");
-    if (a.wmax) {  // the deterministic sums: the one-block 3-wave-per-SIMD forms (whatever the ring knob says)
-        const int fd = hm_form(K, 0, shm);
-        const size_t shd = m2l_hc_lds(K, maxCl, 0, false, hm_waves(fd));
-        ANISO_HM_DISPATCH_K(K, ({
-            auto f = fd == 6 ? k_m2l_hc<KK, 1, 6, true> : k_m2l_hc<KK, 1, 3, true>;
-            set_lds(f, shd);
-            f<<<ncl, hm_threads(fd), shd, s>>>(a);
-        }));
-        HIP_LAUNCH_CHECK();
-        return;
-    }
-    ANISO_HM_DISPATCH_K(K, ANISO_HM_DISPATCH_RING(depth, ({
-        if constexpr (DD == 0 || KK > kRingMaxK) {
-            auto f = form == 6 ? k_m2l_hc<KK, 1, 6> : k_m2l_hc<KK, 1, 3>;
-            if constexpr (KK <= kRingMaxK) {
-                if (form == 4) f = k_m2l_hc<KK, 1, 4>;
-                if (form == 8) f = k_m2l_hc<KK, 1, 8>;
-            }
-            set_lds(f, shm);
-            f<<<ncl, hm_threads(form), shm, s>>>(a);
-        } else {
-            auto f = xl ? k_m2l_hcr<KK, 1, DD, true, 3> : k_m2l_hcr<KK, 1, DD, false, 2>;
-            set_lds(f, shm);
-            f<<<ncl, 256, shm, s>>>(a);
-        }
-    })));
+    ANISO_HM_DISPATCH_K(K, ({
+        auto f = a.wmax ? (form == 6 ? k_m2l_hc<KK, 1, 6, true> : k_m2l_hc<KK, 1, 3, true>)  // the deterministic sums
+                        : (form == 6 ? k_m2l_hc<KK, 1, 6> : k_m2l_hc<KK, 1, 3>);
+        set_lds(f, shm);
+        f<<<ncl, hm_threads(form), shm, s>>>(a);
+    }));
     HIP_LAUNCH_CHECK();
 }
 
@@ -1793,46 +1324,21 @@ bool top_fused_enabled() {
 #endif
 }
 
-void launch_top_m2l_hc(int K, int ncl, int maxCl, const UpArgs& u, const TopArgs& t0, const HcArgs& a,
-                       const NearHsArgs* near, hipStream_t s) {
-    if (t0.ntier < 2 || t0.ntier > kMaxTopTiers || t0.blk0[t0.ntier] != t0.nUp)
+void launch_top_m2l_hc(int K, int ncl, int maxCl, const UpArgs& u, const TopArgs& t, const HcArgs& a, hipStream_t s) {
+    if (t.ntier < 2 || t.ntier > kMaxTopTiers || t.blk0[t.ntier] != t.nUp)
         throw std::invalid_argument("fused top-of-tree launch: bad tier layout");
-    if (!t0.err) throw std::invalid_argument("fused top-of-tree launch: no time-out flag");
-    const int depth = a.geo && K <= kRingMaxK ? a.ring : 0;
-    if (near && (depth != 0 || near->nl <= 0))
-        throw std::invalid_argument("fused top-of-tree launch: the near field rides only with the one-block M2L");
-    if (near && near->colDst)
-        throw std::invalid_argument("fused top-of-tree launch: the near field rides only with directed U storage");
-    const bool xl = a.ringXL;
-    TopArgs t = t0;
-    t.nCl = ncl;
-    const NearHsArgs n = near ? *near : NearHsArgs{};
-    const unsigned nb = (unsigned)(t.nUp + ncl) + (near ? (unsigned)((near->nl + 15) / 16) : 0u);
-    ANISO_HM_DISPATCH_K(K, ANISO_HM_DISPATCH_RING(depth, ({
-        size_t shm = std::max(m2l_hc_lds(KK, maxCl, depth, xl, 4), up_tier_lds(u.maxTask, KK));
-        if (near) shm = std::max(shm, near_hs_lds<KK>(*near));
-        const int form = DD == 0 && !near ? hm_form(KK, a.wpe, shm) : 3;
-        if (form != 3) shm = std::max(shm, m2l_hc_lds(KK, maxCl, depth, xl, hm_waves(form)));
-        if (shm > 160 * 1024) throw std::invalid_argument("fused top-of-tree launch: a cluster and its halo exceed the LDS");
-        // the ring form with its target multipole in VGPRs needs ~216 of them at K = 5
-        if constexpr (DD == 0 || KK > kRingMaxK) {
-            auto f = near ? (t.trace ? k_top_m2l_hc<KK, 1, 3, 0, false, true, true>
-                                     : k_top_m2l_hc<KK, 1, 3, 0, false, false, true>)
-                          : (t.trace ? k_top_m2l_hc<KK, 1, 3, 0, false, true> : k_top_m2l_hc<KK, 1, 3, 0, false>);
-            if (form == 6) f = t.trace ? k_top_m2l_hc<KK, 1, 6, 0, false, true> : k_top_m2l_hc<KK, 1, 6, 0, false>;
-            if constexpr (KK <= kRingMaxK) {
-                if (form == 4) f = t.trace ? k_top_m2l_hc<KK, 1, 4, 0, false, true> : k_top_m2l_hc<KK, 1, 4, 0, false>;
-                if (form == 8) f = t.trace ? k_top_m2l_hc<KK, 1, 8, 0, false, true> : k_top_m2l_hc<KK, 1, 8, 0, false>;
-            }
-            set_lds(f, shm);
-            f<<<nb, hm_threads(form), shm, s>>>(u, t, a, n);
-        } else {
-            auto f = xl ? (t.trace ? k_top_m2l_hc<KK, 1, 3, DD, true, true> : k_top_m2l_hc<KK, 1, 3, DD, true>)
-                        : (t.trace ? k_top_m2l_hc<KK, 1, 2, DD, false, true> : k_top_m2l_hc<KK, 1, 2, DD, false>);
-            set_lds(f, shm);
-            f<<<nb, 256, shm, s>>>(u, t, a, n);
-        }
-    })));
+    if (!t.err) throw std::invalid_argument("fused top-of-tree launch: no time-out flag");
+    const unsigned nb = (unsigned)(t.nUp + ncl);
+    size_t shm = std::max(m2l_hc_lds(K, maxCl, 4), up_tier_lds(u.maxTask, K));
+    const int form = hm_form(shm);
+    if (form != 3) shm = std::max(shm, m2l_hc_lds(K, maxCl, hm_waves(form)));
+    if (shm > 160 * 1024) throw std::invalid_argument("fused top-of-tree launch: a cluster and its halo exceed the LDS");
+    ANISO_HM_DISPATCH_K(K, ({
+        auto f = form == 6 ? (t.trace ? k_top_m2l_hc<KK, 1, 6, true> : k_top_m2l_hc<KK, 1, 6>)
+                           : (t.trace ? k_top_m2l_hc<KK, 1, 3, true> : k_top_m2l_hc<KK, 1, 3>);
+        set_lds(f, shm);
+        f<<<nb, hm_threads(form), shm, s>>>(u, t, a);
+    }));
     HIP_LAUNCH_CHECK();
 }
 
@@ -1854,7 +1360,7 @@ bool near_hs_fusable(int nl, int maxLeaf, int nsMax, const uint16_t* nearLoc, co
 bool launch_near_hm(int K, const NearList& list, const double* E, const TreePoints& pts, const double* sigDiag,
                     const HarmWeights& hw, const double* fT, int flags, double scale, const OutRows& o,
                     const uint16_t* nearLoc, const int64_t* nsPtr, const int* nsPts, int nsMax, const NearCorr* corr,
-                    int wpe, hipStream_t s, const NearHsArgs* in, const HarmWindow* win) {
+                    hipStream_t s, const NearHsArgs* in, const HarmWindow* win) {
     const auto [nl, maxLeaf, leafInfo, nearPtsPtr, nearPts, nearKOff] = list;
     const auto [pxT, pyT] = pts;
     const int* const operm = o.perm;
@@ -1862,9 +1368,9 @@ bool launch_near_hm(int K, const NearList& list, const double* E, const TreePoin
     double* const out = o.out;
     if (nl <= 0) return false;
     // one pass of a block operator of more than kMaxRhs blocks: the offset form, K = kMaxRhs,
-    // the plain directed kernels only
-    if (win && (K != kMaxRhs || (in && (in->upMult || in->colDst))))
-        throw std::invalid_argument("harmonic near field: the offset form takes 8 blocks per pass, directed storage");
+    // the plain kernels only
+    if (win && (K != kMaxRhs || (in && in->upMult)))
+        throw std::invalid_argument("harmonic near field: the offset form takes 8 blocks per pass, no up tier");
     if (near_hs_staged(nl, maxLeaf, nsMax, nearLoc)) {  // sources staged in LDS (k_near_hs)
         unsigned ng = (unsigned)((nl + 15) / 16);
         // the corrections ride along when the table is loaded (near field on)
@@ -1881,8 +1387,7 @@ bool launch_near_hm(int K, const NearList& list, const double* E, const TreePoin
             n.wT = in->wT;
         }
         if (in && in->upMult) {  // the bottom up tier in the near field (the caller checked near_up_fits)
-            if (!fuse || in->colDst)
-                throw std::invalid_argument("near field with the up tier: not the staged directed kernel with its table");
+            if (!fuse) throw std::invalid_argument("near field with the up tier: not the staged kernel with its table");
             n.upMult = in->upMult;
             n.upGrp = in->upGrp;
             n.upP = in->upP;
@@ -1898,25 +1403,14 @@ bool launch_near_hm(int K, const NearList& list, const double* E, const TreePoin
             ng = (unsigned)in->ngrp;
             if (ng == 0) return fuse;
         }
-        if (in && in->colDst) {  // symmetric U storage (the column lists passed are its own)
-            if (!in->nearSym || !in->selfRow || !in->nearPart || !in->grpInPtr)  // grpIn: may be empty
-                throw std::invalid_argument("symmetric staged near field: missing lists");
-            n.nearSym = in->nearSym;
-            n.colDst = in->colDst;
-            n.selfRow = in->selfRow;
-            n.nearPart = in->nearPart;
-            n.grpInPtr = in->grpInPtr;
-            n.grpIn = in->grpIn;
-            n.grpSlots = in->grpSlots;
-        }
         if (win) {
             NearHsArg<true> na;
             static_cast<NearHsArgs&>(na) = n;
             na.i0 = win->i0;
             na.b0 = win->b0;
             const size_t shm = near_hs_lds<kMaxRhs>(n);
-            auto f = fuse ? k_near_hs<kMaxRhs, 2, 2, true, false, false, false, true>
-                          : k_near_hs<kMaxRhs, 2, 2, false, false, false, false, true>;
+            auto f = fuse ? k_near_hs<kMaxRhs, 2, 2, true, false, false, true>
+                          : k_near_hs<kMaxRhs, 2, 2, false, false, false, true>;
             f<<<ng, 256, shm, s>>>(na);
             HIP_LAUNCH_CHECK();
             return fuse;
@@ -1925,11 +1419,9 @@ bool launch_near_hm(int K, const NearList& list, const double* E, const TreePoin
         static_cast<NearHsArgs&>(na) = n;
         ANISO_HM_DISPATCH_K(K, ({
             const size_t shm = near_hs_lds<KK>(n);
-            auto f = n.colDst ? (fuse ? k_near_hs<KK, 4, 2, true, false, true> : k_near_hs<KK, 4, 2, false, false, true>)
-                     // with the up tail: the 4-wave form (<= 128 VGPRs)
-                     : fuse ? (n.upMult ? k_near_hs<KK, 2, 2, true, true, false, true>
-                               : wpe == 4 ? k_near_hs<KK, 2, 2, true, true> : k_near_hs<KK, 2, 2, true>)
-                            : (wpe == 4 ? k_near_hs<KK, 2, 2, false, true> : k_near_hs<KK, 2, 2, false>);
+            // 4 waves per SIMD (<= 128 VGPRs), with the up tail too
+            auto f = !fuse ? k_near_hs<KK, 2, 2, false, true>
+                     : n.upMult ? k_near_hs<KK, 2, 2, true, true, true> : k_near_hs<KK, 2, 2, true, true>;
             f<<<ng, 256, shm, s>>>(na);
         }));
         HIP_LAUNCH_CHECK();
@@ -1946,7 +1438,6 @@ bool launch_near_hm(int K, const NearList& list, const double* E, const TreePoin
         ANISO_HM_DISPATCH_K(K, (k_near_hm<KK, G, 4, 2><<<blocks_for((int64_t)nl * G, 256), 256, 0, s>>>(           \
                                    nl, leafInfo, nearPtsPtr, nearPts, nearKOff, E, pxT, pyT, sigDiag,              \
                                    harm_arg<false>(hw, nullptr), fT, operm, obase, ldo, flags, scale, out)))
-    if (in && in->colDst) throw std::invalid_argument("symmetric near storage needs the staged near field");
     if (in && in->grpList) throw std::invalid_argument("a near-field group subset needs the staged near field");
     if (maxLeaf <= 16) {
         ANISO_NEAR_HM(16);

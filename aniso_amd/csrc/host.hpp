@@ -109,42 +109,12 @@ struct Plan {
     // (0xFFFF outside the grid), so k_near_hs applies the corrections from its table
     std::vector<uint16_t> nearCorrRow;
     bool nearCorrOk = false;
-    // input: the staged near field of block handles with symmetric U storage (DESIGN.md
-    // §3.11): a U pair of two owned leaves <= 16 points is stored once, by its smaller
-    // id, whose lanes apply it both ways from one read.  The partner's product goes to
-    // LDS when the partner is in the same 16-leaf group, else to a partial slot the
-    // down pass adds (nearInPtr / nearInOff).  Per leaf: hsSym = (directed columns,
-    // all columns: the canonical ones, partner by partner, follow the directed ones),
-    // per column hsDst = where its partner product goes (>= 0 the partial slot of that
-    // point, < 0 ~(its LDS row: group slot x 16 + point); 0 for directed columns), and
-    // nearSelfRow = the table row of the leaf's first point.  Built only when every
-    // owned leaf fits the staged kernel (nearSymHsOn), else the harmonic near field
-    // reads the directed lists.
-    bool nearSymHs = false;
-    bool nearSymHsOn = false;
-    std::vector<int> hsDst;
-    std::vector<uint16_t> nearSelfRow;
-    // its column lists (beside the directed nearPtsPtr / nearLoc / nearKOff, which the
-    // per-mode kernels keep): table rows per column, E offsets, (directed, all)
-    // columns per leaf, source nodes per leaf (the att cache build), partial slots
-    std::vector<int64_t> hsPtsPtr, hsKOff, hsSrcPtr;
-    std::vector<uint16_t> hsLoc;
-    std::vector<std::array<int, 2>> hsSym;
-    std::vector<int> hsSrc;
-    int64_t hsKTotal = 0, hsPartTotal = 0, hsStored = 0;
-    // the partner products within a 16-leaf group go to LDS slots (16 rows x K each,
-    // one per in-group canonical block, <= kNearGrpSlots per group; the rest to
-    // partials): per leaf the slots it receives (CSR, ascending), summed in that
-    // fixed order -- no atomics, so the apply stays deterministic
-    static constexpr int kNearGrpSlots = 48;
     // the bottom up tier inside the staged near field (one rank): every
     // 16-leaf group is exactly one tier-0 subtree (a root, 4 parents, 16 leaves, all
     // non-empty) -- then per group 25 ints (NearHsArgs::upGrp): per leaf (parent slot
     // << 2 | quadrant), per parent its quadrant, the parents' nodes, the root node
     std::vector<int> nearUpGrp;
     bool nearUpOk = false;
-    std::vector<int> nearGrpInPtr, nearGrpIn;
-    int nearGrpSlots = 0;
     int64_t nearKTotal = 0;
     std::vector<int> m2lTgt;                   // active target nodes with M2L work
     std::vector<int64_t> m2lPtr;               // CSR over m2lTgt -> source nodes
@@ -282,10 +252,6 @@ struct Plan {
     int xUpTop = 0;
     std::vector<int> xUpTask;
     std::vector<int> xUpRecNode;  // per record of this rank: its upper node
-    // the partial tasks as tails of the bottom tier: per xOwnT0Tasks entry {16 p + q
-    // (its root is slot q of partial task p; -1: none), its root node}, and per partial
-    // task its root count
-    std::vector<int> xT0Part, xUpRoots;
 
     void build(const Tree& t, int np, int rank, int nranks);
     // the exchange plan above; sz / d2: the square grid of the correction stencil
@@ -297,7 +263,6 @@ struct Plan {
     void buildUpTasks(const Tree& t);
     void buildClusters(const Tree& t);
     void buildDownTasks(const Tree& t);
-    void buildNearHs(const Tree& t, const std::vector<int>& leafIdx);
     void buildNearUp(const Tree& t);
 };
 

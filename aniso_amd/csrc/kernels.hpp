@@ -127,30 +127,12 @@ size_t down_tier_lds(int maxTask, int maxLeaves, int maxNear, int maxChain, int 
 // are tier-0 roots with a slot are read from the all-gathered records recv (and
 // stored to mult for the M2L); sendSlot / send -- a task root with a send slot also
 // stores its record into this rank's all-gather buffer.
-// The upper multipoles' partial tasks (Plan::xUpTask) as tails of the sharded
-// bottom tier: block b's task root (node partOf[b].y) is slot q of
-// partial task p (partOf[b].x = 16 p + q; -1: none).  The block copies its root
-// multipole write-through into stage[16 p + q]; the last of a partial task's
-// nroots[p] roots to finish (an agent-scope counter, cnt[p], reset by that block)
-// runs it from the staged roots, storing its records into rec and into each of nPeer
-// parts at peerOff (doubles into buf, the exchange's send buffer).
-struct UpTail {
-    const int2* partOf = nullptr;
-    double* stage = nullptr;
-    unsigned* cnt = nullptr;
-    const int* nroots = nullptr;
-    const int* task = nullptr;
-    double* rec = nullptr;
-    int nPeer = 0;
-    const int64_t* peerOff = nullptr;
-    double* buf = nullptr;
-};
 void launch_up_tier(int K, int ntask, int taskBase, const int* taskList, int maxTask, const int4* desc,
                     const int* grpFix, const int* node, const int4* code, const double4* geom, const int2* leafRange,
                     const double* pxT, const double* pyT, const double* xin, int64_t ldi, int treeIn, const int* perm,
                     const double* sigT, const double* wT, double* fT, double* cT, const Params* P, double* mult,
                     const int* rootSlot, const double* recv, const int* sendSlot, double* send, hipStream_t s,
-                    unsigned* zeroCnt = nullptr, const UpTail* tail = nullptr);
+                    unsigned* zeroCnt = nullptr);
 // config 5's fp32 operator (f32op.hip): node expansions as 64 lanes x float4
 // (void* below), vectors point-major N x 16 floats
 void launch32_p2m(int nleaf, const int* leaves, const int64_t* begin, const int64_t* count, const double* ncx,
@@ -254,10 +236,6 @@ struct HcArgs {
     HarmWeights hw;
     const double* mult;
     double* local;
-    const double* geo = nullptr;  // per node {cx, cy, rx, ry} (the ring form, k_m2l_hcr)
-    int ring = 0;                 // host: the ring form's depth (0: the one-block-in-flight form)
-    bool ringXL = false;          // host: the ring form keeps the target multipole in LDS (3 waves / SIMD)
-    int wpe = 0;                  // host: the cluster form's occupancy (harmonic.hip hm_form; 0: the default)
     // the halo form (Plan::hmHaloPtr): cluster c's halo slots h = haloPtr[c] ..
     // haloPtr[c+1] - 1 go to partial haloPos[h] of hpart (16 x K doubles each, stored
     // scaled, receiver-contiguous: the down pass adds them to the locals)
@@ -311,7 +289,6 @@ struct TopArgs {
     unsigned* steals;             // persistent count of tier tasks computed by a waiting block (aniso_stats)
     unsigned* err;                // host-visible sticky flag (kept for the ABI; the launch no longer sets it)
     int64_t* trace;               // development (ANISO_TOP_TRACE=1): per block {start, waited, end, hw id}
-    int nCl;                      // cluster blocks (set by the launcher); near-field groups follow them
 };
 // the fused corrections of the staged near field (d = 1; harmonic.hip k_near_hs)
 struct NearCorr {  // the fused corrections of k_near_hs (d = 1), or ignored when rows == nullptr
@@ -323,8 +300,7 @@ struct NearCorr {  // the fused corrections of k_near_hs (d = 1), or ignored whe
     const double* Wm;
     const Params* P;
 };
-// the staged near field's arguments (harmonic.hip k_near_hs, and the last blocks of
-// k_top_m2l_hc when the near field rides in that launch): 16 leaves per group
+// the staged near field's arguments (harmonic.hip k_near_hs): 16 leaves per group
 struct NearHsArgs {
     int nl;                  // target leaves
     int nsMax;               // largest source table (rows)
@@ -356,18 +332,6 @@ struct NearHsArgs {
     const int* perm = nullptr;
     const double* sigT = nullptr;
     const double* wT = nullptr;
-    // symmetric U storage (Plan::nearSymHsOn; colDst == nullptr: every column
-    // directed): per leaf (directed columns, all columns), per column where its
-    // partner product goes, the leaf's first table row; partials of other groups
-    const int2* nearSym = nullptr;
-    const int* colDst = nullptr;
-    const uint16_t* selfRow = nullptr;
-    double* nearPart = nullptr;
-    // the in-group partner products' LDS slots (Plan::nearGrpIn): per leaf the slots
-    // it receives, and the most slots of a group (the launch's LDS)
-    const int* grpInPtr = nullptr;
-    const int* grpIn = nullptr;
-    int grpSlots = 0;
     // the 16-leaf groups to run (ngrp of them; nullptr: all, in order): a sharded
     // apply's one-collective form runs the groups that read only the own range before
     // the exchange and the rest after it (Plan::nearGrpEarly / nearGrpLate)
@@ -395,10 +359,7 @@ constexpr int kNearUpInts = 25;
 // (8 Chebyshev weights + K charges), then the 4 parents' 16 x K
 inline size_t near_up_lds_doubles(int K) { return (size_t)256 * (8 + K) + 4 * 16 * K; }
 bool top_fused_enabled();
-// near: the staged near field with its corrections fused (near_hs_fusable) as the
-// launch's last blocks, or nullptr (it runs as a launch of its own)
-void launch_top_m2l_hc(int K, int ncl, int maxCl, const UpArgs& u, const TopArgs& t, const HcArgs& a,
-                       const NearHsArgs* near, hipStream_t s);
+void launch_top_m2l_hc(int K, int ncl, int maxCl, const UpArgs& u, const TopArgs& t, const HcArgs& a, hipStream_t s);
 // whether launch_near_hm would run the staged near field with fused corrections
 bool near_hs_fusable(int nl, int maxLeaf, int nsMax, const uint16_t* nearLoc, const NearCorr* corr, int flags);
 void launch_m2l_hc(int K, int ncl, int maxCl, const HcArgs& a, hipStream_t s);
@@ -406,16 +367,13 @@ void launch_m2l_hc(int K, int ncl, int maxCl, const HcArgs& a, hipStream_t s);
 // sum_b |hw_b mult_b|; out[0] = max |x|
 void launch_node_wmax(int K, int nnodes, const double* mult, const HarmWeights& hw, double* out, hipStream_t s);
 void launch_abs_max(int64_t n, const double* x, double* out, hipStream_t s);
-
-int hm_ring_depth();  // ANISO_HM_RING (read at handle creation): the cluster M2L's LDS ring depth
-int hm_ring_xl(int K, int maxCl, int depth);  // its target multipole in LDS / VGPRs / ring off (1, 0, -1)
 // returns true when the corrections were fused (the caller skips launch_corr)
 bool launch_near_hm(int K, const NearList& list, const double* E, const TreePoints& pts, const double* sigDiag,
                     const HarmWeights& hw, const double* fT, int flags, double scale, const OutRows& o,
                     const uint16_t* nearLoc, const int64_t* nsPtr, const int* nsPts, int nsMax, const NearCorr* corr,
-                    int wpe, hipStream_t s,
+                    hipStream_t s,
                     const NearHsArgs* in = nullptr,  // in->xin: the staged kernel's charges from the input
-                    const HarmWindow* win = nullptr);  // win: the offset form (K = 8, directed storage)
+                    const HarmWindow* win = nullptr);  // win: the offset form (K = 8)
 // out[i] = a[i] (add == 0) or out[i] += a[i], rows i < nrhs of n entries: the sum over a block operator's passes
 void launch_add_rows(int64_t n, int nrhs, const double* a, int64_t lda, double* out, int64_t ldo, int add,
                      hipStream_t s);

@@ -158,7 +158,7 @@ int aniso_forward_solve_calls(aniso_handle h, int *counts, int cap, int *n);
  * columns report {8, 4}, one column {2}.  A mode made resident by aniso_cache(h, id) at
  * np = 4 runs the batched branch of the block apply: one entry per chunk of up to 8 columns,
  * K = 1, 2, 4, 5 or 8 (11 columns: {8, 4}; one column: {1}).  A lean np = 4 mode the mode
- * kernels do not serve (ANISO_NEAR_HS_SYM=1) reports 8, the offset form's rows, once per
+ * kernels do not serve (symmetric near storage) reports 8, the offset form's rows, once per
  * column.  Host only. */
 int aniso_mode_apply_calls(aniso_handle h, int *counts, int cap, int *n);
 /* the near-field launches of the handle's last aniso_mapping_multi(_dev) / aniso_forward_multi_dev

@@ -649,42 +649,38 @@ def test_harmonic_symmetric_blocks_match_directed(sz, d, ks, monkeypatch):
     assert _rel(outs[0], outs[1]) <= 1e-13
 
 
-@pytest.mark.parametrize("sz,d,ks,ml,sym,ring", [(32, 1, 5, 20, "1", "3x"), (19, 2, 3, 20, "1", "3x"),
-                                                 (64, 1, 2, 20, "0", "3x"), (40, 1, 5, 3, "1", "3x"),
-                                                 (32, 1, 5, 20, "1", "0"), (32, 1, 5, 20, "1", "2x"),
-                                                 (32, 1, 5, 20, "1", "4x"), (24, 1, 8, 20, "1", "3x"),
-                                                 (19, 2, 3, 20, "1", "0"), (32, 1, 5, 20, "1", "3v"),
-                                                 (24, 1, 8, 20, "1", "3v"), (32, 1, 5, 20, "1", "3"),
-                                                 (32, 1, 5, 20, "1", "0w4"), (32, 1, 5, 20, "1", "0w3"),
-                                                 (64, 1, 2, 20, "0", "0w4"), (19, 2, 3, 20, "1", "0w4"),
-                                                 (24, 1, 8, 20, "1", "0w4"), (32, 1, 5, 20, "1", "0w6"),
-                                                 (32, 1, 5, 20, "1", "0h"), (19, 2, 3, 20, "1", "0h"),
-                                                 (32, 1, 5, 20, "1", "3xh"), (24, 1, 8, 20, "1", "0h")])
-def test_harmonic_clusters_match_per_target_waves(sz, d, ks, ml, sym, ring, monkeypatch):
+@pytest.mark.parametrize("sz,d,ks,ml,sym,tag", [(32, 1, 5, 20, "1", "3x"), (19, 2, 3, 20, "1", "3x"),
+                                                (64, 1, 2, 20, "0", "3x"), (40, 1, 5, 3, "1", "3x"),
+                                                (32, 1, 5, 20, "1", "0"), (32, 1, 5, 20, "1", "2x"),
+                                                (32, 1, 5, 20, "1", "4x"), (24, 1, 8, 20, "1", "3x"),
+                                                (19, 2, 3, 20, "1", "0"), (32, 1, 5, 20, "1", "3v"),
+                                                (24, 1, 8, 20, "1", "3v"), (32, 1, 5, 20, "1", "3"),
+                                                (32, 1, 5, 20, "1", "0w4"), (32, 1, 5, 20, "1", "0w3"),
+                                                (64, 1, 2, 20, "0", "0w4"), (19, 2, 3, 20, "1", "0w4"),
+                                                (24, 1, 8, 20, "1", "0w4"), (32, 1, 5, 20, "1", "0w6"),
+                                                (32, 1, 5, 20, "1", "0h"), (19, 2, 3, 20, "1", "0h"),
+                                                (32, 1, 5, 20, "1", "3xh"), (24, 1, 8, 20, "1", "0h")])
+def test_harmonic_clusters_match_per_target_waves(sz, d, ks, ml, sym, tag, monkeypatch):
     """The clustered harmonic M2L (in-cluster V pairs read once by
     the smaller id, both products, locals summed in LDS) against one wave per target
     (aniso_set_deterministic); odd sz (non-uniform tree), directed storage, a
-    maxLevel-limited tree; the LDS-ring form at depths 2-4 with the target multipole
-    in LDS (x) or VGPRs (v), every block count it compiles for (2, 4, 5, 8), the
-    one-block-in-flight form (ANISO_HM_RING=0) and the default choice between them, that
-    form at 4 waves per SIMD (w4: m2l_hc_cluster<LR>, <= 128 VGPRs; K = 8 keeps 3) and
-    at 3 (w3: 4-wave workgroups; w6: 6-wave ones).  By default cross-cluster pairs are
+    maxLevel-limited tree; every block count it compiles for (2, 4, 5, 8), in 4-wave
+    workgroups and (ks = 8) in 6-wave ones.  By default cross-cluster pairs are
     read once too (the halo form: partner products in LDS halo slots, folded into the
     locals after the launch); h: ANISO_HM_HALO=0, the directed copies instead.
     Also checks that in-cluster pairs exist, that the cluster plan reads fewer E
     blocks (the halo form: exactly the stored blocks), and that both deterministic
-    forms (one wave per target; the clusters with fixed-point LDS sums, which take the
-    one-block form whatever the ring knob says) repeat bitwise."""
+    forms (one wave per target; the clusters with fixed-point LDS sums) repeat
+    bitwise.
+    tag: h selects ANISO_HM_HALO=0; its other characters are a label only, so cases of
+    one geometry whose tags differ in those alone run the same form.  With 64-target
+    clusters (24, 1, 8) has 64 LDS slots at 8 blocks and takes the 6-wave workgroups;
+    every other case here takes the 4-wave ones."""
     torch = _torch()
     import aniso_amd
 
     monkeypatch.setenv("ANISO_SYMMETRIC", sym)
-    monkeypatch.setenv("ANISO_HM_RING", ring[0])
-    if len(ring) > 1 and ring[1] in "xv":
-        monkeypatch.setenv("ANISO_HM_RING_XL", "1" if ring[1] == "x" else "0")
-    if "w" in ring:
-        monkeypatch.setenv("ANISO_HM_WPE", ring[ring.index("w") + 1])
-    halo = "h" not in ring
+    halo = "h" not in tag
     monkeypatch.setenv("ANISO_HM_HALO", "1" if halo else "0")
     # 64-target clusters even at these sizes (the default depth keeps >= 512
     # clusters, which small trees only reach with 4-target clusters: no in-cluster pairs)
@@ -719,22 +715,19 @@ def test_harmonic_clusters_match_per_target_waves(sz, d, ks, ml, sym, ring, monk
     assert _rel(outs[0], outs[1]) <= 1e-13
 
 
-@pytest.mark.parametrize("ks,world,ring", [(5, 8, "3"), (2, 4, "3"), (3, 3, "3"), (5, 8, "0"), (5, 8, "0f"),
-                                           (5, 8, "0w4"), (2, 4, "0fw4"), (5, 8, "0fw4")])
-def test_small_clusters_on_shards_match_unsharded(ks, world, ring, monkeypatch):
+@pytest.mark.parametrize("ks,world,tag", [(2, 4, "3"), (3, 3, "3"), (5, 8, "0"), (5, 8, "0f"), (2, 4, "0fw4"),
+                                          (3, 3, "0f")])
+def test_small_clusters_on_shards_match_unsharded(ks, world, tag, monkeypatch):
     """The clustered M2L on the small clusters of an N-GPU shard (the adaptive depth
     gives 16-target clusters there) with 2, 4 (3 padded) and 5 blocks: every rank's
-    two-phase apply equals the unsharded operator (the LDS-ring cluster form and the
-    one-block-in-flight form; f: ANISO_TOP_FUSED=0, the upper tiers as launches of
-    their own; w4: the one-block form at 4 waves per SIMD)."""
+    two-phase apply equals the unsharded operator (the upper tiers inside the M2L
+    launch; f in the tag: ANISO_TOP_FUSED=0, as launches of their own; the tag's other
+    characters are a label only).  24 LDS slots per cluster: 4-wave workgroups."""
     torch = _torch()
     import aniso_amd
 
-    monkeypatch.setenv("ANISO_HM_RING", ring[0])
-    if "f" in ring:
+    if "f" in tag:
         monkeypatch.setenv("ANISO_TOP_FUSED", "0")
-    if "w4" in ring:
-        monkeypatch.setenv("ANISO_HM_WPE", "4")
     sz = 256
     full = aniso_amd.Aniso(sz, 1, ks, 0.8, 10, 4, 20)
     xy = full.getNodes()
@@ -752,14 +745,19 @@ def test_small_clusters_on_shards_match_unsharded(ks, world, ring, monkeypatch):
     assert err <= 1e-13, err
 
 
-@pytest.mark.parametrize("env", ["", "ANISO_DET_PER_TARGET=1", "ANISO_HM_HALO=0", "ANISO_HM_WPE=6"])
+@pytest.mark.parametrize("env", ["", "ANISO_DET_PER_TARGET=1", "ANISO_HM_HALO=0", "ANISO_HM_CLDEPTH=3",
+                                 "ANISO_HM_CLDEPTH=3,ANISO_TOP_FUSED=0"])
 def test_deterministic_block_matvec_repeats_bitwise_at_config3_size(env, monkeypatch):
     """aniso_set_deterministic at BASELINE's 1M-point block matvec: repeat applies
     are bitwise identical, and equal the default (clustered) matvec to 1e-13.  The
     default runs the upper up tiers inside the M2L launch (k_top_m2l_hc), so this
     also checks its in-launch hand-offs against the plain tier launches.  Forms: the
     clustered M2L with fixed-point LDS sums (the default deterministic mode; with and
-    without the halo slots, in 6-wave workgroups) and the round-2 per-target M2L."""
+    without the halo slots; ANISO_HM_CLDEPTH=3: 64-target clusters, whose 108 LDS slots
+    leave two workgroups per CU, so the fused launch and the deterministic cluster launch
+    take their 6-wave workgroups, and with ANISO_TOP_FUSED=0 the plain cluster launch too;
+    the other cases have 44 or 64 slots and take the 4-wave ones) and the round-2
+    per-target M2L."""
     torch = _torch()
     import aniso_amd
 
@@ -771,7 +769,7 @@ def test_deterministic_block_matvec_repeats_bitwise_at_config3_size(env, monkeyp
     a.setCoeff(*rough_coeffs(xy, 2))
     for m in range(9):
         a.cache(m)
-    assert a.stats()["top_fused"] == 1
+    assert a.stats()["top_fused"] == (0 if "ANISO_TOP_FUSED=0" in env else 1)
     U = torch.tensor(np.random.default_rng(8).uniform(-1, 1, (5, a.N)), device="cuda")
     ref = torch.zeros_like(U)
     a.block_op_dev(2, U, ref, tree=True)
@@ -871,14 +869,9 @@ def test_deterministic_fixed_point_sums_scale_and_block_counts(ks, scale):
     assert not torch.any(z)
 
 
-@pytest.mark.parametrize("knob", ["ANISO_OVERLAP=1", "ANISO_FUSE_SUB=0", "ANISO_HARMONIC=0", "ANISO_HM_RING=3",
-                                  "ANISO_HM_WPE=3", "ANISO_HM_WPE=4", "ANISO_HM_WPE=6", "ANISO_HM_WPE=8",
-                                  "ANISO_NEAR_IN_TOP=1,ANISO_OVERLAP=1", "ANISO_NEAR_WPE=3", "ANISO_TOP_FUSED=0",
+@pytest.mark.parametrize("knob", ["ANISO_OVERLAP=1", "ANISO_FUSE_SUB=0", "ANISO_HARMONIC=0", "ANISO_TOP_FUSED=0",
                                   "ANISO_HM_HALO=0", "ANISO_NEAR_EARLY=0", "ANISO_NEAR_EARLY=0,ANISO_OVERLAP=1",
-                                  "ANISO_NEAR_HS_SYM=1", "ANISO_NEAR_HS_SYM=1,ANISO_NEAR_EARLY=0",
-                                  "ANISO_NEAR_HS_SYM=1,ANISO_OVERLAP=1", "ANISO_NEAR_HS_SYM=1,ANISO_TOP_FUSED=0",
-                                  "ANISO_NEAR_ORDER=first,ANISO_OVERLAP=1", "ANISO_NEAR_UP=0", "ANISO_HM_TAIL=0",
-                                  "ANISO_HM_TAIL=100000"])
+                                  "ANISO_NEAR_UP=0", "ANISO_HM_TAIL=0", "ANISO_HM_TAIL=100000"])
 def test_block_matvec_knobs_agree(knob, monkeypatch):
     """Every remaining environment knob of the block apply:
     the near field on a side stream beside the up pass and the M2L (one GPU's
@@ -958,23 +951,19 @@ def _two_phase_shards(sz, d, ks, ml, coef, world, X, ref, g=0.8, ns=10):
     return float(torch.linalg.norm(got - ref) / torch.linalg.norm(ref)), nans, halo / X.shape[1]
 
 
-@pytest.mark.parametrize("sz,d,ks,ml,coeffs,world,sym", [
+@pytest.mark.parametrize("sz,d,ks,ml,coeffs,world,tag", [
     (64, 1, 5, 20, "main", 2, 0), (64, 1, 5, 20, "rough", 8, 0), (48, 2, 3, 20, "rough", 3, 0),
     (30, 3, 1, 20, "main", 4, 0), (40, 1, 2, 3, "rough", 3, 0), (16, 1, 5, 20, "main", 3, 0),
     (11, 3, 1, 20, "rough", 2, 0), (1, 3, 1, 20, "main", 2, 0), (64, 1, 5, 20, "rough", 3, 1),
     (48, 2, 3, 20, "rough", 2, 1)])
-def test_two_phase_sharded_apply_reads_only_own_and_halo(sz, d, ks, ml, coeffs, world, sym, monkeypatch):
+def test_two_phase_sharded_apply_reads_only_own_and_halo(sz, d, ks, ml, coeffs, world, tag):
     """The multi-GPU apply (own + halo up pass, tier-0 root all-gather, owned slice
     out) on NaN-poisoned inputs equals the unsharded tree-order operator: the
     exchange plan covers everything each rank's kernels read (uniform, odd-sized,
     maxLevel-limited and single-leaf trees; 1, 2, 3 (padded to 4) and 5 right-hand
-    sides; even and odd world sizes; sym: the near field's symmetric U storage,
-    whose pairs with a ghost leaf stay directed)."""
+    sides; even and odd world sizes; tag: a label of the case, not read)."""
     torch = _torch()
     import aniso_amd
-
-    if sym:
-        monkeypatch.setenv("ANISO_NEAR_HS_SYM", "1")
 
     full = aniso_amd.Aniso(sz, d, ks, 0.8, 10, 4, ml)
     xy = full.getNodes()
@@ -1792,8 +1781,7 @@ class _ThreadCollectives:
                                                (64, 8, "1", 1, 20), (64, 3, "1", 1, 20), (96, 3, "1", 1, 20),
                                                (40, 2, "1", 1, 3), (32, 2, "1", 2, 20), (64, 3, "mixed", 1, 20),
                                                (64, 2, "spin0", 1, 20), (256, 4, "1", 1, 20), (512, 8, "1", 1, 20),
-                                               (256, 4, "partial0", 1, 20), (512, 8, "tails", 1, 20),
-                                               (256, 4, "det", 1, 20)])
+                                               (256, 4, "partial0", 1, 20), (256, 4, "det", 1, 20)])
 def test_native_exchange_ranks_as_threads(sz, world, one, d, ml, monkeypatch):
     """The library's one-call sharded block matvec (aniso_block_op_sharded_dev) with
     `world` ranks as threads of one process on the box's GPU, each rank's input valid
@@ -1820,9 +1808,7 @@ def test_native_exchange_ranks_as_threads(sz, world, one, d, ml, monkeypatch):
 
     import aniso_amd
 
-    monkeypatch.setenv("ANISO_ONE_EXCHANGE", "1" if one in ("mixed", "spin0", "partial0", "tails", "det") else one)
-    # "tails": the upper partial tasks as tails of the own tier-0 launch (ANISO_UP_TAILS=1)
-    monkeypatch.setenv("ANISO_UP_TAILS", "1" if one == "tails" else "0")
+    monkeypatch.setenv("ANISO_ONE_EXCHANGE", "1" if one in ("mixed", "spin0", "partial0", "det") else one)
     monkeypatch.setenv("ANISO_UPPER_PARTIAL", "0" if one in ("spin0", "partial0") else "1")
     ks = 5
     full = aniso_amd.Aniso(sz, d, ks, 0.8, 10, 4, ml)
@@ -1885,7 +1871,7 @@ def test_native_exchange_ranks_as_threads(sz, world, one, d, ml, monkeypatch):
     assert not torch.isnan(Y).any()
     assert float(torch.linalg.norm(Y - ref) / torch.linalg.norm(ref)) <= 1e-13
     used = [h.stats()["one_exchange_applies"] for h in hs]
-    one_used = one in ("1", "spin0", "partial0", "tails", "det") and all(oks) and staged
+    one_used = one in ("1", "spin0", "partial0", "det") and all(oks) and staged
     assert used == [2 * int(one_used)] * world
     ups = [h.shard_upper_partials() for h in hs]
     assert [h.stats()["upper_partial_applies"] for h in hs] == [2 * int(one_used and all(u["on"] for u in ups))] * world
